@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the NGD Gauss-Hermite hot path on MI355X (contract: see the round prompt).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5|c3lit|planar1k|arm7x]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5|c3lit|planar1k|arm7x] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and what the timed steps
+themselves report (passes, accepted steps, final cost).  --full adds everything that takes work of its own: the
+reference-pass-order leg, event-timed stages, the dominant kernel's roofline, the c3lit chain, the CPU baseline and, for
+N > 1, the parity check against one GPU and the sharded c5 run.  --dump-outputs DIR writes the state the last timed step
+left (mean, precision blocks, marginal covariance blocks) and that step's record as float64 .npy files; the inputs are
+seeded, so two builds can be compared file by file.
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on): the synthetic 1024-factor LTV-prior
 chain, d = 12, sparse-GH p = 5 (N = 17 217 sigma points per factor), T = 1025 states of size 6, fp64, plus one unary
@@ -18,7 +25,7 @@ What the JSON line reports
                              passes only m0.  With the default adaptive scheduling an accepted iteration runs ONE full
                              pass (its m0 is the trial cost, its moments are the next gradients), so value ~ the
                              moments-pass rate; both rates are given separately as well.
-  roofline.frac              EXECUTED fp64 VALU issue slots of the dominant launch (each v_fma/v_mul/v_add_f64 counted
+  roofline.frac (--full)     EXECUTED fp64 VALU issue slots of the dominant launch (each v_fma/v_mul/v_add_f64 counted
                              as one FMA = 2 flop) / the 78.6 TF fp64 peak -- the fraction of the pipe that is used.
                              The SURVEY 8(d) algorithmic figure (638 flop per evaluation for the reference's x-space
                              formulation) is kept as roofline.algorithmic.
@@ -66,6 +73,25 @@ def ensure_library(rank: int) -> None:
         if time.time() - t0 > 900:
             raise SystemExit(f"rank {rank}: {_lib.LIB_PATH} did not appear (rank 0 builds it)")
         time.sleep(0.5)
+
+
+DUMP_LIMIT = 64 << 20      # bytes written by --dump-outputs at most
+
+
+def dump_outputs(out_dir, state, last):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the NGD state of gvi_ngd_get_state (mean
+    mu [T][n], joint precision blocks D [T][n][n] and U [T-1][n][n], marginal covariance blocks SigD / SigU) and that step's
+    record [cost_iter, new_cost, accepted, ntrials] -- as float64 .npy files.  A state larger than DUMP_LIMIT (a weak-scaling
+    chain over many GPUs) keeps every s-th block, s the smallest stride that fits: the same blocks in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    stride = 1
+    while sum(a[::stride].nbytes for a in state.values()) > DUMP_LIMIT:
+        stride += 1
+    for name, a in state.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[::stride], dtype=np.float64))
+    rec = np.array([last["cost_iter"], last["new_cost"], float(last["accepted"]), float(last["ntrials"])])
+    np.save(os.path.join(out_dir, "last_step.npy"), rec)
 
 
 KIND_NAMES = {0: "range-1D", 1: "quadratic-prior", 2: "fixed-prior", 4: "hinge-SDF-2D", 5: "hinge-SDF-2D-body", 6: "hinge-SDF-3D", 7: "hinge-SDF-3D-arm"}
@@ -196,8 +222,13 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", default="c3")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline line (A/B leg, stages, roofline, c3lit, CPU baseline; "
+                         "N > 1: parity against one GPU, c5_strong)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step and that step's record to DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: length of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--per-step-calls", action="store_true", help="one gvi_ngd_step call per iteration from Python instead of gvi_ngd_run blocks")
     ap.add_argument("--variant", type=int, default=0, help="0 auto, 1 generic, 2 register (LDS operands), 3 operand-resident, 5 register (SGPR operands), 6 sign-orbit")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
@@ -205,7 +236,7 @@ def main():
                          "by the replicated chain recursions and the exchange); weak: 1024 factors PER GPU, i.e. a (1024 N)-factor "
                          "chain (config c3xN) -- the metric string then names c3xN")
     ap.add_argument("--no-c5-strong", action="store_true",
-                    help="N > 1: skip the additional sharded run of BASELINE configs[4] (block `c5_strong` of the JSON line; ~80 s of set-up)")
+                    help="--full, N > 1: skip the additional sharded run of BASELINE configs[4] (block `c5_strong` of the JSON line; ~80 s of set-up)")
     ap.add_argument("--fuse-trial", type=int, default=2, choices=[0, 1, 2],
                     help="gvi_ngd_set_mode: 0 the reference's pass order (gradient pass + one cost pass per trial), 1 fused, "
                          "2 adaptive (library default)")
@@ -221,6 +252,8 @@ def main():
         args.steps = 3 if big else 200
     if args.warmup is None:
         args.warmup = 1 if big else 20
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -320,8 +353,10 @@ def main():
 
     transport = init_transport(ctx) if sharded else "none"
     ctx.ngd_init(chain["mu0"], chain["D0"], chain["U0"])
-    # HIP events around every 8th dominant launch (a pair costs ~14 us of queue gaps); every launch for the seconds-long c5 passes
-    ctx.profile_enable(1 if big else 3)
+    # --full: HIP events around every 8th dominant launch (a pair costs ~14 us of queue gaps); every launch for the seconds-long
+    # c5 passes.  A plain run records none.
+    if args.full:
+        ctx.profile_enable(1 if big else 3)
 
     def barrier():
         if use_pg:
@@ -380,7 +415,7 @@ def main():
                 restart(); pos = 0                          # timed: host upload + one refresh of the chain products
             r = step_fn(); pos += 1
             log.append(r)
-            if i % 8 == 7 or i == args.steps - 1:
+            if args.full and (i % 8 == 7 or i == args.steps - 1):
                 try:
                     kern_ms.append(ctx.profile_last(ids[0], 0))      # last bracketed launch (sampled: every 8th)
                 except api.GviError:
@@ -391,7 +426,9 @@ def main():
     elapsed = time.perf_counter() - t0
     gc.enable()
     n_full, n_cost = ctx.ngd_counters()
-    if single and not args.per_step_calls:
+    if args.dump_outputs and rank == 0:                 # before anything below moves the state on
+        dump_outputs(args.dump_outputs, ctx.ngd_get_state(), log[-1])
+    if args.full and single and not args.per_step_calls:
         # event time of the bracketed dominant launch: sampled OUTSIDE the timed region (reading an event pair is a host-side
         # synchronisation of ~30 us; inside a 20-step region it was 4 % of the line)
         for _ in range(1 if big else 8):
@@ -407,7 +444,7 @@ def main():
     # A/B leg (not part of `value`): the reference's pass order -- a cost-only pass per trial and a separate
     # gradient pass per iteration (gvi_ngd_set_mode fuse_trial = 0); same iterates, one more psi pass per iteration
     ab = None
-    if single and not big and args.fuse_trial != 0:
+    if args.full and single and not big and args.fuse_trial != 0:
         ctx.ngd_set_mode(True, 0)
         ctx.ngd_init(chain["mu0"], chain["D0"], chain["U0"])
         fpos = 0
@@ -452,7 +489,7 @@ def main():
     dom = int(np.argmax([K * N for (K, d, p, N) in ctx.sets])) if ctx.sets else 0
     chain_pattern = len(ctx.sets) <= 2 and all(spec["kind"] in (1, 2) for spec in local["specs"])
     stages = None
-    if single and not big:
+    if args.full and single and not big:
         def descending_steps(nsteps):                   # same restart rule as the timed region: every step an accepted one
             done = 0
             while done < nsteps:
@@ -509,13 +546,13 @@ def main():
         barrier()
         return out
 
-    parity = parity_vs_single_gpu(ctx, chain, min(12, args.restart_every)) if world > 1 else None
+    parity = parity_vs_single_gpu(ctx, chain, min(12, args.restart_every)) if args.full and world > 1 else None
 
     # ---- N > 1: BASELINE configs[4] (4096 factors, d = 24, p = 7; fp64) sharded over the same ranks, two iterations:
     # the workload whose factor pass (0.095 s on one GPU) dwarfs the replicated chain operations, i.e. where sharding has
     # work to split (strong scaling).  GVI_BENCH_C5_CONFIG selects a smaller d = 24 chain for rehearsals.
     c5_block = None
-    if world > 1 and not args.no_c5_strong:
+    if args.full and world > 1 and not args.no_c5_strong:
         cfg5 = os.environ.get("GVI_BENCH_C5_CONFIG", "c5")
         t_build = time.perf_counter()
         chain5 = synthetic.make_chain(cfg5)
@@ -578,7 +615,7 @@ def main():
     # ---- BASELINE configs[2] as SURVEY 8(d) writes it (`c3lit`: the 1024 LTV priors and two end anchors, no unary set,
     # cond(V) = 2.3e5): 20 driver-timed steps beside the default chain (which adds a unary factor per state)
     c3_literal = None
-    if world == 1 and args.config == "c3":
+    if args.full and world == 1 and args.config == "c3":
         lit = synthetic.make_chain("c3lit")
         cl, _ = api.context_for_chain(lit, device=local_rank)
         cl.ngd_set_mode(True, args.fuse_trial)
@@ -602,94 +639,13 @@ def main():
         cl.close()
 
     if rank == 0:
-        Kd, dd_, pd_, Nd = ctx.sets[dom]
         K0, d0, p0, N0 = ctx.sets[0]
         m0 = d0 // 2
         geo = ctx.profile_geometry(ids[dom])
-        km = float(np.mean(kern_ms)) * 1e-3 if kern_ms else float("nan")
-        kind_dom = int(local["specs"][dom]["kind"])
-
-        def weights_signed(spec):                      # any negative eigenvalue of the residual weight (Q^-1 / K^-1)?
-            W = spec.get("Qinv", spec.get("Kinv"))
-            return bool(np.linalg.eigvalsh(0.5 * (W + np.transpose(W, (0, 2, 1)))).min() <= 0.0)
-
         fused_launch = os.environ.get("GVI_FUSED", "1") != "0" and chain_pattern and geo["variant"] == 6 and geo["nchunk"] == 4 and \
             ((m0 == 6 and d0 == 12) or (m0 == 2 and d0 == 4))
         block3_launch = (os.environ.get("GVI_FUSED", "1") != "0" and os.environ.get("GVI_NO_PAIR", "0") == "0" and world == 1 and
                          [(int(sp["kind"]), int(sp["d"])) for sp in local["specs"]] == [(1, 8), (4, 4), (2, 4)])
-        executed_note = None
-        if chain_pattern:
-            sets_in_launch = [(K0, d0, m0, N0, weights_signed(local["specs"][0]))]
-            both = geo["variant"] in (5, 6) and len(ctx.sets) == 2
-            if both:
-                K1, d1, p1, N1 = ctx.sets[1]
-                sets_in_launch.append((K1, d1, d1, N1, weights_signed(local["specs"][1])))   # unary: m = d
-            if geo["variant"] == 6:
-                kernel_name = (f"factor_fused_kernel<{m0}, {4 if p0 <= 5 else 6}, ..., {d0}, {ctx.sets[1][1] if both else d0 // 2}> (gather + Cholesky products + "
-                               f"sign-orbit walk + chunk sum + cost tail + back-transform in one launch)") if fused_launch else \
-                    f"moments_orbit{'_pair' if both else ''}_kernel<{m0}, {4 if p0 <= 5 else 6}, full>"
-                p_of = {d: p for (K, d, p, N) in ctx.sets}
-                ops_of = lambda d, m, sg: orbit_exec_ops(d, p_of[d], m, True, sg)
-            elif geo["variant"] == 5:
-                kernel_name = f"moments_sreg_pair_kernel<{d0}, {m0}, {m0}, {m0}, full>"
-                mirror = os.environ.get("GVI_MIRROR", "1") != "0"
-                ops_of = lambda d, m, sg: exec_ops(d, m, True, sg, mirror)
-            elif geo["variant"] == 3:
-                kernel_name = f"moments_split_kernel<{d0}, {(m0 + 3) // 4}, full>"
-                ops_of = lambda d, m, sg: exec_ops(d, m, True, True) + 3 + 12      # four waves per factor: sign multiply, 4 partial psi sums
-            else:
-                kernel_name = f"moments_reg_kernel<{d0}, PsiQuad<{d0},{m0}>, full>" if geo["variant"] == 2 else "moments_generic_kernel"
-                ops_of = lambda d, m, sg: exec_ops(d, m, True, sg, False)
-            evals_launch = sum(K * N for K, d, m, N, sg in sets_in_launch)
-            exec_flop = sum(2 * ops_of(d, m, sg) * K * N for K, d, m, N, sg in sets_in_launch)
-            alg_flop = sum(alg_flops(d, m) * K * N for K, d, m, N, sg in sets_in_launch)
-            alg_bytes = sum(K * N * (d + 1) * 8 for K, d, m, N, sg in sets_in_launch)   # (d+1) s bytes per eval
-            ops_table = {f"d={d},m={m}": ops_of(d, m, sg) for K, d, m, N, sg in sets_in_launch}
-            launch_desc = ("every factor set, all stages of the pass" if fused_launch else
-                           ("prior set + unary set in one launch" if len(sets_in_launch) == 2 else "prior set"))
-        else:
-            # non-polynomial psi (hinge on a signed-distance field ...): the lane-per-point register kernel of the dominant set
-            per = REG_KERNEL_FP64_PER_EVAL.get((kind_dom, dd_))
-            kernel_name = (f"moments_reg_kernel<{dd_}, Psi[{KIND_NAMES.get(kind_dom, kind_dom)}], full>" if geo["variant"] == 2
-                           else "moments_generic_kernel")
-            evals_launch = Kd * Nd
-            exec_flop = 2.0 * per * evals_launch if per and geo["variant"] == 2 else float("nan")
-            alg_flop = float("nan")
-            alg_bytes = evals_launch * (dd_ + 1) * 8
-            ops_table = {f"kind={KIND_NAMES.get(kind_dom, kind_dom)},d={dd_}": per}
-            launch_desc = f"set {dom} ({KIND_NAMES.get(kind_dom, kind_dom)}, d = {dd_}, p = {pd_}: the set with the most evaluations)"
-            executed_note = ("fp64 VALU instructions per 64-point step counted in the ISA of the instance (REG_KERNEL_FP64_PER_EVAL), each as one "
-                             "FMA = 2 flop; the SDF look-up adds 4 x 8 B of gathered reads per evaluation from L2")
-        traffic, traffic_source, valu_issue = None, None, None
-        # PMC passes are separate runs (tools/gpu_pmc.sh); their per-launch figures are committed per config
-        tfile = TRAFFIC_FILE if args.config == "c3" else TRAFFIC_FILE.replace(".json", f"_{args.config}.json")
-        tpath = os.path.join(ROOT, tfile)
-        if world == 1 and os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if kernel_name.split("<")[0] in tj.get("kernel", ""):     # counters of the kernel that actually ran
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    traffic_source = (f"{tfile} (git blob {git_blob_sha1(tpath)}; rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                      "command; not re-measured in this run)")
-                    valu_issue = {"busy_frac": tj["derived"]["valu_pipe_busy"], "valu_instructions_per_launch": tj["sq"]["SQ_INSTS_VALU"],
-                                  "wait_frac_of_wave_cycles": tj["derived"]["wait_fraction_of_wave_cycles"],
-                                  "source": tfile + " (SQ_INSTS_VALU x 4 cycles / 1024 SIMDs / kernel cycles; counts every VALU "
-                                            "instruction, fp64 or integer -- the resource this kernel is bound by)"}
-            except Exception:
-                traffic = None
-        # the dominant kernel's duration as rocprofv3 reports it (kernel-trace of this command, committed): the HIP-event
-        # bracket around a launch reads ~9 us more than the kernel runs.  frac is computed on the trace figure when the
-        # committed file is about the kernel that ran; both are in the line.
-        km_events = km
-        trace_src = None
-        kpath = os.path.join(ROOT, KSTATS_FILE)
-        if world == 1 and args.config == "c3" and os.path.exists(kpath):
-            import csv
-            for row in csv.reader(open(kpath)):
-                if row and kernel_name.split("<")[0] in row[0] and "AverageNs" not in row:
-                    km = float(row[3]) * 1e-9
-                    trace_src = f"{KSTATS_FILE} (git blob {git_blob_sha1(kpath)}): AverageNs of {row[1]} launches"
-                    break
         base_metric = "sigma-point psi-evals/sec + NGD iters/sec, 1024-factor d=12 p=5 chain"
         if args.config == "c3":
             metric = base_metric
@@ -732,43 +688,128 @@ def main():
             "accepted_steps": int(sum(r["accepted"] for r in log)),
             "trials_per_step": float(np.mean([r["ntrials"] for r in log])),
             "final_cost": log[-1]["new_cost"],
-            "reference_pass_order": ab,
-            "c3_literal": c3_literal,
-            # event-timed stages of one iteration (gvi_profile_stages, 16 iterations outside the timed region): "chain" = trial
-            # factorisation || gradient solve (kernels_chain.hpp, three launches), "factors" = the factor pass, "assemble"
-            "iteration_breakdown_us": stages,
-            "chain_us": stages["chain"]["mean_us"] if stages else None,
-            "moments_kernel": {"ms": km_events * 1e3, "psi_evals_per_s": evals_launch / km_events, "launch": launch_desc, "timed_by": "HIP events, this run"},
-            # The dominant kernel streams only the quadrature table, which is L2-resident (HBM traffic ~0.5 % of the algorithmic
-            # bytes), so the binding roof is the fp64 VALU pipe, not HBM; it issues NO MFMA instruction (fp64 MFMA and fp64 VALU
-            # share one pipe on MI355X and deliver the same rate: profiles/r02_fp64_pipes.txt), so the label says what runs.
-            "roofline": {"bound": "valu_fp64 (the contract's compute label would be 'mfma'; zero MFMA instructions are issued)",
-                         "achieved": exec_flop / km / 1e12, "peak": FP64_PEAK / 1e12,
-                         "unit": "TFLOP/s", "frac": exec_flop / km / FP64_PEAK,
-                         "traffic": traffic, "traffic_source": traffic_source, "valu_issue": valu_issue,
-                         "kernel": kernel_name, "kernel_ms": km * 1e3, "kernel_ms_hip_events": km_events * 1e3,
-                         "kernel_ms_source": trace_src or "HIP events around the launch (this run)", "evals_per_launch": evals_launch,
-                         "executed_fp64_ops_per_eval": ops_table,
-                         "note": executed_note or ("achieved/frac = EXECUTED fp64 VALU instructions of the bracketed launch (every set in it), each "
-                                                   "counted as one FMA (2 flop), / HIP-event time / 78.6 TF"
-                                                   + ("; the bracket covers the whole fused pass (products, walk, chunk sums, tail, back-transform), "
-                                                      "only the walk's instructions are counted" if fused_launch else "")),
-                         "algorithmic": {"flop_per_eval": alg_flops(d0, m0) if chain_pattern else None, "tflops": alg_flop / km / 1e12,
-                                         "frac_of_peak": alg_flop / km / FP64_PEAK,
-                                         "note": "SURVEY 8(d) count of the reference's x-space algorithm (expand GEMM + psi + three "
-                                                 "moment passes); exceeds the executed figure because the z-space reformulation "
-                                                 "removes the expand -- a statement about the algorithm, not about the pipe"},
-                         "peak_source": "AMD MI355X spec sheet: 78.6 TF fp64 (vector = matrix); not in the local guide. Measured on this pool "
-                                        "(tools/ubench/fp64_pipes.hip, profiles/r02_fp64_pipes.txt): 66.5 TF v_fma_f64, 67 TF v_mfma_f64_16x16x4 "
-                                        "(one pipe: 62 TF interleaved)",
-                         "hbm_algorithmic": {"bytes_per_launch": alg_bytes, "achieved_GBps": alg_bytes / km / 1e9,
-                                             "peak_GBps": HBM_PEAK / 1e9, "frac": alg_bytes / km / HBM_PEAK,
-                                             "note": "BASELINE's '>= 60 % of HBM roofline' figure: (d+1)*8 B per eval over 8 TB/s; "
-                                                     "exceeds 1 where the table is served from L2"}},
         }
+        if args.full:
+            Kd, dd_, pd_, Nd = ctx.sets[dom]
+            km = float(np.mean(kern_ms)) * 1e-3 if kern_ms else float("nan")
+            kind_dom = int(local["specs"][dom]["kind"])
+
+            def weights_signed(spec):                      # any negative eigenvalue of the residual weight (Q^-1 / K^-1)?
+                W = spec.get("Qinv", spec.get("Kinv"))
+                return bool(np.linalg.eigvalsh(0.5 * (W + np.transpose(W, (0, 2, 1)))).min() <= 0.0)
+
+            executed_note = None
+            if chain_pattern:
+                sets_in_launch = [(K0, d0, m0, N0, weights_signed(local["specs"][0]))]
+                both = geo["variant"] in (5, 6) and len(ctx.sets) == 2
+                if both:
+                    K1, d1, p1, N1 = ctx.sets[1]
+                    sets_in_launch.append((K1, d1, d1, N1, weights_signed(local["specs"][1])))   # unary: m = d
+                if geo["variant"] == 6:
+                    kernel_name = (f"factor_fused_kernel<{m0}, {4 if p0 <= 5 else 6}, ..., {d0}, {ctx.sets[1][1] if both else d0 // 2}> (gather + Cholesky products + "
+                                   f"sign-orbit walk + chunk sum + cost tail + back-transform in one launch)") if fused_launch else \
+                        f"moments_orbit{'_pair' if both else ''}_kernel<{m0}, {4 if p0 <= 5 else 6}, full>"
+                    p_of = {d: p for (K, d, p, N) in ctx.sets}
+                    ops_of = lambda d, m, sg: orbit_exec_ops(d, p_of[d], m, True, sg)
+                elif geo["variant"] == 5:
+                    kernel_name = f"moments_sreg_pair_kernel<{d0}, {m0}, {m0}, {m0}, full>"
+                    mirror = os.environ.get("GVI_MIRROR", "1") != "0"
+                    ops_of = lambda d, m, sg: exec_ops(d, m, True, sg, mirror)
+                elif geo["variant"] == 3:
+                    kernel_name = f"moments_split_kernel<{d0}, {(m0 + 3) // 4}, full>"
+                    ops_of = lambda d, m, sg: exec_ops(d, m, True, True) + 3 + 12      # four waves per factor: sign multiply, 4 partial psi sums
+                else:
+                    kernel_name = f"moments_reg_kernel<{d0}, PsiQuad<{d0},{m0}>, full>" if geo["variant"] == 2 else "moments_generic_kernel"
+                    ops_of = lambda d, m, sg: exec_ops(d, m, True, sg, False)
+                evals_launch = sum(K * N for K, d, m, N, sg in sets_in_launch)
+                exec_flop = sum(2 * ops_of(d, m, sg) * K * N for K, d, m, N, sg in sets_in_launch)
+                alg_flop = sum(alg_flops(d, m) * K * N for K, d, m, N, sg in sets_in_launch)
+                alg_bytes = sum(K * N * (d + 1) * 8 for K, d, m, N, sg in sets_in_launch)   # (d+1) s bytes per eval
+                ops_table = {f"d={d},m={m}": ops_of(d, m, sg) for K, d, m, N, sg in sets_in_launch}
+                launch_desc = ("every factor set, all stages of the pass" if fused_launch else
+                               ("prior set + unary set in one launch" if len(sets_in_launch) == 2 else "prior set"))
+            else:
+                # non-polynomial psi (hinge on a signed-distance field ...): the lane-per-point register kernel of the dominant set
+                per = REG_KERNEL_FP64_PER_EVAL.get((kind_dom, dd_))
+                kernel_name = (f"moments_reg_kernel<{dd_}, Psi[{KIND_NAMES.get(kind_dom, kind_dom)}], full>" if geo["variant"] == 2
+                               else "moments_generic_kernel")
+                evals_launch = Kd * Nd
+                exec_flop = 2.0 * per * evals_launch if per and geo["variant"] == 2 else float("nan")
+                alg_flop = float("nan")
+                alg_bytes = evals_launch * (dd_ + 1) * 8
+                ops_table = {f"kind={KIND_NAMES.get(kind_dom, kind_dom)},d={dd_}": per}
+                launch_desc = f"set {dom} ({KIND_NAMES.get(kind_dom, kind_dom)}, d = {dd_}, p = {pd_}: the set with the most evaluations)"
+                executed_note = ("fp64 VALU instructions per 64-point step counted in the ISA of the instance (REG_KERNEL_FP64_PER_EVAL), each as one "
+                                 "FMA = 2 flop; the SDF look-up adds 4 x 8 B of gathered reads per evaluation from L2")
+            traffic, traffic_source, valu_issue = None, None, None
+            # PMC passes are separate runs (tools/gpu_pmc.sh); their per-launch figures are committed per config
+            tfile = TRAFFIC_FILE if args.config == "c3" else TRAFFIC_FILE.replace(".json", f"_{args.config}.json")
+            tpath = os.path.join(ROOT, tfile)
+            if world == 1 and os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    if kernel_name.split("<")[0] in tj.get("kernel", ""):     # counters of the kernel that actually ran
+                        traffic = tj.get("hbm_bytes_per_launch")
+                        traffic_source = (f"{tfile} (git blob {git_blob_sha1(tpath)}; rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                          "command; not re-measured in this run)")
+                        valu_issue = {"busy_frac": tj["derived"]["valu_pipe_busy"], "valu_instructions_per_launch": tj["sq"]["SQ_INSTS_VALU"],
+                                      "wait_frac_of_wave_cycles": tj["derived"]["wait_fraction_of_wave_cycles"],
+                                      "source": tfile + " (SQ_INSTS_VALU x 4 cycles / 1024 SIMDs / kernel cycles; counts every VALU "
+                                                "instruction, fp64 or integer -- the resource this kernel is bound by)"}
+                except Exception:
+                    traffic = None
+            # the dominant kernel's duration as rocprofv3 reports it (kernel-trace of this command, committed): the HIP-event
+            # bracket around a launch reads ~9 us more than the kernel runs.  frac is computed on the trace figure when the
+            # committed file is about the kernel that ran; both are in the line.
+            km_events = km
+            trace_src = None
+            kpath = os.path.join(ROOT, KSTATS_FILE)
+            if world == 1 and args.config == "c3" and os.path.exists(kpath):
+                import csv
+                for row in csv.reader(open(kpath)):
+                    if row and kernel_name.split("<")[0] in row[0] and "AverageNs" not in row:
+                        km = float(row[3]) * 1e-9
+                        trace_src = f"{KSTATS_FILE} (git blob {git_blob_sha1(kpath)}): AverageNs of {row[1]} launches"
+                        break
+            out.update({
+                "reference_pass_order": ab,
+                "c3_literal": c3_literal,
+                # event-timed stages of one iteration (gvi_profile_stages, 16 iterations outside the timed region): "chain" = trial
+                # factorisation || gradient solve (kernels_chain.hpp, three launches), "factors" = the factor pass, "assemble"
+                "iteration_breakdown_us": stages,
+                "chain_us": stages["chain"]["mean_us"] if stages else None,
+                "moments_kernel": {"ms": km_events * 1e3, "psi_evals_per_s": evals_launch / km_events, "launch": launch_desc, "timed_by": "HIP events, this run"},
+                # The dominant kernel streams only the quadrature table, which is L2-resident (HBM traffic ~0.5 % of the algorithmic
+                # bytes), so the binding roof is the fp64 VALU pipe, not HBM; it issues NO MFMA instruction (fp64 MFMA and fp64 VALU
+                # share one pipe on MI355X and deliver the same rate: profiles/r02_fp64_pipes.txt), so the label says what runs.
+                "roofline": {"bound": "valu_fp64 (the contract's compute label would be 'mfma'; zero MFMA instructions are issued)",
+                             "achieved": exec_flop / km / 1e12, "peak": FP64_PEAK / 1e12,
+                             "unit": "TFLOP/s", "frac": exec_flop / km / FP64_PEAK,
+                             "traffic": traffic, "traffic_source": traffic_source, "valu_issue": valu_issue,
+                             "kernel": kernel_name, "kernel_ms": km * 1e3, "kernel_ms_hip_events": km_events * 1e3,
+                             "kernel_ms_source": trace_src or "HIP events around the launch (this run)", "evals_per_launch": evals_launch,
+                             "executed_fp64_ops_per_eval": ops_table,
+                             "note": executed_note or ("achieved/frac = EXECUTED fp64 VALU instructions of the bracketed launch (every set in it), each "
+                                                       "counted as one FMA (2 flop), / HIP-event time / 78.6 TF"
+                                                       + ("; the bracket covers the whole fused pass (products, walk, chunk sums, tail, back-transform), "
+                                                          "only the walk's instructions are counted" if fused_launch else "")),
+                             "algorithmic": {"flop_per_eval": alg_flops(d0, m0) if chain_pattern else None, "tflops": alg_flop / km / 1e12,
+                                             "frac_of_peak": alg_flop / km / FP64_PEAK,
+                                             "note": "SURVEY 8(d) count of the reference's x-space algorithm (expand GEMM + psi + three "
+                                                     "moment passes); exceeds the executed figure because the z-space reformulation "
+                                                     "removes the expand -- a statement about the algorithm, not about the pipe"},
+                             "peak_source": "AMD MI355X spec sheet: 78.6 TF fp64 (vector = matrix); not in the local guide. Measured on an MI355X "
+                                            "(tools/ubench/fp64_pipes.hip, profiles/r02_fp64_pipes.txt): 66.5 TF v_fma_f64, 67 TF v_mfma_f64_16x16x4 "
+                                            "(one pipe: 62 TF interleaved)",
+                             "hbm_algorithmic": {"bytes_per_launch": alg_bytes, "achieved_GBps": alg_bytes / km / 1e9,
+                                                 "peak_GBps": HBM_PEAK / 1e9, "frac": alg_bytes / km / HBM_PEAK,
+                                                 "note": "BASELINE's '>= 60 % of HBM roofline' figure: (d+1)*8 B per eval over 8 TB/s; "
+                                                         "exceeds 1 where the table is served from L2"}},
+            })
         if world > 1:
             out["transport"] = transport
             out.setdefault("rccl_ranks", None)                # (no RCCL group in a rehearsal)
+        if args.full and world > 1:
             out["c5_strong"] = c5_block
             out["parity_vs_single_gpu"] = parity
             # Expected ceiling of strong scaling (BASELINE configs[3]): t(N) = W / N + R + X with W = the factor pass (shards),
@@ -782,7 +823,7 @@ def main():
                                            "expected_speedup_at_n": (W + R) / (W / world + R + max(X, 0.0)),
                                            "constants": "W, R: gvi_profile_stages on rank 0's unsharded context in this run; X = ms_per_step - (W / N + R)",
                                            "note": "t(N) = W / N + R + X; the ceiling as N grows is (W + R) / (R + X)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(chain, args.cpu_seconds, dom if not chain_pattern else 0)
         print(json.dumps(out), flush=True)
     ctx.close()

@@ -167,7 +167,7 @@ def test_bench_two_rank_rehearsal_reproduces_the_single_gpu_cost():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "12", "--warmup", "3", "--no-cpu-baseline"]
+    common = ["--steps", "12", "--warmup", "3", "--full", "--no-cpu-baseline"]
     r1 = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, capture_output=True, text=True, timeout=600)
     assert r1.returncode == 0, r1.stderr[-2000:]
     one = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])

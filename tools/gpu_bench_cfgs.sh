@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 OUT="gpurun_out/$R"
 mkdir -p "$OUT"
 for c in "$@"; do
-  timeout -k 10 400 python bench.py --config "$c" ${GVI_BENCH_ARGS:-} > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo "== $c FAILED"; tail -15 "$OUT/bench_$c.err"; continue; }
+  timeout -k 10 400 python bench.py --config "$c" --full ${GVI_BENCH_ARGS:-} > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo "== $c FAILED"; tail -15 "$OUT/bench_$c.err"; continue; }
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_$c.json"))

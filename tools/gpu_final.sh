@@ -14,11 +14,11 @@ if [ "${GVI_SKIP_TESTS:-0}" != "1" ]; then
 fi
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
 tail -1 "$O/smoke.log"
-timeout -k 10 300 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 300 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 for c in c2 planar1k; do
-  timeout -k 10 300 python bench.py --config $c --steps 500 --warmup 50 > "$O/bench_$c.json" 2> "$O/bench_$c.err" || { tail -20 "$O/bench_$c.err"; exit 1; }
+  timeout -k 10 300 python bench.py --config $c --steps 500 --warmup 50 --full > "$O/bench_$c.json" 2> "$O/bench_$c.err" || { tail -20 "$O/bench_$c.err"; exit 1; }
 done
-timeout -k 10 500 python bench.py --config c5 --no-cpu-baseline > "$O/bench_c5.json" 2> "$O/bench_c5.err" || { tail -20 "$O/bench_c5.err"; exit 1; }
+timeout -k 10 500 python bench.py --config c5 --full --no-cpu-baseline > "$O/bench_c5.json" 2> "$O/bench_c5.err" || { tail -20 "$O/bench_c5.err"; exit 1; }
 python - <<PY
 import json
 for c in ("", "_c2", "_planar1k", "_c5"):
@@ -38,7 +38,7 @@ timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/tr
 find "$O/trace_c5" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$O/kernel_stats_c5.csv"
 rm -rf "$O/trace_c5"
 head -8 "$O/kernel_stats_c3.csv" | cut -c1-150
-GVI_BENCH_REHEARSAL=1 GVI_BENCH_C5_CONFIG=c5small timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 60 --warmup 10 > "$O/bench_rehearsal2.log" 2>&1 || { tail -20 "$O/bench_rehearsal2.log"; exit 1; }
+GVI_BENCH_REHEARSAL=1 GVI_BENCH_C5_CONFIG=c5small timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 60 --warmup 10 --full > "$O/bench_rehearsal2.log" 2>&1 || { tail -20 "$O/bench_rehearsal2.log"; exit 1; }
 grep '^{' "$O/bench_rehearsal2.log" | tail -1 > "$O/bench_rehearsal2.json"
 python - <<PY
 import json

@@ -17,7 +17,7 @@ IFS='|' read -ra ENVS <<< "${GVI_BENCH_ENVS:-|}"
 [ ${#ENVS[@]} -eq 0 ] && ENVS=("")
 i=0
 for e in "${ENVS[@]}"; do
-  env $e timeout -k 10 200 python bench.py --steps 300 --warmup 30 --no-cpu-baseline ${GVI_BENCH_ARGS:-} > "$OUT/bench_iter_$i.json" 2> "$OUT/bench_iter.err" || { tail -20 "$OUT/bench_iter.err"; exit 1; }
+  env $e timeout -k 10 200 python bench.py --steps 300 --warmup 30 --full --no-cpu-baseline ${GVI_BENCH_ARGS:-} > "$OUT/bench_iter_$i.json" 2> "$OUT/bench_iter.err" || { tail -20 "$OUT/bench_iter.err"; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_iter_$i.json"))

@@ -8,7 +8,7 @@ OUT="gpurun_out/$R"; mkdir -p "$OUT"
 for v in ${VARIANTS:-default}; do
   lib=""; [ "$v" != "default" ] && lib="$ROOT/build/variants/libgvi_hip_$v.so"
   extra=""; [ "$v" = "timing" ] && extra="GVI_FUSED_DBG=8"
-  env GVI_LIB_PATH="$lib" $extra ${GVI_ENV:-} timeout -k 10 200 python bench.py --steps ${STEPS:-300} --warmup 30 --no-cpu-baseline ${GVI_BENCH_ARGS:-} > "$OUT/var_$v.json" 2> "$OUT/var_$v.err" || { tail -20 "$OUT/var_$v.err"; exit 1; }
+  env GVI_LIB_PATH="$lib" $extra ${GVI_ENV:-} timeout -k 10 200 python bench.py --steps ${STEPS:-300} --warmup 30 --full --no-cpu-baseline ${GVI_BENCH_ARGS:-} > "$OUT/var_$v.json" 2> "$OUT/var_$v.err" || { tail -20 "$OUT/var_$v.err"; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$OUT/var_$v.json"))
