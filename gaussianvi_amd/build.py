@@ -39,17 +39,20 @@ def lib_sources():
 
 
 def build_lib(force: bool = False, verbose: bool = False, out: str | None = None, defines: tuple = ()) -> str:
-    """out / defines: an A/B build beside the in-tree library (tools/build_variant.py)."""
-    LIB = out or globals()["LIB"]
-    if not force and not _stale(LIB, lib_sources()):
-        return LIB
-    tmp = LIB + f".tmp{os.getpid()}"          # written aside and renamed: a concurrent reader never sees a partial file
+    """The in-tree library is always the product build.  out / defines: a measurement build (e.g. GVI_FUSED_TIMING) beside
+    it -- tools/build_variant.py writes build/variants/, GVI_LIB_PATH selects one at load time."""
+    lib = out or LIB
+    if defines and os.path.realpath(lib) == os.path.realpath(LIB):
+        raise ValueError(f"defines {list(defines)} requested for the in-tree library {LIB}: build into another path (out=)")
+    if not force and not _stale(lib, lib_sources()):
+        return lib
+    tmp = lib + f".tmp{os.getpid()}"          # written aside and renamed: a concurrent reader never sees a partial file
     cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-shared",
            "-Wall", "-Wno-unused-function",
            "-I", os.path.join(ROOT, "include"),
            os.path.join(CSRC, "gvi_hip.hip"), "-x", "hip", os.path.join(CSRC, "spgh.cpp"), os.path.join(CSRC, "table_io.cpp"),
            "-o", tmp]
-    for define in list(defines) + os.environ.get("GVI_BUILD_DEFINES", "").split():      # profiling builds, e.g. GVI_FUSED_TIMING
+    for define in defines:
         cmd.insert(1, "-D" + define)
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
@@ -60,8 +63,8 @@ def build_lib(force: bool = False, verbose: bool = False, out: str | None = None
         if os.path.exists(tmp):
             os.remove(tmp)
         raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + r.stderr[-8000:])
-    os.replace(tmp, LIB)
-    return LIB
+    os.replace(tmp, lib)
+    return lib
 
 
 def build_examples(force: bool = False) -> str:

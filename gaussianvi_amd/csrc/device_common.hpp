@@ -76,7 +76,6 @@ __device__ __forceinline__ bool pred_fail(const LazyPred& p) { return p.has && p
 // LINES = ceil(sizeof(arguments) / 64), a specialisation per kernel that uses it.
 template <int LINES> __device__ __forceinline__ void kernarg_warm();
 template <> __device__ __forceinline__ void kernarg_warm<7>() {
-#ifndef GVI_NO_KERNARG_WARM      // (A/B build)
   unsigned w[7];
   asm volatile(
                "s_load_dword %0, %7, 0x0\n"
@@ -89,10 +88,8 @@ template <> __device__ __forceinline__ void kernarg_warm<7>() {
                "s_waitcnt lgkmcnt(0)"
                : "=&s"(w[0]), "=&s"(w[1]), "=&s"(w[2]), "=&s"(w[3]), "=&s"(w[4]), "=&s"(w[5]), "=&s"(w[6])
                : "s"(__builtin_amdgcn_kernarg_segment_ptr()));
-#endif
 }
 template <> __device__ __forceinline__ void kernarg_warm<13>() {
-#ifndef GVI_NO_KERNARG_WARM      // (A/B build)
   unsigned w[13];
   asm volatile(
                "s_load_dword %0, %13, 0x0\n"
@@ -111,10 +108,8 @@ template <> __device__ __forceinline__ void kernarg_warm<13>() {
                "s_waitcnt lgkmcnt(0)"
                : "=&s"(w[0]), "=&s"(w[1]), "=&s"(w[2]), "=&s"(w[3]), "=&s"(w[4]), "=&s"(w[5]), "=&s"(w[6]), "=&s"(w[7]), "=&s"(w[8]), "=&s"(w[9]), "=&s"(w[10]), "=&s"(w[11]), "=&s"(w[12])
                : "s"(__builtin_amdgcn_kernarg_segment_ptr()));
-#endif
 }
 template <> __device__ __forceinline__ void kernarg_warm<14>() {
-#ifndef GVI_NO_KERNARG_WARM      // (A/B build)
   unsigned w[14];
   asm volatile(
                "s_load_dword %0, %14, 0x0\n"
@@ -134,10 +129,8 @@ template <> __device__ __forceinline__ void kernarg_warm<14>() {
                "s_waitcnt lgkmcnt(0)"
                : "=&s"(w[0]), "=&s"(w[1]), "=&s"(w[2]), "=&s"(w[3]), "=&s"(w[4]), "=&s"(w[5]), "=&s"(w[6]), "=&s"(w[7]), "=&s"(w[8]), "=&s"(w[9]), "=&s"(w[10]), "=&s"(w[11]), "=&s"(w[12]), "=&s"(w[13])
                : "s"(__builtin_amdgcn_kernarg_segment_ptr()));
-#endif
 }
 template <> __device__ __forceinline__ void kernarg_warm<26>() {
-#ifndef GVI_NO_KERNARG_WARM      // (A/B build)
   unsigned w[26];
   asm volatile(
                "s_load_dword %0, %26, 0x0\n"
@@ -169,7 +162,6 @@ template <> __device__ __forceinline__ void kernarg_warm<26>() {
                "s_waitcnt lgkmcnt(0)"
                : "=&s"(w[0]), "=&s"(w[1]), "=&s"(w[2]), "=&s"(w[3]), "=&s"(w[4]), "=&s"(w[5]), "=&s"(w[6]), "=&s"(w[7]), "=&s"(w[8]), "=&s"(w[9]), "=&s"(w[10]), "=&s"(w[11]), "=&s"(w[12]), "=&s"(w[13]), "=&s"(w[14]), "=&s"(w[15]), "=&s"(w[16]), "=&s"(w[17]), "=&s"(w[18]), "=&s"(w[19]), "=&s"(w[20]), "=&s"(w[21]), "=&s"(w[22]), "=&s"(w[23]), "=&s"(w[24]), "=&s"(w[25])
                : "s"(__builtin_amdgcn_kernarg_segment_ptr()));
-#endif
 }
 
 }  // namespace gvi

@@ -1,5 +1,5 @@
 // Block-tridiagonal chain operations (solve / log-det / tridiagonal blocks of the inverse) by SEGMENTED block cyclic
-// reduction with register-resident eliminations -- round 3 rewrite of kernels_bcr_seg.hpp.
+// reduction with register-resident eliminations (round 3 rewrite of the round-2 segmented kernels; see git history).
 //
 // Replaces, per SURVEY.md section 8(a):
 //   a12      ConjugateGradient solve (ngd/NGD-GH-impl.h:59-60)
@@ -171,13 +171,7 @@ __device__ __forceinline__ void asm_pair(const AsmList& L, const int n, const in
   }
 }
 
-#ifndef GVI_CHAIN_UBLATE
-#define GVI_CHAIN_UBLATE 1     // 0: the rows of Ub fetched row by row inside the Schur products (A/B build)
-#endif
-#ifndef GVI_CHAIN_THREADS_SMALL
-#define GVI_CHAIN_THREADS_SMALL 1024
-#endif
-constexpr int chain_threads(int n) { return n <= 8 ? GVI_CHAIN_THREADS_SMALL : 512; }
+constexpr int chain_threads(int n) { return n <= 8 ? 1024 : 512; }
 
 // -DGVI_CHAIN_TIMING (tools/ubench/chain_bench.hip only): shader-clock stamps of wave 0 of the top pass's factorisation
 #ifdef GVI_CHAIN_TIMING
@@ -427,7 +421,7 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
     // formed, so their registers hold Ub -- with one wait in front of the products.  Left to the scheduler the eighteen
     // ds_read_b128 went out in six groups with a wait each: six dependent LDS round trips per elimination (ISA of N = 6).
     // chain_bench T = 1025, n = 6: 47.36 -> 46.83 us.  (The same for the operand rows of the backward step: no gain, 47.4.)
-    constexpr bool UBLATE = !UBPRE && GVI_CHAIN_UBLATE != 0 && N * N * 2 <= (RB == 128 ? 72 : 0);
+    constexpr bool UBLATE = !UBPRE && N * N * 2 <= (RB == 128 ? 72 : 0);
     double ubl[UBLATE ? N : 1][N];
     if constexpr (UBLATE) {
 #pragma unroll

@@ -28,9 +28,6 @@
 namespace gvi {
 
 constexpr int FUSED_MAX_ITEMS = 4;
-#ifndef GVI_FUSED_HELPERS
-#define GVI_FUSED_HELPERS 1     // 0: every item's wave forms its own H and u0 (A/B build)
-#endif
 
 struct FusedSet {
   FactorDev f;
@@ -205,7 +202,7 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
   double* Pbase = Zbase + (size_t)maxitems * zs;               // [items][4][npairs(dmax)]
   // ---- phase 1: wave i forms the products of item i; the block's idle waves (4 - nitems of them) form H and u0 of items
   // 0 .. 3 - nitems beside it (prep_chol_hu0): the item's own chain is then gather -> Cholesky -> L^-1 ----
-  const int nhelp = GVI_FUSED_HELPERS ? min(4 - nitems, nitems) : 0;      // items [0, nhelp) have a helper: the wave with iw = nitems + item
+  const int nhelp = min(4 - nitems, nitems);      // items [0, nhelp) have a helper: the wave with iw = nitems + item
   const auto helped = [&](const int it) {                      // (the shapes whose rows of A fit two registers a lane: all the fused route takes)
     const FactorDev& f = A.s[it < c0 ? 0 : 1].f;
     return it < nhelp && f.m > 0 && f.m * f.d <= 128;

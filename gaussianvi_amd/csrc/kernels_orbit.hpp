@@ -28,10 +28,6 @@
 
 namespace gvi {
 
-#ifndef ORBIT_WHT
-#define ORBIT_WHT 1      // 0: per-point accumulation of the sign-weighted sums for every support size (A/B build)
-#endif
-
 #ifdef GVI_FUSED_TIMING
 __device__ unsigned long long* gvi_walk_stamps;
 #endif
@@ -118,23 +114,6 @@ __host__ __device__ constexpr int orbit_hstride(int M) { return M == 12 ? 14 : M
 __device__ __forceinline__ void lds_add_f64(double* p, double v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-#ifndef GVI_EXP_FLATATOM
-#define GVI_EXP_FLATATOM 0     // timing experiment (WRONG results): every accumulator add of a lane goes to the lane's own address
-#endif                         // (64 consecutive doubles per instruction: what the adds cost without bank / address conflicts)
-#if GVI_EXP_FLATATOM
-__device__ __forceinline__ char* accb_flat(char* base, int sh) { return base - (((int)(threadIdx.x & 63) & ((1 << (sh - 3)) - 1)) << 3); }
-// (= 2: the real address is still computed -- kept alive by an empty asm -- so that only the conflicts are taken out;
-//  = 3: flat targets, and the record's coordinates / row bases kept live up to the adds without being used)
-__device__ __forceinline__ double* orbit_flat_target(char* real, char* base, int n, int sh) {
-#if GVI_EXP_FLATATOM == 2
-  asm volatile("" :: "v"(real));
-#endif
-  return (double*)(accb_flat(base, sh) + ((((n) & 1) * 64 + (int)(threadIdx.x & 63)) << 3));
-}
-#define ORBIT_ADD_TARGET(expr, n, sh) orbit_flat_target((char*)(expr), base, n, sh)
-#else
-#define ORBIT_ADD_TARGET(expr, n, sh) ((double*)(expr))
-#endif
 // The accumulator adds of one orbit.  Values and LDS addresses are formed FIRST (the record's registers die there), then
 // pre() requests the next tile's records into those registers, then the adds go out.  accb: byte address of this lane's
 // copy of entry 0; entry e lives at accb + (e << sh), sh = log2(copies) + 3.
@@ -162,11 +141,6 @@ __device__ __forceinline__ void orbit_accumulate(const int sh, const int (&c)[S]
       for (int j = i + 1; j < S; ++j) val[n++] = wm * mgl[j] * Eij[e++];
     }
   }
-#if GVI_EXP_FLATATOM == 3      // (the record's coordinates and row bases stay live up to here, but no address is formed from them)
-#pragma unroll
-  for (int i = 0; i < S; ++i) asm volatile("" :: "v"(c[i]));
-  asm volatile("" :: "v"(rpk));
-#endif
   pre();
   char* const base = (char*)accb;
   char* const base1 = base + (1u << sh);                         // m1[0]
@@ -181,26 +155,12 @@ __device__ __forceinline__ void orbit_accumulate(const int sh, const int (&c)[S]
   int n = 0;
 #pragma unroll
   for (int i = 0; i < S; ++i) {
-    lds_add_f64(ORBIT_ADD_TARGET(base1 + B[i], n, sh), val[n]); ++n;
-    lds_add_f64(ORBIT_ADD_TARGET(base + (A[i] + B[i]), n, sh), val[n]); ++n;
+    lds_add_f64((double*)(base1 + B[i]), val[n]); ++n;
+    lds_add_f64((double*)(base + (A[i] + B[i])), val[n]); ++n;
 #pragma unroll
-    for (int j = i + 1; j < S; ++j) { lds_add_f64(ORBIT_ADD_TARGET(base + (A[i] + B[j]), n, sh), val[n]); ++n; }
+    for (int j = i + 1; j < S; ++j) { lds_add_f64((double*)(base + (A[i] + B[j])), val[n]); ++n; }
   }
 }
-
-#ifndef ORBIT_LB4
-#define ORBIT_LB4 2
-#endif
-#ifndef GVI_EXP_EXTRA_FMA
-#define GVI_EXP_EXTRA_FMA 0      // timing experiment: this many extra independent fp64 FMAs per half-point
-#endif
-#ifndef GVI_EXP_NOCOL
-#define GVI_EXP_NOCOL 0        // timing experiment (WRONG results): the columns of H are made up instead of read from LDS
-#endif
-#ifndef GVI_EXP_NOATOM
-#define GVI_EXP_NOATOM 0       // timing experiment (WRONG results): the accumulator adds of supports <= this size are skipped
-#endif
-
 
 // one orbit per lane, support size S (all lanes of the wave: tiles are uniform in S)
 // pre(): called between the Gray walk and the accumulator adds -- where the walk's registers are dead -- to request the
@@ -226,7 +186,7 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
     hp[j] = Hl + c[j] * orbit_hstride(M);
     if constexpr (HREG) {
 #pragma unroll
-      for (int r = 0; r < M; ++r) hcol[j][r] = GVI_EXP_NOCOL ? (double)(c[j] + r) * w : hp[j][r];
+      for (int r = 0; r < M; ++r) hcol[j][r] = hp[j][r];
     }
   }
   // start at the corner (-, ..., -, +): the last coordinate keeps its sign, the other S-1 are walked in Gray order
@@ -258,12 +218,12 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
   // s = 4 (unused outputs are dead code); the signs of the higher coordinates are constant inside a block and multiply the
   // block's sums.  WHT_BIG: also for s = 5, 6 (needs the registers: not at m = 12).
   constexpr bool WHT_BIG = M <= 6;
-  constexpr bool WHT = FULL && S >= 2 && ORBIT_WHT && (S <= 4 || WHT_BIG);
+  constexpr bool WHT = FULL && S >= 2 && (S <= 4 || WHT_BIG);
   // coordinates whose signs vary inside a block of 2^LB consecutive Gray steps.  s = 4 takes two blocks of four instead of
   // one of eight: the same number of additions (two 4-point butterflies per scalar + 11 signed adds for the second block
   // against one 8-point butterfly) with 16 fewer live registers -- which is what lets the next tile's records be requested
   // under the current tile's accumulator adds without spilling (orbit_class)
-  constexpr int LBMAX = S == 4 ? ORBIT_LB4 : 3;
+  constexpr int LBMAX = S == 4 ? 2 : 3;
   constexpr int LB = S - 1 < LBMAX ? S - 1 : LBMAX;
   constexpr int BLK = 1 << LB;
   double cpv[WHT ? BLK : 1], lv[WHT ? BLK : 1];
@@ -272,9 +232,6 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
   for (int e = 0; e < S * (S - 1) / 2 + 1; ++e) Eij[e] = 0.0;
 #pragma unroll
   for (int j = 0; j < S; ++j) Oi[j] = 0.0;
-#if GVI_EXP_EXTRA_FMA
-  double xdum[6] = {0, 0, 0, 0, 0, 0};
-#endif
 #pragma unroll
   for (int g = 0; g < NH; ++g) {
     const int jn = g + 1 < NH ? __builtin_ctz(g + 1) : 0;        // coordinate of the next flip (compile-time after unrolling)
@@ -294,10 +251,6 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
       q = SIGNED ? fma(sg[r] * v[r], v[r], q) : fma(v[r], v[r], q);
       if (FULL) l = fma(su0[r], v[r], l);
     }
-#if GVI_EXP_EXTRA_FMA
-#pragma unroll
-    for (int r = 0; r < GVI_EXP_EXTRA_FMA; ++r) xdum[r % 6] = fma(v[r % M], v[(r + 1) % M], xdum[r % 6]);
-#endif
     const double cp = q + k0;
     if constexpr (WHT) {
       // keep (c+, l) of this sign pattern of the low coordinates; at the end of a block: butterfly, then add the block's
@@ -359,18 +312,7 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
   }
   const double wp = w + w;
   m0 = fma(wp, E0, m0);
-#if GVI_EXP_EXTRA_FMA
-  m0 = fma(1e-300, ((xdum[0] + xdum[1]) + (xdum[2] + xdum[3])) + (xdum[4] + xdum[5]), m0);
-#endif
-  if constexpr (FULL && S <= GVI_EXP_NOATOM) {
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i < S; ++i) t += Oi[i];
-#pragma unroll
-    for (int e = 0; e < S * (S - 1) / 2; ++e) t += Eij[e];
-    m0 = fma(1e-300, t, m0);
-    pre();
-  } else if constexpr (FULL) {
+  if constexpr (FULL) {
     orbit_accumulate<S>(lc + 3, c, rpk, mg, wp, E0, Eij, Oi, accl, pre);
   } else {
     pre();
@@ -384,9 +326,6 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
 // fetched from LDS inside the walk -- orbit_walk at m = 12 fetches twelve doubles at (almost) every Gray step, and its wave
 // waits for LDS in 15 % of its cycles -- and the Walsh butterfly of the sign-weighted sums (registers again) applies at
 // s = 5 / 6 as it does at m = 6.  Same number of fp64 instructions per orbit; sums re-associated (rows 0..5 first).
-#ifndef GVI_ORBIT_SPLIT12
-#define GVI_ORBIT_SPLIT12 1
-#endif
 template <int S, bool SIGNED, typename Pre>
 __device__ __forceinline__ void orbit_walk_split(const int lc, const uint64_t cpk, const uint64_t rpk, const double (&mg)[S], const double w,
                                                  const double* Hl, double* accl, const double (&su0)[12], const double (&sg)[12],
@@ -494,7 +433,7 @@ __device__ __forceinline__ void orbit_gray(const double (&hcol)[S][M], const dou
                                            const double k0, double& E0, double (&Eij)[S * (S - 1) / 2 + 1], double (&Oi)[S]) {
   static_assert(S <= 3, "orbit_gray: one butterfly block");
   constexpr int NH = 1 << (S - 1), LB = S - 1, BLK = NH;
-  constexpr bool WHT = FULL && S >= 2 && ORBIT_WHT;
+  constexpr bool WHT = FULL && S >= 2;
   int sig[S];
 #pragma unroll
   for (int j = 0; j < S; ++j) sig[j] = j == S - 1 ? 1 : -1;
@@ -636,7 +575,7 @@ __device__ __forceinline__ void orbit_class_grouped(const OrbitDev& ob, const in
         }
       }
     }
-    if constexpr (FULL && S > GVI_EXP_NOATOM) {
+    if constexpr (FULL) {
       const int sh = lc + 3;
       char* const base = (char*)accl;
       char* const base1 = base + (1u << sh);
@@ -650,29 +589,20 @@ __device__ __forceinline__ void orbit_class_grouped(const OrbitDev& ob, const in
       int n = 0;
 #pragma unroll
       for (int i = 0; i < S; ++i) {
-        lds_add_f64(ORBIT_ADD_TARGET(base1 + B[i], n, sh), acc[n]); ++n;
-        lds_add_f64(ORBIT_ADD_TARGET(base + (A[i] + B[i]), n, sh), acc[n]); ++n;
+        lds_add_f64((double*)(base1 + B[i]), acc[n]); ++n;
+        lds_add_f64((double*)(base + (A[i] + B[i])), acc[n]); ++n;
 #pragma unroll
-        for (int j = i + 1; j < S; ++j) { lds_add_f64(ORBIT_ADD_TARGET(base + (A[i] + B[j]), n, sh), acc[n]); ++n; }
+        for (int j = i + 1; j < S; ++j) { lds_add_f64((double*)(base + (A[i] + B[j])), acc[n]); ++n; }
       }
-    } else if constexpr (FULL) {
-      double tsum = 0.0;
-#pragma unroll
-      for (int q = 0; q < NV; ++q) tsum += acc[q];
-      m0 = fma(1e-300, tsum, m0);
     }
   }
 }
 
-// the tiles [t0, t1) of ONE support-size class, software-pipelined: the records of tile t + 1 are requested while tile t
-// still has its accumulator adds to issue, so that their round trip overlaps the adds and the next tile's column reads
 // largest support size stored support-major (host: build_orbits' group_smax must not exceed it)
-#ifndef ORBIT_GROUP_SMAX
-#define ORBIT_GROUP_SMAX 3
-#endif
-#ifndef ORBIT_PIPE_SMAX
-#define ORBIT_PIPE_SMAX 3
-#endif
+constexpr int ORBIT_GROUP_SMAX = 3;
+
+// the tiles [t0, t1) of ONE support-size class, software-pipelined: the records of tile t + 1 are requested while tile t
+// still has its accumulator adds to issue, so that their round trip overlaps the adds and the next tile's column reads.
 // t0, t1 are wave-uniform (SGPRs); lane8 = 8 * lane.  (Requesting the chunk's first tile ahead of orbit_wave's prologue was
 // tried: the record stays live through every class loop -- 14 registers, spills -- for no gain.)
 template <int M, int S, bool FULL, bool SIGNED>
@@ -680,9 +610,9 @@ __device__ __forceinline__ void orbit_class(const OrbitDev& ob, const int lc, co
                                             const double* Hl, double* accl, const double (&su0)[M], const double (&sg)[M], const double k0,
                                             double& m0) {
   if (t0 >= t1) return;
-  // s >= 4: a tile is long enough (290 VALU instructions and more) for its own load latency not to matter, and its walk
-  // leaves no 14 registers for the next tile's records
-  constexpr bool PIPE = S <= ORBIT_PIPE_SMAX;
+  // pipelined up to s = 3 only.  s >= 4: a tile is long enough (290 VALU instructions and more) for its own load latency
+  // not to matter, and its walk leaves no 14 registers for the next tile's records
+  constexpr bool PIPE = S <= 3;
   OrbitRec<S> cur;
   const uint32_t cb8 = ((uint32_t)ob.cbase[S] - (uint32_t)tfirst * 64u) * 8u + lane8;      // entry of (tile t, this lane) = cb8 + 512 t
   if constexpr (PIPE) orbit_load<S>(ob, cb8 + (uint32_t)t0 * 512u, cur);
@@ -702,7 +632,7 @@ __device__ __forceinline__ void orbit_class(const OrbitDev& ob, const int lc, co
     double mg[S];
 #pragma unroll
     for (int j = 0; j < S; ++j) mg[j] = cur.mg[j];
-    if constexpr (M == 12 && S >= 4 && FULL && GVI_ORBIT_SPLIT12 != 0) orbit_walk_split<S, SIGNED>(lc, cpk, rpk, mg, w, Hl, accl, su0, sg, k0, m0, pre);
+    if constexpr (M == 12 && S >= 4 && FULL) orbit_walk_split<S, SIGNED>(lc, cpk, rpk, mg, w, Hl, accl, su0, sg, k0, m0, pre);
     else orbit_walk<M, S, FULL, SIGNED>(lc, cpk, rpk, mg, w, Hl, accl, su0, sg, k0, m0, pre);
   }
 }

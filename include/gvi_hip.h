@@ -359,8 +359,8 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *   --                   jacobi_tol_exp      -34      stopping threshold of the symmetric-root solve         rounding
  *   --                   split_flush, target_waves, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, dual_chain,
  *                        warm_start: launch geometry / summation order of individual kernels (tests/test_gpu_parity.py A/Bs)
- * Build-time only: GVI_BUILD_DEFINES=GVI_FUSED_TIMING (phase stamps; GVI_FUSED_DBG=8 prints them), GVI_ORBIT_SPLIT12,
- * GVI_EXP_* (timing experiments with WRONG results, tools/build_variant.py).
+ * Build-time only: GVI_FUSED_TIMING (phase stamps; GVI_FUSED_DBG=8 prints them), built beside the in-tree library by
+ * tools/build_variant.py and selected with GVI_LIB_PATH (the in-tree library is always built without defines).
  *
  * Runtime form of the A/B environment switches read at gvi_ctx_create.  Results are identical in every
  * setting of the scheduling switches; the switches that select another summation order or another (mathematically

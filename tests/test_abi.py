@@ -118,3 +118,36 @@ def test_documented_option_names_are_the_implemented_ones():
     body = body[:body.index("return fail(ctx, GVI_ERR_ARG, \"unknown option")]
     implemented = set(re.findall(r'n == "([a-z0-9_]+)"', body))
     assert documented == implemented, (sorted(documented - implemented), sorted(implemented - documented))
+
+
+def test_in_tree_build_refuses_defines(monkeypatch):
+    """The in-tree library is always the product build: a define (a timing build) is refused before hipcc runs."""
+    def no_hipcc(*args, **kwargs):
+        raise AssertionError("hipcc ran")
+    monkeypatch.setattr(build, "_hipcc", no_hipcc)
+    monkeypatch.setattr(build.subprocess, "run", no_hipcc)
+    for out in (None, build.LIB):
+        with pytest.raises(ValueError, match="in-tree"):
+            build.build_lib(force=True, out=out, defines=("GVI_FUSED_TIMING",))
+
+
+def test_variant_build_passes_defines(monkeypatch, tmp_path):
+    """A build into another path (tools/build_variant.py) gets its defines on the compiler line."""
+    cmds = []
+    def fake_run(cmd, **kwargs):
+        cmds.append(cmd)
+        open(cmd[cmd.index("-o") + 1], "wb").close()
+        return build.subprocess.CompletedProcess(cmd, 0, "", "")
+    monkeypatch.setattr(build, "_hipcc", lambda: "hipcc")
+    monkeypatch.setattr(build.subprocess, "run", fake_run)
+    out = str(tmp_path / "libgvi_hip_timing.so")
+    assert build.build_lib(force=True, out=out, defines=("GVI_FUSED_TIMING",)) == out
+    assert os.path.exists(out) and "-DGVI_FUSED_TIMING" in cmds[0]
+
+
+def test_product_sources_have_no_experiment_builds():
+    """No wrong-result timing experiment (GVI_EXP_*) is compiled into the product sources."""
+    csrc = os.path.join(ROOT, "gaussianvi_amd", "csrc")
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name), errors="replace") as f:
+            assert "GVI_EXP_" not in f.read(), name

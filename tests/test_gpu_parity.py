@@ -477,7 +477,8 @@ def _spd_chain(T, n, rng):
 
 
 @pytest.mark.parametrize("T,n", [(1, 1), (1, 4), (2, 2), (3, 1), (9, 3), (33, 6), (65, 2), (17, 12), (5, 16),
-                                 (31, 4), (32, 6), (34, 8), (100, 2), (257, 3), (1000, 1), (129, 12), (70, 5), (40, 7)])
+                                 (31, 4), (32, 6), (34, 8), (100, 2), (257, 3), (1000, 1), (129, 12), (70, 5), (40, 7),
+                                 (20, 14), (33, 9), (33, 10), (33, 11), (33, 13), (33, 15)])
 def test_bt_ops_vs_oracle(T, n):
     rng = np.random.default_rng(T * 31 + n)
     D, U = _spd_chain(T, n, rng)

@@ -1,4 +1,5 @@
-"""A/B builds of the library: python tools/build_variant.py <name> [DEFINE[=v] ...] -> build/variants/libgvi_hip_<name>.so
+"""Measurement builds of the library (e.g. GVI_FUSED_TIMING; the in-tree library takes no defines):
+python tools/build_variant.py <name> [DEFINE[=v] ...] -> build/variants/libgvi_hip_<name>.so
 (select with GVI_LIB_PATH; build/ is git-ignored and travels to the GPU box with the gpurun snapshot)."""
 import os
 import sys

@@ -8,8 +8,8 @@ B=tools/ubench/chain_bench
   for n in 6 2 4 12 8 3 1 5 7 9 10 11 13 14 16; do timeout -k 10 120 $B 1025 $n 100; done
   timeout -k 10 120 $B 65 2 200
   timeout -k 10 120 $B 4097 12 50
-  timeout -k 10 120 $B 40000 6 20 0
-  timeout -k 10 120 $B 3000 14 20 0
+  timeout -k 10 120 $B 40000 6 20
+  timeout -k 10 120 $B 3000 14 20
   timeout -k 10 120 $B 7 6 20
   timeout -k 10 120 $B 7 5 20
   timeout -k 10 120 $B 1 6 20

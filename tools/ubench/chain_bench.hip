@@ -1,7 +1,7 @@
-// Stand-alone check + timing of the chain kernels (kernels_chain.hpp) against a sequential host solver and against the
-// round-2 segmented kernels (kernels_bcr_seg.hpp), both chain operations of an NGD iteration side by side:
+// Stand-alone check + timing of the chain kernels (kernels_chain.hpp) against a sequential host solver, both chain
+// operations of an NGD iteration side by side:
 //   factorisation of Lam (1/2 log det + tridiagonal blocks of the inverse)  ||  pivoted solve V x = -g
-// Build:  hipcc --offload-arch=gfx950 -O3 -std=c++20 -I gaussianvi_amd/csrc -I tools/ab tools/ubench/chain_bench.hip -o tools/ubench/chain_bench
+// Build:  hipcc --offload-arch=gfx950 -O3 -std=c++20 -I gaussianvi_amd/csrc tools/ubench/chain_bench.hip -o tools/ubench/chain_bench
 // Run:    tools/ubench/chain_bench [T=1025] [n=6] [reps=200]
 #include <hip/hip_runtime.h>
 
@@ -12,7 +12,6 @@
 #include <vector>
 
 #include "chain_launch.hpp"
-#include "kernels_bcr_seg.hpp"
 
 using namespace gvi;
 
@@ -86,19 +85,6 @@ static double relerr(const std::vector<double>& a, const std::vector<double>& b)
   return num / (den > 0 ? den : 1);
 }
 
-// ---- round-2 kernels, launched as gvi_hip.hip did ----
-struct OldPass { int level0, m, S, prev0, top; };
-static std::vector<OldPass> old_plan(int T, int n, int* threads) {
-  const int m_seg = n <= 6 ? 5 : (n <= 8 ? 4 : 3);
-  const int cap = n <= 2 ? 128 : (n <= 4 ? 64 : (n <= 6 ? 48 : (n <= 8 ? 24 : 8)));
-  std::vector<OldPass> p;
-  int level0 = 0, prev0 = 0;
-  auto alive = [&](int l) { return (int)(((int64_t)T + (1 << l) - 1) >> l); };
-  while (alive(level0) > cap) { p.push_back({level0, m_seg, 1 << m_seg, prev0, 0}); prev0 = level0; level0 += m_seg; }
-  p.push_back({level0, chain_levels(T) - level0, alive(level0), prev0, 1});
-  *threads = n <= 8 ? 1024 : 512;
-  return p;
-}
 // CHAIN_MERGE=1: the top pass and the first backward pass in one launch (chain_launch.hpp::ChainSync)
 static unsigned* g_sync_words = nullptr;
 static unsigned g_sync_seq = 0;
@@ -113,38 +99,8 @@ static gvi::ChainSync next_sync() {
   return sy;
 }
 
-template <int N>
-static void old_launch(int T, SegArgs a0, SegArgs a1, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    CK(hipFuncSetAttribute((const void*)bcr_seg_forward_dual_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    CK(hipFuncSetAttribute((const void*)bcr_seg_backward_dual_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  int threads;
-  const auto pl = old_plan(T, N, &threads);
-  for (const auto& ps : pl) {
-    for (SegArgs* a : {&a0, &a1}) { a->level0 = ps.level0; a->m = ps.m; a->S = ps.S; a->prev0 = ps.prev0; a->top = ps.top; }
-    const size_t lds = std::max(seg_fwd_lds_doubles(N, ps.S, false, ps.top != 0, threads / 64), seg_fwd_lds_doubles(N, ps.S, true, ps.top != 0, threads / 64)) * 8;
-    const int stride = ps.S << ps.level0;
-    const int blocks = ps.top ? 1 : (T + stride - 1) / stride;
-    hipLaunchKernelGGL((bcr_seg_forward_dual_kernel<N>), dim3(2 * blocks), dim3(threads), lds, st, a0, a1, blocks);
-  }
-  for (int i = (int)pl.size() - 2; i >= 0; --i) {
-    const auto& ps = pl[i];
-    for (SegArgs* a : {&a0, &a1}) { a->level0 = ps.level0; a->m = ps.m; a->S = ps.S; a->prev0 = ps.prev0; a->top = 0; }
-    const size_t lds = std::max(seg_bwd_lds_doubles(N, ps.S, false), seg_bwd_lds_doubles(N, ps.S, true)) * 8;
-    const int stride = ps.S << ps.level0;
-    const int blocks = (T + stride - 1) / stride;
-    hipLaunchKernelGGL((bcr_seg_backward_dual_kernel<N>), dim3(2 * blocks), dim3(threads), lds, st, a0, a1, blocks);
-  }
-  CK(hipGetLastError());
-}
-
-template <int N>                     // N = n where the round-2 kernels are instantiated (A/B leg), else 0
-static int run(int T, int n, int reps, bool with_old) {
+static int run(int T, int n, int reps) {
   const int nn = n * n, NP = chain_padded(n);
-  if (N == 0) with_old = false;
   std::mt19937_64 rng(1234 + T + n);
   std::normal_distribution<double> nd(0.0, 1.0);
   // two chains: Lam (SPD, factorised) and V (SPD here too, solved with pivoting), diagonally dominant blocks
@@ -166,14 +122,12 @@ static int run(int T, int n, int reps, bool with_old) {
   host_chain(T, n, D1, U1, rhs, -1.0, dummyD, dummyU, rx, dh);
 
   const size_t btD = (size_t)T * nn, btU = (size_t)std::max(0, T - 1) * nn;
-  double *dD0, *dD1, *drhs, *dSig, *dx_, *dhld, *ws0, *ws1, *ows0, *ows1;
-  int *wi0, *wi1, *obad0, *obad1;
+  double *dD0, *dD1, *drhs, *dSig, *dx_, *dhld, *ws0, *ws1;
+  int *wi0, *wi1;
   CK(hipMalloc(&dD0, (btD + btU + 1) * 8)); CK(hipMalloc(&dD1, (btD + btU + 1) * 8)); CK(hipMalloc(&drhs, (size_t)T * n * 8));
   CK(hipMalloc(&dSig, (btD + btU + 1) * 8)); CK(hipMalloc(&dx_, (size_t)T * n * 8)); CK(hipMalloc(&dhld, 8));
   CK(hipMalloc(&ws0, chain_ws_doubles(T, NP) * 8)); CK(hipMalloc(&ws1, chain_ws_doubles(T, NP) * 8));
   CK(hipMalloc(&wi0, chain_lp_entries(T) * 4)); CK(hipMalloc(&wi1, chain_lp_entries(T) * 4));
-  const size_t oldw = (size_t)9 * T * nn + (size_t)4 * T * n + T;
-  CK(hipMalloc(&ows0, oldw * 8)); CK(hipMalloc(&ows1, oldw * 8)); CK(hipMalloc(&obad0, (size_t)T * 4)); CK(hipMalloc(&obad1, (size_t)T * 4));
   CK(hipMemcpy(dD0, D0.data(), btD * 8, hipMemcpyHostToDevice)); CK(hipMemcpy(dD0 + btD, U0.data(), btU * 8, hipMemcpyHostToDevice));
   CK(hipMemcpy(dD1, D1.data(), btD * 8, hipMemcpyHostToDevice)); CK(hipMemcpy(dD1 + btD, U1.data(), btU * 8, hipMemcpyHostToDevice));
   CK(hipMemcpy(drhs, rhs.data(), (size_t)T * n * 8, hipMemcpyHostToDevice));
@@ -205,24 +159,13 @@ static int run(int T, int n, int reps, bool with_old) {
   int fail = 0;
   clear_out();
   CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync()));
-  fail |= check("new");
+  fail |= check("both");
   // single operations through the same kernels
   clear_out();
   CK(chain_launch(n, pl, a0, a1, true, false, st, nullptr, next_sync()));
   CK(chain_launch(n, pl, a0, a1, false, true, st, nullptr, next_sync()));
-  fail |= check("new/1");
-
-  SegArgs o0{}, o1{};
-  if (with_old) {
-    o0.T = T; o0.n = n; o0.need_E = 1; o0.D = dD0; o0.U = dD0 + btD; o0.rhs = nullptr; o0.rhs_scale = 1.0; o0.w.base = ows0; o0.w.bad = obad0;
-    o0.SigD = dSig; o0.SigU = dSig + btD; o0.x = nullptr; o0.hld = dhld; o0.mixVD = nullptr; o0.mixOutD = nullptr; o0.mix_step = 0; o0.pred = nullptr; o0.pred_val = 0;
-    o1 = o0;
-    o1.need_E = 0; o1.D = dD1; o1.U = dD1 + btD; o1.rhs = drhs; o1.rhs_scale = -1.0; o1.w.base = ows1; o1.w.bad = obad1; o1.SigD = nullptr; o1.SigU = nullptr; o1.x = dx_; o1.hld = nullptr;
-    clear_out();
-    if constexpr (N > 0) old_launch<N>(T, o0, o1, st);
-    fail |= check("old");
-  }
-  // run-to-run bit identity of the new kernels
+  fail |= check("single");
+  // run-to-run bit identity
   {
     std::vector<double> A(btD + btU), B(btD + btU);
     CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); CK(hipStreamSynchronize(st));
@@ -268,10 +211,9 @@ static int run(int T, int n, int reps, bool with_old) {
     CK(hipEventElapsedTime(&ms, e0, e1));
     printf("%-28s %8.2f us per call\n", name, 1e3 * ms / reps);
   };
-  time_it("new: factor || solve", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
-  time_it("new: factor only", [&]() { CK(chain_launch(n, pl, a0, a1, true, false, st, nullptr, next_sync())); });
-  time_it("new: solve only", [&]() { CK(chain_launch(n, pl, a0, a1, false, true, st, nullptr, next_sync())); });
-  if constexpr (N > 0) { if (with_old) time_it("old: factor || solve", [&]() { old_launch<N>(T, o0, o1, st); }); }
+  time_it("factor || solve", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
+  time_it("factor only", [&]() { CK(chain_launch(n, pl, a0, a1, true, false, st, nullptr, next_sync())); });
+  time_it("solve only", [&]() { CK(chain_launch(n, pl, a0, a1, false, true, st, nullptr, next_sync())); });
   {
     // the same launches with a predicate that does not hold: every block returns at its first instruction -- what the launch
     // configuration itself costs (dispatch of 2 x 33 workgroups of 16 waves with ~100 KB of LDS each, kernel arguments, drain)
@@ -288,20 +230,8 @@ static int run(int T, int n, int reps, bool with_old) {
 
 int main(int argc, char** argv) {
   const int T = argc > 1 ? atoi(argv[1]) : 1025, n = argc > 2 ? atoi(argv[2]) : 6, reps = argc > 3 ? atoi(argv[3]) : 200;
-  const bool with_old = argc > 4 ? atoi(argv[4]) != 0 : true;
-  int rc = 1;
-  switch (n) {
-    case 1: rc = run<1>(T, n, reps, with_old); break;
-    case 2: rc = run<2>(T, n, reps, with_old); break;
-    case 3: rc = run<3>(T, n, reps, with_old); break;
-    case 4: rc = run<4>(T, n, reps, with_old); break;
-    case 6: rc = run<6>(T, n, reps, with_old); break;
-    case 8: rc = run<8>(T, n, reps, with_old); break;
-    case 12: rc = run<12>(T, n, reps, with_old); break;
-    default:
-      if (!chain_supported(n)) { fprintf(stderr, "n must be in 1..16\n"); return 2; }
-      rc = run<0>(T, n, reps, false);
-  }
+  if (!chain_supported(n)) { fprintf(stderr, "n must be in 1..16\n"); return 2; }
+  const int rc = run(T, n, reps);
   printf(rc ? "FAILED\n" : "OK\n");
   return rc;
 }
