@@ -87,6 +87,11 @@ SIGNATURES = {
     "gvi_dist_info": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "gvi_ngd_get_state": [C.c_void_p] + [C.c_void_p] * 5,
     "gvi_ngd_get_gradients": [C.c_void_p] + [C.c_void_p] * 6,
+    "gvi_randn": [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p],
+    "gvi_bt_sample": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p],
+    "gvi_ngd_sample": [C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_void_p],
+    "gvi_ngd_sample_dev": [C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_void_p],
+    "gvi_bt_logpdf": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gvi_profile_enable": [C.c_void_p, C.c_int],
     "gvi_profile_last": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)],
     "gvi_profile_geometry": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)],

@@ -347,6 +347,39 @@ class Context:
         self._ck(self.lib.gvi_ngd_get_gradients(self.h, *[_p(out[k]) for k in ("dmu", "dD", "dU", "g", "VD", "VU")]))
         return out
 
+    # ---- samples of q = N(mu, Lambda^-1) and log q ----
+    def randn(self, seed, first, count):
+        """Normal numbers first .. first + count - 1 of stream `seed` (the samplers' generator)."""
+        out = np.empty(int(count))
+        self._ck(self.lib.gvi_randn(self.h, int(seed), int(first), int(count), _p(out)))
+        return out
+
+    def bt_sample(self, D, U, mu, S, seed=0, first=0, eps=None):
+        """S samples [S][T][n] of N(mu, (D, U)^-1); eps ([S][T][n]) replaces the generated normals."""
+        D, U, mu = _f64(D), _f64(U), _f64(mu)
+        if eps is not None:
+            eps = _f64(eps)
+            assert eps.size == S * self.T * self.n, "eps must hold S * T * n numbers"
+        X = np.empty((int(S), self.T, self.n))
+        self._ck(self.lib.gvi_bt_sample(self.h, _p(D), _p(U), _p(mu), int(S), int(seed), int(first), _p(eps), _p(X)))
+        return X
+
+    def ngd_sample(self, S, seed=0, first=0):
+        X = np.empty((int(S), self.T, self.n))
+        self._ck(self.lib.gvi_ngd_sample(self.h, int(S), int(seed), int(first), _p(X)))
+        return X
+
+    def ngd_sample_dev(self, S, ptr, seed=0, first=0):
+        """Into device memory at ptr (S * T * n doubles), asynchronous on the context stream."""
+        self._ck(self.lib.gvi_ngd_sample_dev(self.h, int(S), int(seed), int(first), C.c_void_p(ptr)))
+
+    def bt_logpdf(self, D, U, mu, X):
+        D, U, mu, X = _f64(D), _f64(U), _f64(mu), _f64(X)
+        S = X.size // (self.T * self.n)
+        out = np.empty(S)
+        self._ck(self.lib.gvi_bt_logpdf(self.h, _p(D), _p(U), _p(mu), S, _p(X), _p(out)))
+        return out
+
     # ---- measurement ----
     def profile_enable(self, on=True):
         self._ck(self.lib.gvi_profile_enable(self.h, int(on)))

@@ -27,6 +27,7 @@
 #include "kernels_fused.hpp"
 #include "kernels_block.hpp"
 #include "kernels_orbit_psi.hpp"
+#include "kernels_sample.hpp"
 #include "orbits.hpp"
 #include "spgh.hpp"
 
@@ -288,6 +289,10 @@ struct gvi_ctx {
   bool safe_publish = false;          // option "safe_publish": checked publish + release / acquire arrival counters (device_common.hpp)
   DevMem dbg_log;                     // gvi_debug_cost_log: ring of the costs the epilogue tails published, indexed by sequence
   int dbg_mask = 0;
+  // samplers / log-density (kernels_sample.hpp): workspaces of their own, so that a call between NGD steps touches nothing
+  // the iteration reads or writes
+  DevMem smp_ws, smp_io, smp_cws, smp_cwsi;
+  bool sample_sweep = true;           // option "sample_sweep" = 0: the samplers run the factorisation only (tools/sample_bench.py)
 };
 
 namespace {
@@ -3461,6 +3466,7 @@ gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value) {
   else if (n == "assemble_on_load") ctx->asm_on_load = value != 0;
   else if (n == "pipeline") ctx->pipeline = value != 0;
   else if (n == "chain_wave") chain_wave_enabled() = value != 0;
+  else if (n == "sample_sweep") ctx->sample_sweep = value != 0;
   else if (n == "chain_merge") { ctx->chain_merge = value != 0; ctx->chain_merge_fault = value == 2; }
   else if (n == "trust_table_degree") ctx->trust_table_degree = value != 0;
   else if (n == "safe_publish") {
@@ -3519,6 +3525,167 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant) {
   ctx->prefer_opsi = variant == 7;
   ctx->variant = variant == 7 ? 0 : variant;
   return GVI_OK;
+}
+
+// ---- sampling and log-density of q = N(mu, Lambda^-1) (kernels_sample.hpp) ----
+static gvi_status sample_check(gvi_ctx* ctx, int S) {
+  if (!ctx) return GVI_ERR_ARG;
+  if (S < 0) return fail(ctx, GVI_ERR_ARG, "S < 0");
+  if (ctx->T < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_chain_set first");
+  return GVI_OK;
+}
+
+// Factorisation (every node's R, GA, GB) and sweep of S samples into the device buffer X, all on the context stream.
+// Chain arguments of its own: no fused trial precision, no accept predicate, no selected inverse.
+static gvi_status run_sample(gvi_ctx* c, const double* D, const double* U, const double* mu, int S, uint64_t seed, int64_t first,
+                             const double* eps, double* X) {
+  if (c->n > SAMPLE_NMAX) return fail(c, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  if (S == 0) return GVI_OK;
+  const int T = c->T, n = c->n, L = chain_levels(T);
+  const size_t nn = nn_(c), Tnn = (size_t)T * nn;
+  HIPCK(c, c->smp_ws.ensure((7 * Tnn + T + 1) * 8));
+  double* w = c->smp_ws.d();
+  SampleFactorArgs fa{};
+  fa.T = T; fa.n = n; fa.L = L; fa.D = D; fa.U = U;
+  double* Db[2] = {w, w + Tnn};
+  double* Cb[2] = {w + 2 * Tnn, w + 3 * Tnn};
+  fa.R = w + 4 * Tnn; fa.GA = w + 5 * Tnn; fa.GB = w + 6 * Tnn; fa.lp = w + 7 * Tnn; fa.hld = fa.lp + T;
+  for (int l = 0; l <= L; ++l) {
+    fa.level = l;
+    fa.Dr = Db[(l + 1) & 1]; fa.Cr = Cb[(l + 1) & 1];
+    fa.Dw = Db[l & 1]; fa.Cw = Cb[l & 1];
+    const int alive = (int)(((int64_t)T + (1 << l) - 1) >> l);
+    hipLaunchKernelGGL(sample_factor_kernel, dim3(alive), dim3(64), 0, c->stream, fa);
+  }
+  HIPCK(c, hipGetLastError());
+  if (!c->sample_sweep) return GVI_OK;
+  SampleSweepArgs sa{};
+  sa.T = T; sa.n = n; sa.L = L; sa.S = S; sa.seed = seed; sa.first = first; sa.eps = eps;
+  sa.R = fa.R; sa.GA = fa.GA; sa.GB = fa.GB; sa.mu = mu; sa.hld = fa.hld; sa.X = X;
+  const size_t rowb = (size_t)T * n * 8;
+  const bool lds = rowb <= (size_t)SAMPLE_LDS_BYTES;
+  const int cap = lds ? std::min<int>(SAMPLE_TILE_MAX, (int)(SAMPLE_LDS_BYTES / rowb)) : SAMPLE_TILE_MAX;
+  sa.tile = std::max(1, std::min(cap, (S + 511) / 512));     // >= 512 workgroups while S allows, then longer tiles
+  const dim3 grid((unsigned)((S + sa.tile - 1) / sa.tile)), blk(SAMPLE_SWEEP_THREADS);
+  const size_t ldsb = lds ? (size_t)sa.tile * rowb : 0;
+  auto go = [&](auto kern) -> gvi_status {
+    if (lds) GVICK(allow_lds(c, (const void*)kern, SAMPLE_LDS_BYTES));
+    hipLaunchKernelGGL(kern, grid, blk, ldsb, c->stream, sa);
+    HIPCK(c, hipGetLastError());
+    return GVI_OK;
+  };
+  if (n <= 4) return lds ? go(sample_sweep_kernel<4, true>) : go(sample_sweep_kernel<4, false>);
+  if (n <= 8) return lds ? go(sample_sweep_kernel<8, true>) : go(sample_sweep_kernel<8, false>);
+  return lds ? go(sample_sweep_kernel<16, true>) : go(sample_sweep_kernel<16, false>);
+}
+
+gvi_status gvi_randn(gvi_ctx* ctx, uint64_t seed, int64_t first, int64_t count, double* out) {
+  if (!ctx) return GVI_ERR_ARG;
+  if (count < 0 || first < 0) return fail(ctx, GVI_ERR_ARG, "count < 0 or first < 0");
+  if (!out) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (count == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  HIPCK(ctx, ctx->smp_io.ensure((size_t)count * 8));
+  const int64_t pairs = ((first + count - 1) >> 1) - (first >> 1) + 1;
+  hipLaunchKernelGGL(randn_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, seed, first, count, ctx->smp_io.d());
+  HIPCK(ctx, hipGetLastError());
+  GVICK(d2h(ctx, out, ctx->smp_io.p, (size_t)count * 8));
+  return sync(ctx);
+}
+
+gvi_status gvi_bt_sample(gvi_ctx* ctx, const double* D, const double* U, const double* mu, int S, uint64_t seed, int64_t first,
+                         const double* eps, double* X) {
+  GVICK(sample_check(ctx, S));
+  if (!D || (!U && ctx->T > 1) || !mu || !X) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
+  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t T = ctx->T, nn = nn_(ctx), Tn = T * ctx->n, SX = (size_t)S * Tn;
+  HIPCK(ctx, ctx->smp_io.ensure((bt_count(ctx) + Tn + (eps ? SX : 0) + SX) * 8));
+  double* dD = ctx->smp_io.d();
+  double* dU = dD + T * nn;
+  double* dmu = dU + (T - 1) * nn;
+  double* dX = dmu + Tn;
+  double* deps = eps ? dX + SX : nullptr;
+  GVICK(h2d(ctx, dD, D, T * nn * 8));
+  if (T > 1) GVICK(h2d(ctx, dU, U, (T - 1) * nn * 8));
+  GVICK(h2d(ctx, dmu, mu, Tn * 8));
+  if (eps) GVICK(h2d(ctx, deps, eps, SX * 8));
+  GVICK(run_sample(ctx, dD, dU, dmu, S, seed, first, deps, dX));
+  GVICK(d2h(ctx, X, dX, SX * 8));
+  return sync(ctx);
+}
+
+static gvi_status ngd_sample_to(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, double* X_dev) {
+  NgdState& g = ctx->ngd;
+  const size_t Tnn = (size_t)ctx->T * nn_(ctx);
+  return run_sample(ctx, g.Lam[g.cur].d(), g.Lam[g.cur].d() + Tnn, g.mu[g.cur].d(), S, seed, first, nullptr, X_dev);
+}
+
+gvi_status gvi_ngd_sample(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, double* X) {
+  GVICK(sample_check(ctx, S));
+  if (!X) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
+  GVICK(ngd_check(ctx));
+  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t SX = (size_t)S * ctx->T * ctx->n;
+  HIPCK(ctx, ctx->smp_io.ensure(SX * 8));
+  GVICK(ngd_sample_to(ctx, S, seed, first, ctx->smp_io.d()));
+  GVICK(d2h(ctx, X, ctx->smp_io.p, SX * 8));
+  return sync(ctx);
+}
+
+gvi_status gvi_ngd_sample_dev(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, double* X_dev) {
+  GVICK(sample_check(ctx, S));
+  if (!X_dev) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
+  GVICK(ngd_check(ctx));
+  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  return ngd_sample_to(ctx, S, seed, first, X_dev);
+}
+
+gvi_status gvi_bt_logpdf(gvi_ctx* ctx, const double* D, const double* U, const double* mu, int S, const double* X, double* logq) {
+  GVICK(sample_check(ctx, S));
+  if (!D || (!U && ctx->T > 1) || !mu || !X || !logq) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  const int NP = chain_padded(ctx->n);
+  if (!NP) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const int T = ctx->T, n = ctx->n;
+  const size_t nn = nn_(ctx), Tn = (size_t)T * n, SX = (size_t)S * Tn;
+  HIPCK(ctx, ctx->smp_io.ensure((bt_count(ctx) + Tn + SX + (size_t)S * T + S + 1) * 8));
+  double* dD = ctx->smp_io.d();
+  double* dU = dD + (size_t)T * nn;
+  double* dmu = dU + (size_t)(T - 1) * nn;
+  double* dX = dmu + Tn;
+  double* dQ = dX + SX;
+  double* dl = dQ + (size_t)S * T;
+  double* dh = dl + S;
+  GVICK(h2d(ctx, dD, D, (size_t)T * nn * 8));
+  if (T > 1) GVICK(h2d(ctx, dU, U, (size_t)(T - 1) * nn * 8));
+  GVICK(h2d(ctx, dmu, mu, Tn * 8));
+  GVICK(h2d(ctx, dX, X, SX * 8));
+  // the existing half log-det (chain kernels), on arguments and a workspace of its own: no mix, no predicate, no back pass
+  HIPCK(ctx, ctx->smp_cws.ensure(chain_ws_doubles(T, NP) * 8));
+  HIPCK(ctx, ctx->smp_cwsi.ensure(chain_lp_entries(T) * sizeof(int)));
+  ChainArgs a{};
+  a.T = T; a.n = n; a.need_back = 0;
+  a.D = dD; a.U = dU; a.rhs_scale = 1.0;
+  a.ws = ctx->smp_cws.d(); a.wsi = (int*)ctx->smp_cwsi.p; a.hld = dh;
+  const hipError_t e = chain_launch(n, chain_plan(T, n), a, a, true, false, ctx->stream);
+  if (e == hipErrorInvalidValue) return fail(ctx, GVI_ERR_UNSUPPORTED, "chain kernels: block size / LDS budget");
+  HIPCK(ctx, e);
+  const int64_t items = (int64_t)S * T;
+  hipLaunchKernelGGL(logpdf_quad_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, T, n, S, dD, dU, dmu, dX, dQ);
+  hipLaunchKernelGGL(logpdf_reduce_kernel, dim3(S), dim3(256), 0, ctx->stream, T, n, dQ, dh, dl);
+  HIPCK(ctx, hipGetLastError());
+  GVICK(d2h(ctx, logq, dl, (size_t)S * 8));
+  return sync(ctx);
 }
 
 }  // extern "C"

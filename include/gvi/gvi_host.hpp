@@ -1382,6 +1382,35 @@ class GVIGH {
   inline SpMat precision() const { return precision_ref(); }
   inline SpMat covariance() const { return covariance_ref(); }
 
+  // Exact samples of q = N(mean(), precision()^-1), one per column (no reference counterpart; gvi_hip.h, "samples of q").
+  // DeviceResident: drawn from the resident state (gvi_ngd_sample); FactorWise: from the host blocks (gvi_bt_sample).
+  // Column j is sample j of stream `seed`, the same numbers for both paths.
+  MatrixXd sample(int n_samples, uint64_t seed = 0) {
+    if (n_samples < 0) throw GviError(GVI_ERR_ARG, "n_samples < 0");
+    std::vector<double> X((size_t)n_samples * _dim);
+    if (_exec == Execution::DeviceResident) {
+      sync_resident();
+      _dev->check(gvi_ngd_sample(_dev->get(), n_samples, seed, 0, X.data()));
+    } else {
+      _dev->check(gvi_bt_sample(_dev->get(), _D.data(), _U.data(), _mu.data(), n_samples, seed, 0, nullptr, X.data()));
+    }
+    MatrixXd M(_dim, n_samples);
+    for (int j = 0; j < n_samples; ++j)
+      for (int i = 0; i < _dim; ++i) M(i, j) = X[(size_t)j * _dim + i];
+    return M;
+  }
+  // log q(x) of every column of X (gvi_bt_logpdf)
+  VectorXd log_density(const MatrixXd& X) {
+    if (X.rows() != _dim) throw GviError(GVI_ERR_ARG, "log_density: X must have mean().size() rows");
+    const int S = X.cols();
+    std::vector<double> Xr((size_t)S * _dim);
+    for (int j = 0; j < S; ++j)
+      for (int i = 0; i < _dim; ++i) Xr[(size_t)j * _dim + i] = X(i, j);
+    VectorXd out(S);
+    _dev->check(gvi_bt_logpdf(_dev->get(), _D.data(), _U.data(), _mu.data(), S, Xr.data(), out.data()));
+    return out;
+  }
+
   // inverse(mat) (gvibase/GVI-GH.h:161-165): the block-tridiagonal part of mat^-1 (EigenWrapper::inv_sparse /
   // inverse_GBP), computed by the device's selected inverse
   inline SpMat inverse(const SpMat& mat) {

@@ -303,6 +303,30 @@ gvi_status gvi_ngd_get_state(gvi_ctx* ctx, double* mu, double* D, double* U, dou
 gvi_status gvi_ngd_get_gradients(gvi_ctx* ctx, double* dmu, double* dD, double* dU, double* g,
                                  double* VD, double* VU);
 
+/* ---- samples of q = N(mu, Lambda^-1), Lambda = (D, U) block-tridiagonal, and log q (no reference counterpart: the
+ *      reference has no sampler).  X[S][T][n]; an exact draw y ~ N(0, Lambda^-1) is the chain solver's back-substitution
+ *      with standard normals as right-hand side.  S = 0 is a no-op; S < 0 or a NULL buffer:
+ *      GVI_ERR_ARG; n > 16: GVI_ERR_UNSUPPORTED; Lambda not positive definite (half log-det NaN): every entry of X / logq
+ *      is NaN.
+ *      Generator (restated in tests/test_sample_host.py): Philox4x32-10, key = seed (low word first); normal number i
+ *      of stream `seed` comes from counter c = i >> 1 (words 0-1, words 2-3 zero) by Box-Muller:
+ *      u1 = ((w0 | w1 << 32) >> 11) + 0.5) 2^-53, u2 the same from (w2, w3), r = sqrt(-2 ln u1),
+ *      z[2c] = r cos(2 pi u2), z[2c + 1] = r sin(2 pi u2).  Sample j uses normals (first + j) T n ... (first + j + 1) T n - 1
+ *      in [t][k] order, so a batch may be split across calls (or ranks) without changing it. ---- */
+/* out[i] = normal number first + i of stream seed (host output). */
+gvi_status gvi_randn(gvi_ctx* ctx, uint64_t seed, int64_t first, int64_t count, double* out);
+/* Host buffers.  eps ([S][T][n], optional): the normals to use instead of the generator (seed / first are ignored). */
+gvi_status gvi_bt_sample(gvi_ctx* ctx, const double* D, const double* U, const double* mu, int S, uint64_t seed, int64_t first,
+                         const double* eps, double* X);
+/* Samples of the resident state (mu, D, U) after gvi_ngd_init / _step / _run / prox_*; the state never leaves HBM and
+ * the iteration is not disturbed.  GVI_ERR_STATE before gvi_ngd_init.  The _dev twin writes device memory, asynchronously
+ * on the context stream. */
+gvi_status gvi_ngd_sample(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, double* X);
+gvi_status gvi_ngd_sample_dev(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, double* X_dev);
+/* logq[j] = -1/2 (x_j - mu)^T Lambda (x_j - mu) + 1/2 log det Lambda - (T n / 2) log 2 pi; host buffers, X[S][T][n]. */
+gvi_status gvi_bt_logpdf(gvi_ctx* ctx, const double* D, const double* U, const double* mu, int S, const double* X,
+                         double* logq);
+
 /* ---- measurement hooks (bench.py): HIP-event time of the last moments / cost kernel launch of a
  *      set, in milliseconds, measured on the context stream; enable before the launches.
  *      on = 1: only the dominant launch (set 0, full moments pass) is bracketed -- an event pair costs
@@ -355,6 +379,7 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *   GVI_SPGH_EXTENDED    --                  auto     long-double merge of the Smolyak weights (0 / 1 force)  weights
  *   GVI_RCCL_PATH        --                  --       the only librccl candidate gvi_dist_* tries            --
  *   --                   chol_sqrt           1        Cholesky factor for sum-of-squares psi                 agree to 1e-10
+ *   --                   sample_sweep        1        samplers: 0 runs the factorisation only (timing)       X not written
  *   --                   trust_table_degree  0        gvi_factors_add_table: the table is the rule of degree p  --
  *   --                   jacobi_tol_exp      -34      stopping threshold of the symmetric-root solve         rounding
  *   --                   split_flush, target_waves, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, dual_chain,
@@ -387,7 +412,7 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * (the word is stored wrong on purpose).
  * Names: split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, dual_chain, warm_start, no_scost, target_waves,
  * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge,
- * trust_table_degree, safe_publish. */
+ * trust_table_degree, safe_publish, sample_sweep. */
 gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value);
 
 #ifdef __cplusplus
