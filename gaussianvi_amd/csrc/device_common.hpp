@@ -6,12 +6,12 @@ namespace gvi {
 
 // One-wave workgroups (blockDim == 64): LDS operations of a wave execute in order, so a wave-level
 // "barrier" only has to drain the LDS queue and stop the compiler from moving memory operations
-// across it.  Unlike __syncthreads() it does not wait for outstanding global loads / stores (vmcnt)
-// -- which made every barrier of the first sequential chain kernels cost a memory round trip.
+// across it.  It does not wait for outstanding global loads / stores (vmcnt) -- and neither does __syncthreads() on
+// gfx950: a hand-over of global data to another wave or workgroup needs an explicit s_waitcnt vmcnt(0) by the producer.
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// LDS-only workgroup barrier: unlike __syncthreads() it does not drain outstanding global loads / stores
-// (vmcnt); everything the phases exchange goes through LDS.
+// LDS-only workgroup barrier: it does not drain outstanding global loads / stores (vmcnt); everything the phases
+// exchange goes through LDS.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Publish a scalar result to host-mapped (fine-grained, uncached) memory.

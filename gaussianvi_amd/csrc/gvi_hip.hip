@@ -1040,7 +1040,10 @@ gvi_status run_chain(gvi_ctx* c, const ChainArgs& a0, const ChainArgs& a1, bool 
     constexpr unsigned RING = 64;
     if (!c->chain_sync.p) {
       HIPCK(c, c->chain_sync.ensure(RING * 2 * sizeof(unsigned)));
-      HIPCK(c, hipMemset(c->chain_sync.p, 0, RING * 2 * sizeof(unsigned)));       // (once per context)
+      // (once per context) on the launch stream, then waited for: the chain kernels run on non-blocking streams (c->stream,
+      // or c->side for a side-stream solve), which a clear on the null stream would not be ordered before
+      HIPCK(c, hipMemsetAsync(c->chain_sync.p, 0, RING * 2 * sizeof(unsigned), st));
+      HIPCK(c, hipStreamSynchronize(st));
     }
     if (++c->chain_seq == 0) ++c->chain_seq;       // 0 is the cleared state of a word
     sy.seq = c->chain_seq;

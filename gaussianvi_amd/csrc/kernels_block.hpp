@@ -111,6 +111,12 @@ __device__ __forceinline__ void block_epilogue(const Block3Args& A, const BlockS
   epilogue_body_t<DT>(e, k, sm, 2, P);
 }
 
+// End of phase 1 in the lead wave: its stores of the products must have reached L2 before the barrier releases phase 2.
+// The priors' phase 2 (sreg_body / sreg_pipe_body) reads H through the constant address space, i.e. with scalar loads,
+// which are served by the scalar cache and L2 and never see the vector L1 -- and __syncthreads() does not wait for
+// outstanding stores (vmcnt) on gfx950.  (tests/test_handover_isa.py checks the wait in the built code object.)
+__device__ __forceinline__ void block_products_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
 // LDS of one wave's phases 1 and 3 (doubles), d <= 8; a workgroup has four of them
 __host__ __device__ inline size_t block3_lds_doubles() {
   constexpr size_t d = 8, dd = 64, dp = 8;
@@ -146,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void factor_block3_kernel(Block3Args A) {
     const BlockSet& S = A.s[1];
     const int nch = block3_nch(S.a.nchunk), k = b * (4 / nch) + wave / nch, c = wave % nch;
     const bool lead = c == 0 && k < K1;
-    if (lead) block_products<4, false>(A, S, k, smw);          // (symmetric root: psi is not a sum of squares)
+    if (lead) { block_products<4, false>(A, S, k, smw); block_products_drain(); }   // (symmetric root: psi is not a sum of squares)
     __syncthreads();
     reg_body<4, PsiH, true>(S.a, 0, 0, hs, red, k, c);
     __syncthreads();
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void factor_block3_kernel(Block3Args A) {
     const BlockSet& S = A.s[0];
     const int nch = block3_nch(S.a.nchunk), k = (b - nb1) * (4 / nch) + wave / nch, c = wave % nch;
     const bool lead = c == 0 && k < K0;
-    if (lead) block_products<8, true>(A, S, k, smw);
+    if (lead) { block_products<8, true>(A, S, k, smw); block_products_drain(); }
     __syncthreads();
     if (A.pipe) sreg_pipe_dispatch<8, 4>(S.a, 0, 0, hs, red, k, c);
     else sreg_body<8, 4, true>(S.a, 0, 0, hs, red, k, c);
@@ -165,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void factor_block3_kernel(Block3Args A) {
     const BlockSet& S = A.s[2];
     const int nch = block3_nch(S.a.nchunk), k = (b - nb1 - nb0) * (4 / nch) + wave / nch, c = wave % nch;
     const bool lead = c == 0 && k < K2;
-    if (lead) block_products<4, true>(A, S, k, smw);
+    if (lead) { block_products<4, true>(A, S, k, smw); block_products_drain(); }
     __syncthreads();
     reg_body<4, PsiA, true>(S.a, 0, 0, hs, red, k, c);
     __syncthreads();

@@ -96,7 +96,7 @@ struct ChainArgs {
   const double* pred;    // predicated launch (device_common.hpp, pred_skip) or null
   double pred_val;
   // top pass + first backward pass in ONE launch (chain_top_back_kernel): the top pass's workgroup stores sync_seq to *sync
-  // (release, agent scope) behind its last store; the backward workgroups wait for it in front of their first load of what
+  // (relaxed, agent scope) behind its last store (chain_signal); the backward workgroups wait for it in front of their first load of what
   // the top pass wrote (chain_wait).  null: separate launches
   unsigned* sync;
   unsigned sync_seq;
@@ -547,12 +547,15 @@ __host__ __device__ constexpr size_t bwd_lds_doubles(int S) {
 // ---- hand-over inside a launch (chain_top_back_kernel) ----
 // No fences: a release at agent scope writes the XCD's whole L2 back and an acquire invalidates it -- with both the merged
 // launch took exactly as long as the two launches it replaces (chain_bench, T = 1025, n = 6: 47.6 vs 47.4 us).  Instead the
-// producer stores what the consumers read WRITE-THROUGH at agent scope (st_out), every thread waits for its stores at the
-// barrier (vmcnt(0): the workgroup-scope release of __syncthreads), and thread 0 stores the word; the consumers read those
-// values -- and only those -- with agent-scope loads (chain_ld) behind the word.  Same protocol as the epilogue's tail
-// (kernels_factor.hpp, epi_tail).
+// producer stores what the consumers read WRITE-THROUGH at agent scope (st_out), every thread waits for its own stores
+// (s_waitcnt vmcnt(0)) in front of the barrier, and thread 0 stores the word; the consumers read those values -- and only
+// those -- with agent-scope loads (chain_ld) behind the word.  Same protocol as the epilogue's tail (kernels_factor.hpp,
+// epi_tail).  The explicit wait is needed: __syncthreads() is a workgroup-scope release, which on gfx950 (outside
+// threadgroup-split mode) is s_waitcnt lgkmcnt(0) + s_barrier WITHOUT vmcnt(0) -- the word could overtake other waves'
+// data stores.  tests/test_handover_isa.py checks the order in the built code object.
 __device__ __forceinline__ void chain_signal(unsigned* sync, const unsigned seq) {
   if (!sync) return;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) __hip_atomic_store(sync, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
