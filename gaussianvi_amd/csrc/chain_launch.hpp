@@ -148,6 +148,10 @@ inline hipError_t chain_launch_t(const ChainPlan& pl, ChainArgs a0, ChainArgs a1
 inline bool& chain_wave_enabled() { static bool on = true; return on; }
 inline bool chain_wave_applies(int T, int n) { return chain_wave_enabled() && n >= 1 && n <= chain_wave::WN && T >= 1 && T <= chain_wave::WT_MAX; }
 
+// chain_asm_dense_enabled() = false keeps an assemble-on-load on the generic set loop (A/B leg of the batched first-pass load,
+// kernels_chain.hpp AsmDense: GVI_ASM_DENSE=0, option "asm_dense")
+inline bool& chain_asm_dense_enabled() { static bool on = true; return on; }
+
 // n: the caller's block size (a0.n / a1.n are set here).  AL: the factor sets of an assemble-on-load (a0.asm_on / a1.asm_on), else null
 inline hipError_t chain_launch(int n, const ChainPlan& pl, ChainArgs a0, ChainArgs a1, bool on0, bool on1, hipStream_t st,
                                const AsmList* AL = nullptr, const ChainSync& sync = ChainSync{}) {
@@ -155,6 +159,10 @@ inline hipError_t chain_launch(int n, const ChainPlan& pl, ChainArgs a0, ChainAr
   AsmList none{};
   const AsmList& L = AL ? *AL : none;
   if (!AL) a0.asm_on = a1.asm_on = 0;
+  else if (chain_asm_dense_enabled() && chain_asm_dense(L, n) && (on0 ? a0.T : a1.T) > 1) {     // the first pass's batched load path (kernels_chain.hpp, AsmDense)
+    if (a0.asm_on) a0.asm_on = ASM_DENSE;
+    if (a1.asm_on) a1.asm_on = ASM_DENSE;
+  }
   if (chain_wave_applies(on0 ? a0.T : a1.T, n)) {
     const int nb0 = on0 ? 1 : 0, nb = nb0 + (on1 ? 1 : 0);
     if (nb == 0) return hipSuccess;

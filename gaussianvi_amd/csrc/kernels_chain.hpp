@@ -89,7 +89,7 @@ struct ChainArgs {
   // vector g are not read but ASSEMBLED from the per-factor results (the sums of bt_scatter_all_kernel, same order):
   //   solve (rhs != null):  (D, U, rhs) <- assembled (V_D, V_U, g), written out to asmD / asmU / asmG on the way;
   //   factorisation:        the mixed-in matrix mixV <- assembled (the chain operated on is D + mix_step (V - D)).
-  int asm_on;
+  int asm_on;            // 0: off; 1: on; ASM_DENSE (set by chain_launch): on, and the sets fit the batched load path
   double* asmD;
   double* asmU;
   double* asmG;
@@ -169,6 +169,99 @@ __device__ __forceinline__ void asm_pair(const AsmList& L, const int n, const in
 #pragma unroll
     for (int u = 0; u < 2; ++u) { vD[u] += (0.0 + d0[u]) + d1[u]; vU[u] += 0.0 + u0[u]; }
   }
+}
+
+// ---- DENSE assemble-on-load (ChainArgs::asm_on == ASM_DENSE; the host classifies, chain_asm_dense below) ----
+// asm_pair / asm_element walk the sets in a run-time loop: per set four or five scalar loads of its fields one after the other,
+// the element loads each behind its own branch, and a wait for them before the next set starts -- about five dependent
+// vector-memory round trips and fifteen scalar ones in front of a pass's first level, on data the factor pass of other XCDs
+// wrote a moment ago.  None of these loads depends on another.  The common pattern -- at most ONE binary set (d = 2n) and at
+// most ONE unary set (d = n), neither sparse -- needs no loop: the fields of both are fetched in one scalar batch, every
+// address is formed branch-free (index clamped to 0, value selected to 0.0 where the generic path skips the load), and the
+// caller issues all loads of its round before the first use.  The sums keep asm_pair's association, in set order.
+constexpr int ASM_DENSE = 2;
+struct AsmDense {
+  int Kb, Ku;                       // factors of the binary / unary set (0: absent)
+  const double *Vb, *Vu, *gb, *gu;  // their Vddmu / Vdmu (an absent set: a valid pointer, never selected)
+  bool b_first, two_sets;           // set order of the sums
+};
+__device__ __forceinline__ AsmDense asm_dense_fields(const AsmList& L, const int n) {
+  const AsmSet& s0 = L.s[0];
+  const AsmSet& s1 = L.s[1];
+  const int K0 = s0.K, d0 = s0.d, K1 = s1.K;
+  const double *V0 = s0.Vddmu, *V1 = s1.Vddmu, *g0 = s0.Vdmu, *g1 = s1.Vdmu;
+  AsmDense q;
+  q.two_sets = L.nsets > 1;
+  q.b_first = d0 == 2 * n;
+  const bool sec = q.two_sets;
+  q.Kb = q.b_first ? K0 : (sec ? K1 : 0);
+  q.Ku = q.b_first ? (sec ? K1 : 0) : K0;
+  q.Vb = (q.b_first || !sec) ? V0 : V1;
+  q.gb = (q.b_first || !sec) ? g0 : g1;
+  q.Vu = (q.b_first && sec) ? V1 : V0;
+  q.gu = (q.b_first && sec) ? g1 : g0;
+  return q;
+}
+// the loads of one element (r, c) of state t: predicates p[0..3] and values v[0..3] = binary set's own block, its left
+// neighbour's block, its coupling block; unary set's block.  (Plain arrays, not a struct: an array of structs in the caller
+// was not promoted to registers at N = 1 -- 36 bytes of scratch.)
+__device__ __forceinline__ void asm_dense_issue(const AsmDense& q, const int n, const int t, const int r, const int c, const bool onD,
+                                                const bool onU, bool (&p)[4], double (&v)[4]) {
+  // one 32 x 32 -> 64 bit product per set; the other two blocks of the binary set sit at block-uniform distances from the first:
+  //   (t - 1) d d + (n + r) d + n + c = i0 + n - d d / 2,   t d d + r d + n + c = i0 + n        (d = 2n)
+  // (cheap enough that the selects below stay selects: behind a product each, the compiler branched around the address)
+  const unsigned d = 2u * (unsigned)n, dd = d * d;
+  p[0] = onD && t < q.Kb;
+  p[1] = onD && t > 0 && t - 1 < q.Kb;
+  p[2] = onU && t < q.Kb;
+  p[3] = onD && t < q.Ku;
+  const unsigned long long i0 = (unsigned long long)(unsigned)t * dd + ((unsigned)r * d + (unsigned)c);
+  const unsigned long long j0 = (unsigned long long)(unsigned)t * (unsigned)(n * n) + (unsigned)(r * n + c);
+  v[0] = q.Vb[p[0] ? i0 : 0ull];
+  v[1] = q.Vb[p[1] ? i0 + (unsigned)n - dd / 2 : 0ull];
+  v[2] = q.Vb[p[2] ? i0 + (unsigned)n : 0ull];
+  v[3] = q.Vu[p[3] ? j0 : 0ull];
+}
+__device__ __forceinline__ void asm_dense_sum(const AsmDense& q, const bool (&p)[4], const double (&v)[4], double& vD, double& vU) {
+  const double sDb = (0.0 + (p[0] ? v[0] : 0.0)) + (p[1] ? v[1] : 0.0), sUb = 0.0 + (p[2] ? v[2] : 0.0);   // binary set
+  const double sDu = (0.0 + (p[3] ? v[3] : 0.0)) + 0.0, sUu = 0.0 + 0.0;                                   // unary set
+  vD = 0.0 + (q.b_first ? sDb : sDu);
+  vU = 0.0 + (q.b_first ? sUb : sUu);
+  if (q.two_sets) { vD += q.b_first ? sDu : sDb; vU += q.b_first ? sUu : sUb; }
+}
+// entry r of g[t] (asm_element, which = 2): binary set's own factor, its left neighbour's; unary set's
+__device__ __forceinline__ void asm_dense_g_issue(const AsmDense& q, const int n, const int t, const int r, const bool on, bool (&p)[3],
+                                                  double (&v)[3]) {
+  const unsigned d = 2u * (unsigned)n;
+  p[0] = on && t < q.Kb;
+  p[1] = on && t > 0 && t - 1 < q.Kb;
+  p[2] = on && t < q.Ku;
+  const unsigned long long i0 = (unsigned long long)(unsigned)t * d + (unsigned)r;       // (t - 1) d + n + r = i0 - n
+  v[0] = q.gb[p[0] ? i0 : 0ull];
+  v[1] = q.gb[p[1] ? i0 - (unsigned)n : 0ull];
+  v[2] = q.gu[p[2] ? (unsigned long long)(unsigned)t * (unsigned)n + (unsigned)r : 0ull];
+}
+__device__ __forceinline__ double asm_dense_g_sum(const AsmDense& q, const bool (&p)[3], const double (&v)[3]) {
+  double sb = 0.0, su = 0.0;
+  sb = p[0] ? sb + v[0] : sb;
+  sb = p[1] ? sb + v[1] : sb;
+  su = p[2] ? su + v[2] : su;
+  double acc = 0.0 + (q.b_first ? sb : su);
+  if (q.two_sets) acc += q.b_first ? su : sb;
+  return acc;
+}
+// host: the pattern above (every set present, with data; set order free)
+inline bool chain_asm_dense(const AsmList& L, const int n) {
+  if (L.nsets < 1 || L.nsets > 2) return false;
+  int nb = 0, nu = 0;
+  for (int i = 0; i < L.nsets; ++i) {
+    const AsmSet& s = L.s[i];
+    if (s.nsp != 0 || s.K < 1 || !s.Vdmu || !s.Vddmu) return false;
+    if (s.d == 2 * n) ++nb;
+    else if (s.d == n) ++nu;
+    else return false;
+  }
+  return nb <= 1 && nu <= 1;
 }
 
 constexpr int chain_threads(int n) { return n <= 8 ? 1024 : 512; }
@@ -584,11 +677,22 @@ __device__ __forceinline__ double chain_ld(const double* p, const bool fresh) {
   return fresh ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
 }
 
+// pred_fail that stays where it is written.  The compare is invariant in the load loop, so the compiler hoisted it -- and with
+// it the wait for the predicate word -- in front of the loop: s_waitcnt vmcnt(0) ahead of the first data load, a dependent
+// round trip at the start of every pass, which is what LazyPred exists to avoid (ISA of chain_forward_kernel<6, false>).
+// Passing the value through a volatile asm pins the wait; the scheduling barrier keeps the loads written before it in front of
+// it (without it seven of a round's twelve loads were issued behind the wait).
+__device__ __forceinline__ bool pred_fail_here(LazyPred& p) {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" : "+v"(p.v));
+  return pred_fail(p);
+}
+
 // ---- passes A / B: one workgroup per segment ----
 template <bool PIVOT, bool HAS_E, bool HAS_Y, bool TOP, int N>
 __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& AL, const int bid, double* sm) {
   constexpr int nn = N * N;
-  const LazyPred lpred = pred_issue(a.pred, a.pred_val);        // checked in front of the first store (device_common.hpp)
+  LazyPred lpred = pred_issue(a.pred, a.pred_val);              // checked in front of the first store (device_common.hpp)
   const int T = a.T, S = a.S, st = 1 << a.level0;
   // the wave index as a SCALAR: everything derived from it (node, offsets, has_b) is then wave-uniform for the compiler too
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nwaves = blockDim.x >> 6, nthr = blockDim.x;
@@ -629,9 +733,68 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
     }
   }
   // ---- load (+ fold what the previous pass left at the segment boundaries) ----
+  // dense assemble-on-load (asm_dense_fields): block-uniform.  The solve's g entry of this thread (the rhs loop below handles
+  // entry e = tid first) is requested with the loads of the first round, not behind the first store (gpre)
+  const bool dense = first && a.asm_on == ASM_DENSE;
+  AsmDense AD{};
+  [[maybe_unused]] double gpre = 0.0;
+  if (dense) AD = asm_dense_fields(AL, a.n);
   for (int e0 = tid; e0 < cnt * nn; e0 += 2 * nthr) {
     double dv[2], cu[2];
     bool on[2], hasc[2];
+    if (dense) {
+      // every load of the round goes out before the first use: per element the binary set's three blocks, the unary set's
+      // one and (factorisation) D and U.  (r, c) of the caller's block = (r, c) of the padded one wherever xe >= 0
+      bool lp0[4], lp1[4];
+      double lv0[4], lv1[4];
+      bool val[2];
+      [[maybe_unused]] double d_in[2], u_in[2];
+      int xs[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int e = e0 + u * nthr;
+        on[u] = e < cnt * nn;
+        const int j = on[u] ? e / nn : 0, el = on[u] ? e % nn : 0, x = x0 + j * st;
+        const int r = el / N, c = el % N;
+        val[u] = on[u] && r < a.n && c < a.n;
+        hasc[u] = on[u] && x + st < T;
+        xs[u] = el;
+        if (u == 0) asm_dense_issue(AD, a.n, x, r, c, val[u], val[u] && hasc[u], lp0, lv0);
+        else asm_dense_issue(AD, a.n, x, r, c, val[u], val[u] && hasc[u], lp1, lv1);
+        if constexpr (!HAS_Y) {
+          const size_t ge = (size_t)x * (a.n * a.n) + r * a.n + c;
+          d_in[u] = a.D[val[u] ? ge : 0];
+          u_in[u] = a.U[(val[u] && hasc[u]) ? ge : 0];
+        }
+      }
+      [[maybe_unused]] bool gp[3];
+      [[maybe_unused]] double gv[3];
+      if constexpr (HAS_Y) {                          // (requested in every round, in the same batch: rounds beyond the first
+        const int j = tid / N, r = tid % N;           // exist only for N >= 12, and a load is cheaper than a branch here)
+        asm_dense_g_issue(AD, a.n, x0 + j * st, r, j < cnt && r < a.n, gp, gv);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (HAS_Y) { const double gs = asm_dense_g_sum(AD, gp, gv); gpre = e0 == tid ? gs : gpre; }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int el = xs[u];
+        double vD, vU;
+        if (u == 0) asm_dense_sum(AD, lp0, lv0, vD, vU);
+        else asm_dense_sum(AD, lp1, lv1, vD, vU);
+        dv[u] = cu[u] = 0.0;
+        if (on[u]) {
+          const double pad = (el / N == el % N) ? 1.0 : 0.0;                                        // identity padding
+          if constexpr (HAS_Y) {
+            dv[u] = val[u] ? vD : pad;
+            if (hasc[u] && val[u]) cu[u] = vU;
+          } else {
+            dv[u] = val[u] ? d_in[u] : pad;
+            if (val[u]) dv[u] = dv[u] + a.mix_step * (vD - dv[u]);                                  // trial_kernel's arithmetic
+            if (hasc[u] && val[u]) { cu[u] = u_in[u]; cu[u] = cu[u] + a.mix_step * (vU - cu[u]); }
+          }
+        }
+      }
+    } else {
     // assemble-on-load: the V_D / V_U elements of both elements of this round in one sweep over the factor sets
     double aD[2] = {0.0, 0.0}, aU[2] = {0.0, 0.0};
     if (first && a.asm_on) {
@@ -683,7 +846,8 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
         }
       }
     }
-    if (pred_fail(lpred)) return;                   // (block-uniform; nothing has been written yet)
+    }
+    if (pred_fail_here(lpred)) return;              // (block-uniform; nothing has been written yet)
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int e = e0 + u * nthr;
@@ -707,6 +871,7 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
     }
   }
   if (pred_fail(lpred)) return;
+  CHAIN_STAMP(TOP && HAS_E);                        // end of the load rounds (what follows: zero fill, rhs, barrier)
   for (int e = tid; e < (S + 1) * nn; e += nthr) sm[oRl + e] = 0.0;
   for (int e = tid; e < (S + 1 - cnt) * nn; e += nthr) sm[oDl + cnt * nn + e] = 0.0;
   if (tid < N + (N & 1)) sm[oZero + tid] = 0.0;
@@ -717,7 +882,7 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
       if (j < cnt) {
         if (first) {
           if (a.asm_on && r < a.n) {
-            const double gv = asm_element(AL, a.n, x, 2, r, 0);
+            const double gv = (dense && e == tid) ? gpre : asm_element(AL, a.n, x, 2, r, 0);
             a.asmG[(size_t)x * a.n + r] = gv;
             v = a.rhs_scale * gv;
           } else v = r < a.n ? a.rhs_scale * a.rhs[(size_t)x * a.n + r] : 0.0;

@@ -2,12 +2,13 @@
 // operations of an NGD iteration side by side:
 //   factorisation of Lam (1/2 log det + tridiagonal blocks of the inverse)  ||  pivoted solve V x = -g
 // Build:  hipcc --offload-arch=gfx950 -O3 -std=c++20 -I gaussianvi_amd/csrc tools/ubench/chain_bench.hip -o tools/ubench/chain_bench
-// Run:    tools/ubench/chain_bench [T=1025] [n=6] [reps=200]
+// Run:    tools/ubench/chain_bench [T=1025] [n=6] [reps=200]        (ASM_LEG=0: without the assemble-on-load leg)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -83,6 +84,25 @@ static double relerr(const std::vector<double>& a, const std::vector<double>& b)
   double num = 0, den = 0;
   for (size_t i = 0; i < a.size(); ++i) { num = std::max(num, fabs(a[i] - b[i])); den = std::max(den, fabs(b[i])); }
   return num / (den > 0 ? den : 1);
+}
+
+// Assemble-on-load leg: what the factor pass leaves for the chain's first pass -- per-factor Vdmu / Vddmu of a binary set
+// (K = T - 1, d = 2n) and a unary set (K = T, d = n) -- rewritten by a launch of its own in front of every chain call, so the
+// first pass reads lines that other XCDs wrote a moment ago, as in the iteration.  Values: SPD-dominant blocks that depend
+// on `salt` (a different matrix every call; the unary set carries the diagonal weight).
+__global__ void asm_fill_kernel(double* Vdmu_b, double* Vddmu_b, double* Vdmu_u, double* Vddmu_u, int T, int n, unsigned salt) {
+  const int d = 2 * n;
+  const size_t nb = (size_t)(T - 1) * d * d, nu = (size_t)T * n * n, gb = (size_t)(T - 1) * d, gu = (size_t)T * n;
+  const size_t total = nb + nu + gb + gu;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    unsigned h = (unsigned)i * 2654435761u + salt * 40503u;
+    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
+    const double v = (double)(h & 0xffff) / 65536.0 - 0.5;            // [-0.5, 0.5)
+    if (i < nb) { const size_t e = i % ((size_t)d * d); const int r = (int)(e / d), c = (int)(e % d); Vddmu_b[i] = r == c ? 1.0 + 0.1 * v : 0.0; if (r != c) { const int lo = r < c ? r : c, hi = r < c ? c : r; unsigned g = (unsigned)((i / ((size_t)d * d)) * d * d + lo * d + hi) * 2654435761u + salt * 40503u; g ^= g >> 15; g *= 2246822519u; g ^= g >> 13; Vddmu_b[i] = 0.3 * ((double)(g & 0xffff) / 65536.0 - 0.5) / n; } }
+    else if (i < nb + nu) { const size_t e = (i - nb) % ((size_t)n * n); const int r = (int)(e / n), c = (int)(e % n); Vddmu_u[i - nb] = r == c ? 3.0 + 0.1 * v : 0.0; }
+    else if (i < nb + nu + gb) Vdmu_b[i - nb - nu] = v;
+    else Vdmu_u[i - nb - nu - gb] = v;
+  }
 }
 
 // CHAIN_MERGE=1: the top pass and the first backward pass in one launch (chain_launch.hpp::ChainSync)
@@ -197,6 +217,74 @@ static int run(int T, int n, int reps) {
     printf("\n");
   }
 #endif
+  // ---- assemble-on-load leg (ASM_LEG=0 skips it) ----
+  const char* leg_env = getenv("ASM_LEG");
+  const bool asm_leg = T > 1 && !(leg_env && atoi(leg_env) == 0);
+  double *dVb = nullptr, *dGb = nullptr, *dVu = nullptr, *dGu = nullptr, *dMix = nullptr, *dAsm = nullptr;
+  ChainArgs b0 = a0, b1 = a1;
+  AsmList AL{};
+  unsigned salt = 1;
+  if (asm_leg) {
+    const int d = 2 * n;
+    CK(hipMalloc(&dVb, (size_t)(T - 1) * d * d * 8)); CK(hipMalloc(&dGb, (size_t)(T - 1) * d * 8));
+    CK(hipMalloc(&dVu, (size_t)T * nn * 8)); CK(hipMalloc(&dGu, (size_t)T * n * 8));
+    CK(hipMalloc(&dMix, (btD + btU + 1) * 8)); CK(hipMalloc(&dAsm, ((size_t)T * n + btD + btU + 1) * 8));
+    AL.nsets = 2;
+    AL.s[0].K = T - 1; AL.s[0].d = d; AL.s[0].Vdmu = dGb; AL.s[0].Vddmu = dVb; AL.s[0].nsp = 0;
+    AL.s[1].K = T; AL.s[1].d = n; AL.s[1].Vdmu = dGu; AL.s[1].Vddmu = dVu; AL.s[1].nsp = 0;
+    // as in the iteration: the factorisation takes D + step (V - D) with V assembled, the solve operates on V and g
+    b0.asm_on = 1; b0.mixV = nullptr; b0.mixOut = dMix; b0.mix_step = 0.55;
+    b1.asm_on = 1; b1.asmG = dAsm; b1.asmD = dAsm + (size_t)T * n; b1.asmU = b1.asmD + btD; b1.D = nullptr; b1.U = nullptr; b1.rhs = drhs;
+    auto fill = [&]() { hipLaunchKernelGGL(asm_fill_kernel, dim3(256), dim3(256), 0, st, dGb, dVb, dGu, dVu, T, n, salt++); };
+    // dense path against the generic set loop, same inputs: every output bit for bit
+    const size_t nout = btD + btU + (size_t)T * n + 1 + (btD + btU) + ((size_t)T * n + btD + btU);
+    std::vector<double> R[2];
+    for (int leg = 0; leg < 2; ++leg) {
+      chain_asm_dense_enabled() = leg == 0;
+      clear_out();
+      CK(hipMemsetAsync(dMix, 0xff, (btD + btU) * 8, st)); CK(hipMemsetAsync(dAsm, 0xff, ((size_t)T * n + btD + btU) * 8, st));
+      salt = 77;
+      fill();
+      CK(chain_launch(n, pl, b0, b1, true, true, st, &AL, next_sync()));
+      CK(hipStreamSynchronize(st));
+      R[leg].resize(nout);
+      double* o = R[leg].data();
+      CK(hipMemcpy(o, dSig, (btD + btU) * 8, hipMemcpyDeviceToHost)); o += btD + btU;
+      CK(hipMemcpy(o, dx_, (size_t)T * n * 8, hipMemcpyDeviceToHost)); o += (size_t)T * n;
+      CK(hipMemcpy(o, dhld, 8, hipMemcpyDeviceToHost)); o += 1;
+      CK(hipMemcpy(o, dMix, (btD + btU) * 8, hipMemcpyDeviceToHost)); o += btD + btU;
+      CK(hipMemcpy(o, dAsm, ((size_t)T * n + btD + btU) * 8, hipMemcpyDeviceToHost));
+    }
+    chain_asm_dense_enabled() = true;
+    size_t diff = 0, nan = 0;
+    for (size_t i = 0; i < nout; ++i) { diff += memcmp(&R[0][i], &R[1][i], 8) != 0; nan += R[0][i] != R[0][i]; }
+    printf("assemble-on-load: dense vs generic differing words: %zu of %zu (NaN: %zu)\n", diff, nout, nan);
+    fail |= diff != 0 || nan != 0;
+  }
+#ifdef GVI_CHAIN_TIMING
+  if (asm_leg) {
+    // the same stamps with the assemble-on-load in the first pass, its inputs freshly written; then with the generic set loop
+    for (int leg = 0; leg < 2; ++leg) {
+      chain_asm_dense_enabled() = leg == 0;
+      for (int rep = 0; rep < 3; ++rep) {
+        int zero = 0;
+        hipLaunchKernelGGL(asm_fill_kernel, dim3(256), dim3(256), 0, st, dGb, dVb, dGu, dVu, T, n, salt++);
+        CK(hipStreamSynchronize(st));
+        CK(hipMemcpyToSymbol(HIP_SYMBOL(gvi_chain_nstamp), &zero, sizeof(int)));
+        CK(chain_launch(n, pl, b0, b1, true, true, st, &AL, next_sync()));
+        CK(hipStreamSynchronize(st));
+        int ns = 0;
+        std::vector<unsigned long long> stp(256);
+        CK(hipMemcpyFromSymbol(&ns, HIP_SYMBOL(gvi_chain_nstamp), sizeof(int)));
+        CK(hipMemcpyFromSymbol(stp.data(), HIP_SYMBOL(gvi_chain_stamps), 256 * sizeof(unsigned long long)));
+        printf("asm-on-load %s stamps (%d), cycles between:", leg == 0 ? "dense  " : "generic", ns);
+        for (int i = 1; i < ns && i < 12; ++i) printf(" %llu", stp[i] - stp[i - 1]);
+        printf("\n");
+      }
+    }
+    chain_asm_dense_enabled() = true;
+  }
+#endif
   // timing
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
@@ -214,6 +302,20 @@ static int run(int T, int n, int reps) {
   time_it("factor || solve", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
   time_it("factor only", [&]() { CK(chain_launch(n, pl, a0, a1, true, false, st, nullptr, next_sync())); });
   time_it("solve only", [&]() { CK(chain_launch(n, pl, a0, a1, false, true, st, nullptr, next_sync())); });
+  if (asm_leg) {
+    auto call = [&]() {
+      hipLaunchKernelGGL(asm_fill_kernel, dim3(256), dim3(256), 0, st, dGb, dVb, dGu, dVu, T, n, salt++);
+      CK(chain_launch(n, pl, b0, b1, true, true, st, &AL, next_sync()));
+    };
+    time_it("fill only", [&]() { hipLaunchKernelGGL(asm_fill_kernel, dim3(256), dim3(256), 0, st, dGb, dVb, dGu, dVu, T, n, salt++); });
+    for (int rep = 0; rep < 2; ++rep) {              // interleaved: dense, generic, dense, generic
+      chain_asm_dense_enabled() = true;
+      time_it("fill + asm-on-load dense", call);
+      chain_asm_dense_enabled() = false;
+      time_it("fill + asm-on-load generic", call);
+    }
+    chain_asm_dense_enabled() = true;
+  }
   {
     // the same launches with a predicate that does not hold: every block returns at its first instruction -- what the launch
     // configuration itself costs (dispatch of 2 x 33 workgroups of 16 waves with ~100 KB of LDS each, kernel arguments, drain)
