@@ -87,6 +87,15 @@ def dist_unique_id() -> bytes:
     return buf.raw
 
 
+def asm_launches():
+    """(dense, generic): chain launches of this process that assembled (g, V) while loading, by the load path they were
+    classified for (gvi_debug_asm_launches)."""
+    lib = _lib.load()
+    a, b = C.c_int64(), C.c_int64()
+    _ck_global(lib, lib.gvi_debug_asm_launches(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
 class Context:
     def __init__(self, device: int = 0, dtype: int = GVI_F64):
         self.lib = _lib.load()

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 #include "kernels_chain.hpp"
@@ -152,6 +153,10 @@ inline bool chain_wave_applies(int T, int n) { return chain_wave_enabled() && n 
 // kernels_chain.hpp AsmDense: GVI_ASM_DENSE=0, option "asm_dense")
 inline bool& chain_asm_dense_enabled() { static bool on = true; return on; }
 
+// How chain_launch classified the launches that carried an assemble list, per process: [0] the batched load path (ASM_DENSE),
+// [1] the generic set loop.  Read-only bookkeeping for the tests (gvi_debug_asm_launches); no kernel sees it.
+inline std::atomic<long long>* chain_asm_launches() { static std::atomic<long long> c[2]; return c; }
+
 // n: the caller's block size (a0.n / a1.n are set here).  AL: the factor sets of an assemble-on-load (a0.asm_on / a1.asm_on), else null
 inline hipError_t chain_launch(int n, const ChainPlan& pl, ChainArgs a0, ChainArgs a1, bool on0, bool on1, hipStream_t st,
                                const AsmList* AL = nullptr, const ChainSync& sync = ChainSync{}) {
@@ -162,7 +167,8 @@ inline hipError_t chain_launch(int n, const ChainPlan& pl, ChainArgs a0, ChainAr
   else if (chain_asm_dense_enabled() && chain_asm_dense(L, n) && (on0 ? a0.T : a1.T) > 1) {     // the first pass's batched load path (kernels_chain.hpp, AsmDense)
     if (a0.asm_on) a0.asm_on = ASM_DENSE;
     if (a1.asm_on) a1.asm_on = ASM_DENSE;
-  }
+    ++chain_asm_launches()[0];
+  } else ++chain_asm_launches()[1];
   if (chain_wave_applies(on0 ? a0.T : a1.T, n)) {
     const int nb0 = on0 ? 1 : 0, nb = nb0 + (on1 ? 1 : 0);
     if (nb == 0) return hipSuccess;

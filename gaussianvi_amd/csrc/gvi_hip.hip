@@ -3349,6 +3349,12 @@ gvi_status gvi_ngd_counters(gvi_ctx* ctx, int64_t* full_passes, int64_t* cost_pa
   return GVI_OK;
 }
 
+gvi_status gvi_debug_asm_launches(int64_t* dense, int64_t* generic) {
+  if (dense) *dense = chain_asm_launches()[0].load();
+  if (generic) *generic = chain_asm_launches()[1].load();
+  return GVI_OK;
+}
+
 gvi_status gvi_ngd_exchange(gvi_ctx* ctx, int which, void** dev_ptr, int64_t* count) {
   GVICK(ngd_check(ctx));
   if (!dev_ptr || !count) return fail(ctx, GVI_ERR_ARG, "NULL argument");

@@ -347,6 +347,10 @@ gvi_status gvi_profile_geometry(gvi_ctx* ctx, int set_id, int* variant, int* nch
  * on the DEVICE; entries == 0 with out != NULL copies that ring after a stream sync; entries < 0 stops recording.  *seq_now =
  * sequence number of the last publish issued. */
 gvi_status gvi_debug_cost_log(gvi_ctx* ctx, int entries, double* out, double* seq_now);
+/* Test hook of the assemble-on-load (options "assemble_on_load" / "asm_dense"): how many chain launches that assembled (g, V)
+ * while loading took the batched load path (dense) and how many the generic loop over the sets, in this PROCESS since the
+ * library was loaded.  Read-only, either pointer may be NULL; a launch without an assemble counts in neither. */
+gvi_status gvi_debug_asm_launches(int64_t* dense, int64_t* generic);
 /* Kernel variant override for A/B runs: 0 = auto (sum-of-squares sets with m = 6 / 12 on a table that decomposes into sign
  * orbits take the sign-orbit kernel; otherwise 5 / 2 / 1 as instantiated), 1 = generic LDS kernel, 2 = register kernel
  * (psi operands in LDS), 5 = register kernel with psi operands in SGPRs, 6 = sign-orbit kernel where supported, 7 = auto, with

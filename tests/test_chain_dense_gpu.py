@@ -9,7 +9,9 @@ from another state, so nothing a run reads can be left over from the run it is c
 
 Chains: c3small (33 states: one launch, the TOP instance), c3mini (9 states), c3t75 (75 states: a segmented first pass whose
 last workgroup holds 11 of 32 nodes -- T - 1 = 74 is not a multiple of 32 -- and the merged top + backward launch) and planar
-(sparse anchor sets: the generic loop stays in charge)."""
+(sparse anchor sets: the generic loop stays in charge).  api.asm_launches() says which of the two a run's launches were
+classified for: the batched path on the three LTV chains, the generic loop on planar and under asm_dense 0, neither where the
+assemble is a launch of its own."""
 import os
 
 import numpy as np
@@ -25,6 +27,7 @@ pytestmark = pytest.mark.gpu
 syn.CONFIGS.setdefault("c3t75", (39, 75, 6, 5, "ltv"))
 STEPS = 6
 DENSE_DEFAULT = int(os.environ.get("GVI_ASM_DENSE", "1") != "0")     # the process-wide switch as the library read it
+ON_LOAD_DEFAULT = int(os.environ.get("GVI_ASM_ON_LOAD", "1") != "0")  # (per context, read at its creation)
 
 
 def _run(ch, seed, options):
@@ -37,11 +40,21 @@ def _run(ch, seed, options):
         ctx.ngd_init(ch["mu0"], ch["D0"], ch["U0"])
         ctx.ngd_step(0.55, 10)
         ctx.ngd_init(muB, DB, UB)
+        before = api.asm_launches()
         results = [ctx.ngd_step(0.55, 10) for _ in range(STEPS)]
         state = ctx.ngd_get_state()
+        after = api.asm_launches()
     finally:
         ctx.set_option("asm_dense", DENSE_DEFAULT)  # (process-wide switch)
         ctx.close()
+    # the launches that assembled while loading: all on the batched path, all on the generic loop, or none at all
+    dense, generic = after[0] - before[0], after[1] - before[1]
+    if not options.get("assemble_on_load", ON_LOAD_DEFAULT):
+        assert (dense, generic) == (0, 0), (options, dense, generic)
+    elif ch["name"] != "planar" and options.get("asm_dense", DENSE_DEFAULT):
+        assert dense >= 1 and generic == 0, (options, dense, generic)
+    else:
+        assert dense == 0 and generic >= 1, (options, dense, generic)
     return results, state
 
 
