@@ -96,6 +96,15 @@ def asm_launches():
     return a.value, b.value
 
 
+def fused_launches():
+    """Launches of the one-launch factor pass by this process, per instantiation: (<6,4,4,12,6>, <6,6,2,12,6>, <2,4,4,4,2>)
+    (gvi_debug_fused_launches)."""
+    lib = _lib.load()
+    c = (C.c_int64 * 3)()
+    _ck_global(lib, lib.gvi_debug_fused_launches(c))
+    return tuple(int(v) for v in c)
+
+
 class Context:
     def __init__(self, device: int = 0, dtype: int = GVI_F64):
         self.lib = _lib.load()

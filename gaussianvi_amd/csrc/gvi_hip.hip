@@ -634,7 +634,7 @@ bool orbit_supported(const gvi_ctx* c, const FactorSet& s) {
   if (!c->orbit || !(c->variant == 0 || c->variant == 6)) return false;
   if (s.kind != KIND_QUAD_PRIOR && s.kind != KIND_FIXED_PRIOR) return false;
   if (!(s.m == 2 || s.m == 6 || s.m == 12 || (s.m == 14 && s.table->orb.smax <= 4)) || s.d > 32) return false;   // m = 14: the d = 28 priors of the arm graph
-  if (s.m == 2 && s.table->orb.smax > 4) return false;          // m = 2 is instantiated for degree <= 5 only
+  if (s.m == 2 && s.table->orb.smax > 4) return false;          // m = 2 is instantiated for supports <= 4: every table of d <= 4, wider ones to degree 5
   const OrbitHost& o = s.table->orb;
   return o.ok && o.smax >= 1 && o.smax <= ORBIT_SMAX && !o.tile_s.empty();
 }
@@ -734,6 +734,10 @@ void launch_orbit_pair(const OrbitArgs& a0, const OrbitArgs& a1, int m, int smax
   else launch_orbit_pair_t<12, 6, 2>(a0, a1, full, lds, st, e0, e1, stack);
 }
 
+// Launches of factor_fused_kernel in this process, per instantiation: [0] <6,4,4,12,6>, [1] <6,6,2,12,6>, [2] <2,4,4,4,2>.
+// Read-only bookkeeping for the tests (gvi_debug_fused_launches); no kernel sees it.
+inline std::atomic<long long>* fused_launches() { static std::atomic<long long> c[3]; return c; }
+
 // the full pass of the resident iteration as one launch (kernels_fused.hpp)
 template <int M, int SMAX, int WAVES, int D0, int D1>
 gvi_status launch_fused_t(gvi_ctx* c, const FusedArgs& A, unsigned grid, size_t lds, int dmax, int copies, int items, hipEvent_t e0, hipEvent_t e1) {
@@ -749,6 +753,7 @@ gvi_status launch_fused_t(gvi_ctx* c, const FusedArgs& A, unsigned grid, size_t 
 #endif
   hipExtLaunchKernelGGL((factor_fused_kernel<M, SMAX, WAVES, D0, D1>), dim3(grid), dim3(256), (uint32_t)lds, c->stream, e0, e1, 0, A, dmax, copies, items,
                         (dbg & 8) ? stamps : (unsigned long long*)nullptr);
+  ++fused_launches()[M == 2 ? 2 : (SMAX <= 4 ? 0 : 1)];
 #ifdef GVI_FUSED_TIMING
   if ((dbg & 8) && stamps && ++nprint > 200 && nprint <= 202) {          // a few warm launches, 100 MHz ticks
     unsigned long long h[1120];
@@ -3352,6 +3357,12 @@ gvi_status gvi_ngd_counters(gvi_ctx* ctx, int64_t* full_passes, int64_t* cost_pa
 gvi_status gvi_debug_asm_launches(int64_t* dense, int64_t* generic) {
   if (dense) *dense = chain_asm_launches()[0].load();
   if (generic) *generic = chain_asm_launches()[1].load();
+  return GVI_OK;
+}
+
+gvi_status gvi_debug_fused_launches(int64_t counts[3]) {
+  if (!counts) return fail(nullptr, GVI_ERR_ARG, "NULL");
+  for (int i = 0; i < 3; ++i) counts[i] = fused_launches()[i].load();
   return GVI_OK;
 }
 

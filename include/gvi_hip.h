@@ -351,6 +351,11 @@ gvi_status gvi_debug_cost_log(gvi_ctx* ctx, int entries, double* out, double* se
  * while loading took the batched load path (dense) and how many the generic loop over the sets, in this PROCESS since the
  * library was loaded.  Read-only, either pointer may be NULL; a launch without an assemble counts in neither. */
 gvi_status gvi_debug_asm_launches(int64_t* dense, int64_t* generic);
+/* Test hook of the one-launch factor pass (option "fused"): how many launches of it this PROCESS has issued since the library
+ * was loaded, per compiled instantiation <m, smax, waves, d0, d1>: counts[0] <6,4,4,12,6> (n = 6, GH degree <= 5), counts[1]
+ * <6,6,2,12,6> (n = 6, degree 6 / 7), counts[2] <2,4,4,4,2> (n = 2).  Read-only; a pass that took the three-launch route
+ * counts nowhere. */
+gvi_status gvi_debug_fused_launches(int64_t counts[3]);
 /* Kernel variant override for A/B runs: 0 = auto (sum-of-squares sets with m = 6 / 12 on a table that decomposes into sign
  * orbits take the sign-orbit kernel; otherwise 5 / 2 / 1 as instantiated), 1 = generic LDS kernel, 2 = register kernel
  * (psi operands in LDS), 5 = register kernel with psi operands in SGPRs, 6 = sign-orbit kernel where supported, 7 = auto, with
