@@ -94,6 +94,10 @@ SIGNATURES = {
     "gvi_ngd_sample": [C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_void_p],
     "gvi_ngd_sample_dev": [C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_void_p],
     "gvi_bt_logpdf": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_bt_solve_multi": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_bt_cov_columns": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_ngd_cov_columns": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_ngd_cov_columns_dev": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gvi_profile_enable": [C.c_void_p, C.c_int],
     "gvi_profile_last": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)],
     "gvi_profile_geometry": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)],

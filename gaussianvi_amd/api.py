@@ -398,6 +398,38 @@ class Context:
         self._ck(self.lib.gvi_bt_logpdf(self.h, _p(D), _p(U), _p(mu), S, _p(X), _p(out)))
         return out
 
+    # ---- many right-hand sides and block columns of Lambda^-1 (Lambda positive definite) ----
+    def bt_solve_multi(self, D, U, B):
+        """X [R][T][n] with X_r = (D, U)^-1 B_r for B [R][T][n]: one factorisation for the whole batch."""
+        D, U, B = _f64(D), _f64(U), _f64(B)
+        assert B.size % (self.T * self.n) == 0, "B must hold R * T * n numbers"
+        R = B.size // (self.T * self.n)
+        X = np.empty((R, self.T, self.n))
+        self._ck(self.lib.gvi_bt_solve_multi(self.h, _p(D), _p(U), R, _p(B), _p(X)))
+        return X
+
+    def _nodes(self, nodes):
+        return np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
+
+    def bt_cov_columns(self, D, U, nodes):
+        """C [ncols][T][n][n]: C[c][t] = block (t, nodes[c]) of (D, U)^-1."""
+        D, U, nodes = _f64(D), _f64(U), self._nodes(nodes)
+        Cc = np.empty((nodes.size, self.T, self.n, self.n))
+        self._ck(self.lib.gvi_bt_cov_columns(self.h, _p(D), _p(U), nodes.size, _p(nodes), _p(Cc)))
+        return Cc
+
+    def ngd_cov_columns(self, nodes):
+        """bt_cov_columns of the resident precision (the state stays on the device)."""
+        nodes = self._nodes(nodes)
+        Cc = np.empty((nodes.size, self.T, self.n, self.n))
+        self._ck(self.lib.gvi_ngd_cov_columns(self.h, nodes.size, _p(nodes), _p(Cc)))
+        return Cc
+
+    def ngd_cov_columns_dev(self, nodes, ptr):
+        """Into device memory at ptr (ncols * T * n * n doubles), asynchronous on the context stream."""
+        nodes = self._nodes(nodes)
+        self._ck(self.lib.gvi_ngd_cov_columns_dev(self.h, nodes.size, _p(nodes), C.c_void_p(ptr)))
+
     # ---- measurement ----
     def profile_enable(self, on=True):
         self._ck(self.lib.gvi_profile_enable(self.h, int(on)))

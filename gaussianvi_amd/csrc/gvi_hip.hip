@@ -28,6 +28,7 @@
 #include "kernels_block.hpp"
 #include "kernels_orbit_psi.hpp"
 #include "kernels_sample.hpp"
+#include "kernels_solve.hpp"
 #include "orbits.hpp"
 #include "spgh.hpp"
 
@@ -292,7 +293,11 @@ struct gvi_ctx {
   // samplers / log-density (kernels_sample.hpp): workspaces of their own, so that a call between NGD steps touches nothing
   // the iteration reads or writes
   DevMem smp_ws, smp_io, smp_cws, smp_cwsi;
-  bool sample_sweep = true;           // option "sample_sweep" = 0: the samplers run the factorisation only (tools/sample_bench.py)
+  bool sample_sweep = true;           // option "sample_sweep" = 0: the samplers and the multi-solve run the factorisation only (tools/*_bench.py)
+  // multi-right-hand-side solve / covariance columns (kernels_solve.hpp): the sampler's factor workspace (smp_ws) and staging
+  // (smp_io), plus the node list of the columns
+  DevMem slv_idx;
+  bool solve_lds = true;              // option "solve_lds" = 0: the sweep keeps its vectors in the output buffer whatever the size
 };
 
 namespace {
@@ -3489,6 +3494,7 @@ gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value) {
   else if (n == "chain_wave") chain_wave_enabled() = value != 0;
   else if (n == "asm_dense") chain_asm_dense_enabled() = value != 0;
   else if (n == "sample_sweep") ctx->sample_sweep = value != 0;
+  else if (n == "solve_lds") ctx->solve_lds = value != 0;
   else if (n == "chain_merge") { ctx->chain_merge = value != 0; ctx->chain_merge_fault = value == 2; }
   else if (n == "trust_table_degree") ctx->trust_table_degree = value != 0;
   else if (n == "safe_publish") {
@@ -3557,17 +3563,14 @@ static gvi_status sample_check(gvi_ctx* ctx, int S) {
   return GVI_OK;
 }
 
-// Factorisation (every node's R, GA, GB) and sweep of S samples into the device buffer X, all on the context stream.
-// Chain arguments of its own: no fused trial precision, no accept predicate, no selected inverse.
-static gvi_status run_sample(gvi_ctx* c, const double* D, const double* U, const double* mu, int S, uint64_t seed, int64_t first,
-                             const double* eps, double* X) {
-  if (c->n > SAMPLE_NMAX) return fail(c, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  if (S == 0) return GVI_OK;
+// Factorisation of Lambda = (D, U) on the context stream: every node's R, GA, GB and the half log-det, left in smp_ws
+// (fa says where).  One launch of sample_factor_kernel per level.  Shared by the samplers and the multi-solve.
+static gvi_status run_sample_factor(gvi_ctx* c, const double* D, const double* U, SampleFactorArgs& fa) {
   const int T = c->T, n = c->n, L = chain_levels(T);
   const size_t nn = nn_(c), Tnn = (size_t)T * nn;
   HIPCK(c, c->smp_ws.ensure((7 * Tnn + T + 1) * 8));
   double* w = c->smp_ws.d();
-  SampleFactorArgs fa{};
+  fa = SampleFactorArgs{};
   fa.T = T; fa.n = n; fa.L = L; fa.D = D; fa.U = U;
   double* Db[2] = {w, w + Tnn};
   double* Cb[2] = {w + 2 * Tnn, w + 3 * Tnn};
@@ -3580,6 +3583,18 @@ static gvi_status run_sample(gvi_ctx* c, const double* D, const double* U, const
     hipLaunchKernelGGL(sample_factor_kernel, dim3(alive), dim3(64), 0, c->stream, fa);
   }
   HIPCK(c, hipGetLastError());
+  return GVI_OK;
+}
+
+// Factorisation and sweep of S samples into the device buffer X, all on the context stream.
+// Chain arguments of its own: no fused trial precision, no accept predicate, no selected inverse.
+static gvi_status run_sample(gvi_ctx* c, const double* D, const double* U, const double* mu, int S, uint64_t seed, int64_t first,
+                             const double* eps, double* X) {
+  if (c->n > SAMPLE_NMAX) return fail(c, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  if (S == 0) return GVI_OK;
+  const int T = c->T, n = c->n, L = chain_levels(T);
+  SampleFactorArgs fa;
+  GVICK(run_sample_factor(c, D, U, fa));
   if (!c->sample_sweep) return GVI_OK;
   SampleSweepArgs sa{};
   sa.T = T; sa.n = n; sa.L = L; sa.S = S; sa.seed = seed; sa.first = first; sa.eps = eps;
@@ -3708,6 +3723,131 @@ gvi_status gvi_bt_logpdf(gvi_ctx* ctx, const double* D, const double* U, const d
   HIPCK(ctx, hipGetLastError());
   GVICK(d2h(ctx, logq, dl, (size_t)S * 8));
   return sync(ctx);
+}
+
+
+// ---- multi-right-hand-side solve and block columns of Lambda^-1 (kernels_solve.hpp) ----
+static gvi_status solve_check(gvi_ctx* ctx, int count, const char* what) {
+  if (!ctx) return GVI_ERR_ARG;
+  if (count < 0) return fail(ctx, GVI_ERR_ARG, std::string(what) + " < 0");
+  if (ctx->T < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_chain_set first");
+  return GVI_OK;
+}
+
+static gvi_status solve_check_nodes(gvi_ctx* ctx, int ncols, const int32_t* nodes) {
+  for (int c = 0; c < ncols; ++c)
+    if (nodes[c] < 0 || nodes[c] >= ctx->T) return fail(ctx, GVI_ERR_ARG, "node outside [0, T)");
+  if ((int64_t)ncols * ctx->n > INT32_MAX) return fail(ctx, GVI_ERR_ARG, "ncols * state_dim exceeds 2^31 - 1");
+  return GVI_OK;
+}
+
+// Factorisation (run_sample_factor) and sweep of R right-hand sides into the device buffer X, all on the context stream.
+// B ([R][T][n], device) or, with B null, the unit columns of the device node list (R = ncols n, X = C[ncols][T][n][n]).
+// Like run_sample it builds no ChainArgs.
+static gvi_status run_solve(gvi_ctx* c, const double* D, const double* U, int R, const double* B, const int32_t* nodes, double* X) {
+  if (c->n > SOLVE_NMAX) return fail(c, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  if (R == 0) return GVI_OK;
+  const int T = c->T, n = c->n;
+  SampleFactorArgs fa;
+  GVICK(run_sample_factor(c, D, U, fa));
+  if (!c->sample_sweep) return GVI_OK;
+  SolveSweepArgs sa{};
+  sa.T = T; sa.n = n; sa.L = fa.L; sa.R = R; sa.B = B; sa.nodes = nodes;
+  sa.Rf = fa.R; sa.GA = fa.GA; sa.GB = fa.GB; sa.hld = fa.hld; sa.X = X;
+  const size_t rowb = (size_t)T * n * 8;
+  const bool lds = c->solve_lds && rowb <= (size_t)SOLVE_LDS_BYTES;
+  const int cap = lds ? std::min<int>(SOLVE_TILE_MAX, (int)(SOLVE_LDS_BYTES / rowb)) : SOLVE_TILE_MAX;
+  sa.tile = std::max(1, std::min(cap, (R + 511) / 512));     // >= 512 workgroups while R allows, then longer tiles
+  const dim3 grid((unsigned)((R + sa.tile - 1) / sa.tile)), blk(SOLVE_SWEEP_THREADS);
+  const size_t ldsb = lds ? (size_t)sa.tile * rowb : 0;
+  auto go = [&](auto kern) -> gvi_status {
+    if (lds) GVICK(allow_lds(c, (const void*)kern, SOLVE_LDS_BYTES));
+    hipLaunchKernelGGL(kern, grid, blk, ldsb, c->stream, sa);
+    HIPCK(c, hipGetLastError());
+    return GVI_OK;
+  };
+  if (n <= 4) return lds ? go(solve_sweep_kernel<4, true>) : go(solve_sweep_kernel<4, false>);
+  if (n <= 8) return lds ? go(solve_sweep_kernel<8, true>) : go(solve_sweep_kernel<8, false>);
+  return lds ? go(solve_sweep_kernel<16, true>) : go(solve_sweep_kernel<16, false>);
+}
+
+gvi_status gvi_bt_solve_multi(gvi_ctx* ctx, const double* D, const double* U, int R, const double* B, double* X) {
+  GVICK(solve_check(ctx, R, "R"));
+  if (!D || (!U && ctx->T > 1) || !B || !X) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (ctx->n > SOLVE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  if (R == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t T = ctx->T, nn = nn_(ctx), RX = (size_t)R * T * ctx->n;
+  HIPCK(ctx, ctx->smp_io.ensure((bt_count(ctx) + 2 * RX) * 8));
+  double* dD = ctx->smp_io.d();
+  double* dU = dD + T * nn;
+  double* dB = dU + (T - 1) * nn;
+  double* dX = dB + RX;
+  GVICK(h2d(ctx, dD, D, T * nn * 8));
+  if (T > 1) GVICK(h2d(ctx, dU, U, (T - 1) * nn * 8));
+  GVICK(h2d(ctx, dB, B, RX * 8));
+  GVICK(run_solve(ctx, dD, dU, R, dB, nullptr, dX));
+  GVICK(d2h(ctx, X, dX, RX * 8));
+  return sync(ctx);
+}
+
+// node list to the device (slv_idx), on the context stream
+static gvi_status solve_put_nodes(gvi_ctx* ctx, int ncols, const int32_t* nodes) {
+  HIPCK(ctx, ctx->slv_idx.ensure((size_t)ncols * sizeof(int32_t)));
+  return h2d(ctx, ctx->slv_idx.p, nodes, (size_t)ncols * sizeof(int32_t));
+}
+
+gvi_status gvi_bt_cov_columns(gvi_ctx* ctx, const double* D, const double* U, int ncols, const int32_t* nodes, double* C) {
+  GVICK(solve_check(ctx, ncols, "ncols"));
+  if (!D || (!U && ctx->T > 1) || !nodes || !C) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (ctx->n > SOLVE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  GVICK(solve_check_nodes(ctx, ncols, nodes));
+  if (ncols == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t T = ctx->T, nn = nn_(ctx), CX = (size_t)ncols * T * nn;
+  HIPCK(ctx, ctx->smp_io.ensure((bt_count(ctx) + CX) * 8));
+  double* dD = ctx->smp_io.d();
+  double* dU = dD + T * nn;
+  double* dC = dU + (T - 1) * nn;
+  GVICK(h2d(ctx, dD, D, T * nn * 8));
+  if (T > 1) GVICK(h2d(ctx, dU, U, (T - 1) * nn * 8));
+  GVICK(solve_put_nodes(ctx, ncols, nodes));
+  GVICK(run_solve(ctx, dD, dU, ncols * ctx->n, nullptr, (const int32_t*)ctx->slv_idx.p, dC));
+  GVICK(d2h(ctx, C, dC, CX * 8));
+  return sync(ctx);
+}
+
+static gvi_status ngd_cov_columns_to(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C_dev) {
+  NgdState& g = ctx->ngd;
+  const size_t Tnn = (size_t)ctx->T * nn_(ctx);
+  GVICK(solve_put_nodes(ctx, ncols, nodes));
+  return run_solve(ctx, g.Lam[g.cur].d(), g.Lam[g.cur].d() + Tnn, ncols * ctx->n, nullptr, (const int32_t*)ctx->slv_idx.p, C_dev);
+}
+
+gvi_status gvi_ngd_cov_columns(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C) {
+  GVICK(solve_check(ctx, ncols, "ncols"));
+  if (!nodes || !C) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  GVICK(ngd_check(ctx));
+  if (ctx->n > SOLVE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  GVICK(solve_check_nodes(ctx, ncols, nodes));
+  if (ncols == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t CX = (size_t)ncols * ctx->T * nn_(ctx);
+  HIPCK(ctx, ctx->smp_io.ensure(CX * 8));
+  GVICK(ngd_cov_columns_to(ctx, ncols, nodes, ctx->smp_io.d()));
+  GVICK(d2h(ctx, C, ctx->smp_io.p, CX * 8));
+  return sync(ctx);
+}
+
+gvi_status gvi_ngd_cov_columns_dev(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C_dev) {
+  GVICK(solve_check(ctx, ncols, "ncols"));
+  if (!nodes || !C_dev) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  GVICK(ngd_check(ctx));
+  if (ctx->n > SOLVE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  GVICK(solve_check_nodes(ctx, ncols, nodes));
+  if (ncols == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  return ngd_cov_columns_to(ctx, ncols, nodes, C_dev);
 }
 
 }  // extern "C"

@@ -1411,6 +1411,49 @@ class GVIGH {
     return out;
   }
 
+  // precision()^-1 B, the columns of B being the right-hand sides: ONE factorisation for all of them (gvi_bt_solve_multi on
+  // the host blocks, which both execution modes keep current).  No reference counterpart (gvi_hip.h, "many right-hand sides").
+  MatrixXd solve(const MatrixXd& B) {
+    if (B.rows() != _dim) throw GviError(GVI_ERR_ARG, "solve: B must have mean().size() rows");
+    const int R = B.cols();
+    if (R == 0) return MatrixXd(_dim, 0);
+    std::vector<double> Br((size_t)R * _dim), Xr((size_t)R * _dim);
+    for (int j = 0; j < R; ++j)
+      for (int i = 0; i < _dim; ++i) Br[(size_t)j * _dim + i] = B(i, j);
+    _dev->check(gvi_bt_solve_multi(_dev->get(), _D.data(), _U.data(), R, Br.data(), Xr.data()));
+    MatrixXd M(_dim, R);
+    for (int j = 0; j < R; ++j)
+      for (int i = 0; i < _dim; ++i) M(i, j) = Xr[(size_t)j * _dim + i];
+    return M;
+  }
+  // The block columns of the joint covariance precision()^-1 that belong to `states` (duplicates allowed): T n x ncols n,
+  // column c n + k = column (states[c], k) of the covariance, so rows t n .. t n + n - 1 of block column c are cov(x_t, x_states[c]).
+  // DeviceResident: from the resident precision (gvi_ngd_cov_columns); FactorWise: from the host blocks (gvi_bt_cov_columns);
+  // the same numbers for both paths.  Beyond the tridiagonal pattern that covariance() / inverse() fill.
+  MatrixXd covariance_columns(const std::vector<int>& states) {
+    const int T = _num_states, n = _dim_state, nc = (int)states.size();
+    if (nc == 0) return MatrixXd(T * n, 0);
+    std::vector<int32_t> nodes(states.begin(), states.end());
+    std::vector<double> Cc((size_t)nc * T * n * n);
+    if (_exec == Execution::DeviceResident) {
+      sync_resident();
+      _dev->check(gvi_ngd_cov_columns(_dev->get(), nc, nodes.data(), Cc.data()));
+    } else {
+      _dev->check(gvi_bt_cov_columns(_dev->get(), _D.data(), _U.data(), nc, nodes.data(), Cc.data()));
+    }
+    MatrixXd M(T * n, nc * n);
+    for (int c = 0; c < nc; ++c)
+      for (int t = 0; t < T; ++t)
+        for (int r = 0; r < n; ++r)
+          for (int k = 0; k < n; ++k) M(t * n + r, c * n + k) = Cc[(((size_t)c * T + t) * n + r) * n + k];
+    return M;
+  }
+  // cov(x_i, x_j), n x n, for any pair of states
+  MatrixXd cross_covariance(int i, int j) {
+    if (i < 0 || i >= _num_states) throw GviError(GVI_ERR_ARG, "cross_covariance: state outside [0, num_states)");
+    return covariance_columns(std::vector<int>{j}).block(i * _dim_state, 0, _dim_state, _dim_state);
+  }
+
   // inverse(mat) (gvibase/GVI-GH.h:161-165): the block-tridiagonal part of mat^-1 (EigenWrapper::inv_sparse /
   // inverse_GBP), computed by the device's selected inverse
   inline SpMat inverse(const SpMat& mat) {

@@ -327,6 +327,29 @@ gvi_status gvi_ngd_sample_dev(gvi_ctx* ctx, int S, uint64_t seed, int64_t first,
 gvi_status gvi_bt_logpdf(gvi_ctx* ctx, const double* D, const double* U, const double* mu, int S, const double* X,
                          double* logq);
 
+/* ---- many right-hand sides and block columns of Lambda^-1, Lambda = (D, U) symmetric POSITIVE DEFINITE block-tridiagonal
+ *      (no reference counterpart: the reference solves one system by ConjugateGradient, ngd/NGD-GH-impl.h:59-60, and its
+ *      inverse_GBP / EigenWrapper::inv_sparse fill the tridiagonal pattern of the inverse only,
+ *      gvibase/GVI-GH-GBP-impl.h:246-305, helpers/EigenWrapper.h:282-381 -- the closest lines for all four entry points).
+ *      One factorisation (the samplers' block cyclic reduction, Cholesky inside the blocks) serves every right-hand side; the
+ *      sweep runs the reduction up and down per right-hand side.  gvi_bt_solve is a different routine
+ *      and stays as it is: ONE right-hand side, partial pivoting inside the blocks, any non-singular symmetric (D, U); the
+ *      entry points here need Lambda positive definite and agree with it to rounding there.
+ *      A count of 0 is a no-op; a negative count, a NULL buffer or a node outside [0, T): GVI_ERR_ARG; before gvi_chain_set
+ *      (gvi_ngd_*: before gvi_ngd_init): GVI_ERR_STATE; n > 16: GVI_ERR_UNSUPPORTED; Lambda not positive definite (half
+ *      log-det NaN): every entry of the output is NaN.  Results are bit-identical from run to run, and a right-hand side's
+ *      result does not depend on the batch it is solved in, so a batch may be split across calls.  Duplicate nodes are allowed. ---- */
+/* X_r = Lambda^-1 B_r, r < R.  B, X [R][T][n], host buffers (may not alias). */
+gvi_status gvi_bt_solve_multi(gvi_ctx* ctx, const double* D, const double* U, int R, const double* B, double* X);
+/* C[c][t] (n x n, row-major) = block (t, nodes[c]) of Lambda^-1 = cov(x_t, x_nodes[c]):  C[ncols][T][n][n], host buffers.  The
+ * unit right-hand sides are generated on the device from the node list; the numbers are those of gvi_bt_solve_multi on them. */
+gvi_status gvi_bt_cov_columns(gvi_ctx* ctx, const double* D, const double* U, int ncols, const int32_t* nodes, double* C);
+/* The same for the resident precision after gvi_ngd_init / _step / _run / prox_*; the state never leaves HBM and the
+ * iteration is not disturbed.  The _dev twin writes device memory (nodes stays a HOST array), asynchronously on the
+ * context stream. */
+gvi_status gvi_ngd_cov_columns(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C);
+gvi_status gvi_ngd_cov_columns_dev(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C_dev);
+
 /* ---- measurement hooks (bench.py): HIP-event time of the last moments / cost kernel launch of a
  *      set, in milliseconds, measured on the context stream; enable before the launches.
  *      on = 1: only the dominant launch (set 0, full moments pass) is bracketed -- an event pair costs
@@ -390,7 +413,9 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *   GVI_SPGH_EXTENDED    --                  auto     long-double merge of the Smolyak weights (0 / 1 force)  weights
  *   GVI_RCCL_PATH        --                  --       the only librccl candidate gvi_dist_* tries            --
  *   --                   chol_sqrt           1        Cholesky factor for sum-of-squares psi                 agree to 1e-10
- *   --                   sample_sweep        1        samplers: 0 runs the factorisation only (timing)       X not written
+ *   --                   sample_sweep        1        samplers, multi-solve: 0 = factorisation only (timing) output not written
+ *   --                   solve_lds           1        multi-solve sweep: vectors in LDS when they fit (0: in  bit-identical
+ *                                                     the output buffer whatever the size)
  *   --                   trust_table_degree  0        gvi_factors_add_table: the table is the rule of degree p  --
  *   --                   jacobi_tol_exp      -34      stopping threshold of the symmetric-root solve         rounding
  *   --                   split_flush, target_waves, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, dual_chain,
@@ -425,7 +450,7 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * (the word is stored wrong on purpose).
  * Names: split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, dual_chain, warm_start, no_scost, target_waves,
  * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge, asm_dense,
- * trust_table_degree, safe_publish, sample_sweep. */
+ * trust_table_degree, safe_publish, sample_sweep, solve_lds. */
 gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value);
 
 #ifdef __cplusplus
