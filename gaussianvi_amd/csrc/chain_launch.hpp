@@ -63,6 +63,11 @@ inline hipError_t chain_allow_lds() {
   if ((e = hipFuncSetAttribute((const void*)chain_forward_kernel<N, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)chain_backward_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)chain_top_back_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
+  if constexpr (N == 6) {
+    if ((e = hipFuncSetAttribute((const void*)chain_forward_readlane_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)chain_forward_readlane_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)chain_top_back_readlane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
+  }
   if (dev >= 0 && dev < 64) done[dev] = true;
   return hipSuccess;
 }
@@ -84,14 +89,19 @@ inline hipError_t chain_launch_t(const ChainPlan& pl, ChainArgs a0, ChainArgs a1
   a0.sync = a1.sync = nullptr; a0.sync_seq = a1.sync_seq = 0; a0.sync_fault = a1.sync_fault = sync.fault;
   const bool back0 = on0 && a0.need_back;
   const int npass = (int)pl.passes.size();
+  // N = 6, per pass: the two-row form (the kernels' default bodies) where some level is crowded -- more eliminations at the pass's
+  // first level than two per SIMD, the levels on which it puts two nodes into one wave -- and option chain_pair is on; else the
+  // v_readlane kernels (a plan-time decision: without a crowded level the two-row form is the slower one)
+  const bool pair_on = N == 6 && a0.pair != 0;
+  auto rowb = [&](const ChainPass& ps) { return pair_on && (ps.S >> 1) > pl.threads / 128; };
   // the top pass carries the backward workgroups of the last segmented pass when there is one and its LDS fits
   bool merged = false;
   if (sync.words && npass >= 2 && (back0 || on1)) {
     const ChainPass& pt = pl.passes[npass - 1];
     const ChainPass& pc = pl.passes[npass - 2];
     size_t lds = 0;
-    if (on0) lds = std::max(lds, chain::fwd_lds_doubles<true, false, true, N>(pt.S));
-    if (on1) lds = std::max(lds, chain::fwd_lds_doubles<false, true, true, N>(pt.S));
+    if (on0) lds = std::max(lds, chain::fwd_lds_doubles<true, false, true, N>(pt.S, rowb(pt)));
+    if (on1) lds = std::max(lds, chain::fwd_lds_doubles<false, true, true, N>(pt.S, rowb(pt)));
     if (back0) lds = std::max(lds, chain::bwd_lds_doubles<true, N>(pc.S));
     if (on1) lds = std::max(lds, chain::bwd_lds_doubles<false, N>(pc.S));
     merged = lds * 8 <= 160 * 1024;
@@ -101,8 +111,8 @@ inline hipError_t chain_launch_t(const ChainPlan& pl, ChainArgs a0, ChainArgs a1
     if (ps.top && merged) {
       const ChainPass& pc = pl.passes[npass - 2];
       size_t lds = 0;
-      if (on0) lds = std::max(lds, chain::fwd_lds_doubles<true, false, true, N>(ps.S));
-      if (on1) lds = std::max(lds, chain::fwd_lds_doubles<false, true, true, N>(ps.S));
+      if (on0) lds = std::max(lds, chain::fwd_lds_doubles<true, false, true, N>(ps.S, rowb(ps)));
+      if (on1) lds = std::max(lds, chain::fwd_lds_doubles<false, true, true, N>(ps.S, rowb(ps)));
       if (back0) lds = std::max(lds, chain::bwd_lds_doubles<true, N>(pc.S));
       if (on1) lds = std::max(lds, chain::bwd_lds_doubles<false, N>(pc.S));
       lds *= 8;
@@ -110,21 +120,34 @@ inline hipError_t chain_launch_t(const ChainPlan& pl, ChainArgs a0, ChainArgs a1
       const int nb0 = on0 ? 1 : 0, nbt = nb0 + (on1 ? 1 : 0);
       const int nb0c = back0 ? pc.blocks : 0, nbc = nb0c + (on1 ? pc.blocks : 0);
       const ChainPassDev cp{pc.level0, pc.m, pc.S, pc.first, pc.par, pc.lp_off};
-      hipLaunchKernelGGL((chain_top_back_kernel<N>), dim3(nbt + nbc), dim3(pl.threads), lds, st, a0, a1, nb0, AL, cp, nbt, nb0c);
+      bool launched = false;
+      if constexpr (N == 6) {
+        if (!rowb(ps)) { hipLaunchKernelGGL(chain_top_back_readlane_kernel, dim3(nbt + nbc), dim3(pl.threads), lds, st, a0, a1, nb0, AL, cp, nbt, nb0c); launched = true; }
+      }
+      if (!launched) hipLaunchKernelGGL((chain_top_back_kernel<N>), dim3(nbt + nbc), dim3(pl.threads), lds, st, a0, a1, nb0, AL, cp, nbt, nb0c);
       a0.sync = a1.sync = nullptr;
       continue;
     }
     size_t lds = 0;
     if (ps.top) {
-      if (on0) lds = std::max(lds, chain::fwd_lds_doubles<true, false, true, N>(ps.S));
-      if (on1) lds = std::max(lds, chain::fwd_lds_doubles<false, true, true, N>(ps.S));
+      if (on0) lds = std::max(lds, chain::fwd_lds_doubles<true, false, true, N>(ps.S, rowb(ps)));
+      if (on1) lds = std::max(lds, chain::fwd_lds_doubles<false, true, true, N>(ps.S, rowb(ps)));
     } else {
-      if (on0) lds = std::max(lds, chain::fwd_lds_doubles<true, false, false, N>(ps.S));
-      if (on1) lds = std::max(lds, chain::fwd_lds_doubles<false, true, false, N>(ps.S));
+      if (on0) lds = std::max(lds, chain::fwd_lds_doubles<true, false, false, N>(ps.S, rowb(ps)));
+      if (on1) lds = std::max(lds, chain::fwd_lds_doubles<false, true, false, N>(ps.S, rowb(ps)));
     }
     lds *= 8;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int nb0 = on0 ? ps.blocks : 0, nb = nb0 + (on1 ? ps.blocks : 0);
+    bool launched = false;
+    if constexpr (N == 6) {                          // the v_readlane kernels (kernels_chain.hpp)
+      if (!rowb(ps)) {
+        if (ps.top) hipLaunchKernelGGL(chain_forward_readlane_kernel<true>, dim3(nb), dim3(pl.threads), lds, st, a0, a1, nb0, AL);
+        else hipLaunchKernelGGL(chain_forward_readlane_kernel<false>, dim3(nb), dim3(pl.threads), lds, st, a0, a1, nb0, AL);
+        launched = true;
+      }
+    }
+    if (launched) continue;
     if (ps.top) hipLaunchKernelGGL((chain_forward_kernel<N, true>), dim3(nb), dim3(pl.threads), lds, st, a0, a1, nb0, AL);
     else hipLaunchKernelGGL((chain_forward_kernel<N, false>), dim3(nb), dim3(pl.threads), lds, st, a0, a1, nb0, AL);
   }
@@ -153,6 +176,10 @@ inline bool chain_wave_applies(int T, int n) { return chain_wave_enabled() && n 
 // kernels_chain.hpp AsmDense: GVI_ASM_DENSE=0, option "asm_dense")
 inline bool& chain_asm_dense_enabled() { static bool on = true; return on; }
 
+// chain_pair_enabled() = false keeps the N = 6 eliminations of every pass on the v_readlane kernels (A/B leg of the two-row
+// layout with DPP row-broadcast pivots, kernels_chain.hpp eliminate / gj_rowb / eliminate2: GVI_CHAIN_PAIR=0, option "chain_pair")
+inline bool& chain_pair_enabled() { static bool on = true; return on; }
+
 // How chain_launch classified the launches that carried an assemble list, per process: [0] the batched load path (ASM_DENSE),
 // [1] the generic set loop.  Read-only bookkeeping for the tests (gvi_debug_asm_launches); no kernel sees it.
 inline std::atomic<long long>* chain_asm_launches() { static std::atomic<long long> c[2]; return c; }
@@ -161,6 +188,7 @@ inline std::atomic<long long>* chain_asm_launches() { static std::atomic<long lo
 inline hipError_t chain_launch(int n, const ChainPlan& pl, ChainArgs a0, ChainArgs a1, bool on0, bool on1, hipStream_t st,
                                const AsmList* AL = nullptr, const ChainSync& sync = ChainSync{}) {
   a0.n = a1.n = n;
+  a0.pair = a1.pair = chain_pair_enabled() ? 1 : 0;
   AsmList none{};
   const AsmList& L = AL ? *AL : none;
   if (!AL) a0.asm_on = a1.asm_on = 0;

@@ -1140,6 +1140,7 @@ gvi_status gvi_ctx_create(int device, int dtype, gvi_ctx** out) {
   if (const char* w = getenv("GVI_PIPELINE")) c->pipeline = atoi(w) != 0;
   if (const char* w = getenv("GVI_CHAIN_WAVE")) chain_wave_enabled() = atoi(w) != 0;     // (process-wide: A/B leg of kernels_chain_wave.hpp)
   if (const char* w = getenv("GVI_ASM_DENSE")) chain_asm_dense_enabled() = atoi(w) != 0;   // (process-wide: A/B leg of the batched first-pass load)
+  if (const char* w = getenv("GVI_CHAIN_PAIR")) chain_pair_enabled() = atoi(w) != 0;      // (process-wide: A/B leg of the row-broadcast eliminations)
   if (const char* w = getenv("GVI_CHAIN_MERGE")) c->chain_merge = atoi(w) != 0;
   if (const char* w = getenv("GVI_SREG_PIPE")) c->sreg_pipe = atoi(w) != 0;
   if (const char* w = getenv("GVI_MIRROR")) c->mirror = atoi(w) != 0;
@@ -3493,6 +3494,7 @@ gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value) {
   else if (n == "pipeline") ctx->pipeline = value != 0;
   else if (n == "chain_wave") chain_wave_enabled() = value != 0;
   else if (n == "asm_dense") chain_asm_dense_enabled() = value != 0;
+  else if (n == "chain_pair") chain_pair_enabled() = value != 0;
   else if (n == "sample_sweep") ctx->sample_sweep = value != 0;
   else if (n == "solve_lds") ctx->solve_lds = value != 0;
   else if (n == "chain_merge") { ctx->chain_merge = value != 0; ctx->chain_merge_fault = value == 2; }

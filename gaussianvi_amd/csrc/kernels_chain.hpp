@@ -70,6 +70,7 @@ struct ChainArgs {
   int par;           // pass parity (Ls / yLs double buffer)
   int need_back;     // factorisation: selected inverse wanted (else log-det only)
   int lp_off;        // first log-pivot entry of this pass (top pass: number of entries written by the earlier passes)
+  int pair;          // option chain_pair (set by chain_launch; host side only: it picks the kernels per pass, no kernel reads it)
   const double* D;
   const double* U;
   const double* rhs;     // solve only
@@ -324,6 +325,29 @@ __device__ __forceinline__ double readlane64(double v, int src) {
   return u.d;
 }
 
+// ---- 64-bit DPP row broadcast (gfx950: row_newbcast:n is the one DPP control of the 64-bit ALU) ----
+// Every lane reads the operand from lane P of its OWN 16-lane row (tests/test_rowbcast_semantics_gpu.py pins this on the device,
+// also for lanes switched off).  Inline asm gets no hazard handling from the compiler: a vector write of a register needs two
+// wait states before a DPP read of it.  rowb_mov opens with the s_nop that covers them (WS = 4: also the five after a vector
+// write of EXEC, for callers with divergent code in front); rowb_fmac carries none -- its caller keeps every writer of the
+// broadcast operand in front of a rowb_mov (rowb_pin fixes compiler-written values there).
+template <int P, int WS>
+__device__ __forceinline__ double rowb_mov(const double v) {
+  double o;
+  if constexpr (WS > 1) asm volatile("s_nop 4\n\tv_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(o) : "v"(v), "n"(P));
+  else asm volatile("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(o) : "v"(v), "n"(P));
+  return o;
+}
+// c += (c of lane P of the row) * b
+template <int P>
+__device__ __forceinline__ void rowb_fmac(double& c, const double b) {
+  asm volatile("v_fmac_f64_dpp %0, %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "+v"(c) : "v"(b), "n"(P));
+}
+// the value is in its register HERE (volatile asm statements keep their order)
+__device__ __forceinline__ void rowb_pin(double& v) { asm volatile("" : "+v"(v)); }
+template <int P>
+__device__ __forceinline__ int rowb_int(const int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + P, 0xf, 0xf, false); }
+
 // element el = r N + c of a padded block -> offset inside the caller's n x n block, -1 for the padding
 template <int N> __device__ __forceinline__ int ext_el(const int n, const int el) {
   if (n == N) return el;
@@ -341,7 +365,11 @@ enum { W_E = 0, W_GA = 1, W_GB = 2, W_NU = 3, W_DEFF = 4, W_LS = 5 /* +par */, W
 enum { V_V = 0, V_YLS = 1 /* +par */, V_YRS = 3, V_YEFF = 4 };
 
 // accumulated log-pivots of a wave: product of the pivots' mantissas (renormalised), sum of their exponents, "a pivot was
-// not positive"
+// not positive".
+// INVARIANT: only LANE 0's copy is meaningful, and every consumer reads lane 0 (forward_body: the entry written at the end of a
+// pass, the top pass's reduction slots).  With v_readlane pivots every lane happens to hold the same values; in the two-row
+// layout (ROWB) lanes outside the tile -- 30 to 63 with one node per wave, an idle half with two -- run the Gauss-Jordan on
+// zeros and hold bad = 1 and NaN.  Never reduce a LogPiv across lanes.
 struct LogPiv {
   double m;
   int e, bad;
@@ -370,18 +398,95 @@ struct ElimIO {
   int oEl, oGAl, oGBl, ovl;
 };
 
+// ---- Gauss-Jordan with row-broadcast pivots (eliminate, ROWB): steps P .. N - 1 ----
+// The arithmetic of the v_readlane form below: fma(-ap[r], f, col[r]) and col[r] += bcast_P(col[r]) * (-f) are the same bits.
+// Every lane of the wave runs every step (a DPP read of a lane that is switched off returns nothing).  Pivot, reciprocal and
+// factor are uniform per 16-lane ROW; the rows of a tile carry the same D columns, so they agree bit for bit.
+// Wait states: see rowb_mov.  Writers of a register a DPP operation reads, and what separates them from it --
+//   col[r], r != P : the loads / the swap (pinned in front of this step's rowb_mov) or the rowb_fmac of step P - 1 (this
+//                    step's rowb_mov and the reciprocal chain that depends on it lie between);
+//   col[P]         : the same, or the rowb_fmac immediately in front of rowb_mov (its s_nop);
+//   col[P - 1] = f : pinned in front of the rowb_fmacs of step P - 1.
+template <bool PIVOT, int N, int P>
+__device__ __forceinline__ void gj_rowb(double (&col)[N], double& mp, int& es, int& bad) {
+  if constexpr (P < N) {
+    if (PIVOT) {                                           // threshold partial pivoting as below; the choice is broadcast per row
+      double best = fabs(col[P]);
+      int rs = P;
+#pragma unroll
+      for (int r = P + 1; r < N; ++r) {
+        const bool gt = fabs(col[r]) > best;
+        best = gt ? fabs(col[r]) : best;
+        rs = gt ? r : rs;
+      }
+      rs = fabs(col[P]) * 8.0 >= best ? P : rs;
+      rs = rowb_int<P>(rs);
+      if (__builtin_amdgcn_ballot_w64(rs != P) != 0) {     // wave-uniform branch; lanes of a row that keeps its pivot swap nothing
+#pragma unroll
+        for (int r = P + 1; r < N; ++r) {
+          const bool sw = r == rs;
+          const double t = col[P];
+          col[P] = sw ? col[r] : t;
+          col[r] = sw ? t : col[r];
+        }
+      }
+    }
+    if (PIVOT || P == 0) {
+#pragma unroll
+      for (int r = 0; r < N; ++r) rowb_pin(col[r]);
+    }
+    const double piv = rowb_mov<P, PIVOT ? 4 : 1>(col[P]);
+    if (!(piv > 0.0)) bad = 1;
+    mp *= __builtin_amdgcn_frexp_mant(piv);                // the log-pivot product in the order of the loop below
+    es += __builtin_amdgcn_frexp_exp(piv);
+    double ip = __builtin_amdgcn_rcp(piv);                 // reciprocal + two Newton steps (full fp64 accuracy)
+    ip = fma(fma(-piv, ip, 1.0), ip, ip);
+    ip = fma(fma(-piv, ip, 1.0), ip, ip);
+    double f = col[P] * ip;
+    rowb_pin(f);
+    const double nf = -f;
+#pragma unroll
+    for (int r = 0; r < N; ++r)
+      if (r != P) rowb_fmac<P>(col[r], nf);
+    col[P] = f;
+    gj_rowb<PIVOT, N, P + 1>(col, mp, es, bad);
+  }
+}
+
 // ---- forward elimination of one node by one wave ----
-template <bool PIVOT, bool HAS_E, bool HAS_Y, bool TOP, int N>
+// ROWB (N = 6; option chain_pair): the tile lies in TWO 16-lane rows and the pivot columns are broadcast inside a row by DPP
+// (gj_rowb) instead of v_readlane through scalar registers.  The D columns are carried twice (D' in row 1 runs the same
+// arithmetic and writes nothing), so that every column has its pivot column in its own row:
+//   factorisation   row 0: D(6) | I(6) | Ua^T[0..3]      row 1: D'(6) | Ua^T[4..5] | Ub(6)
+//   solve           row 0: D(6) | Ua^T(6) | Ub[0..3]     row 1: D'(6) | Ub[4..5] | y
+template <bool PIVOT, bool HAS_E, bool HAS_Y, bool TOP, int N, bool ROWB = false>
 __device__ __forceinline__ void eliminate(double* sm, const int lane, const ElimIO io, double* gE, double* gGA, double* gGB,
                                           double* gv, double* gNU, LogPiv& lp) {
   using C = Cols<HAS_E, HAS_Y, N>;
   const bool has_a = io.oUa >= 0, has_b = io.oUb >= 0;              // wave-uniform
-  const bool isD = lane < N;
-  const bool isE = HAS_E && lane >= C::cE && lane < C::cA;
-  const bool isA = lane >= C::cA && lane < C::cB;
-  const bool isB = lane >= C::cB && lane < C::cY;
-  const bool isY = HAS_Y && lane == C::cY;
-  const int cc = isD ? lane : (isE ? lane - C::cE : (isA ? lane - C::cA : (isB ? lane - C::cB : 0)));   // column inside its group
+  bool isD, isE, isA, isB, isY;
+  int cc;                                                           // column inside its group
+  if constexpr (ROWB) {
+    constexpr int G0 = 16 - 2 * N;                                  // columns of the split group (Ua^T / Ub) that fit row 0
+    static_assert(!ROWB || (G0 > 0 && G0 <= N && 2 * N - G0 + (HAS_E ? N : 1) <= 16), "two-row layout");
+    constexpr int l1 = 16 + N, l2 = l1 + N - G0;                    // row 1: rest of the split group, then Ub / y
+    const bool split0 = lane >= 16 - G0 && lane < 16, split1 = lane >= l1 && lane < l2;
+    isD = lane < N || (lane >= 16 && lane < l1);
+    isE = HAS_E && lane >= N && lane < 2 * N;
+    isA = HAS_E ? (split0 || split1) : (lane >= N && lane < 2 * N);
+    isB = HAS_E ? (lane >= l2 && lane < l2 + N) : (split0 || split1);
+    isY = HAS_Y && lane == l2;
+    const int cs = split0 ? lane - (16 - G0) : lane - l1 + G0;      // column of a lane of the split group
+    cc = isD ? (lane < N ? lane : lane - 16) : (isE ? lane - N : (isA ? (HAS_E ? cs : lane - N) : (isB ? (HAS_E ? lane - l2 : cs) : 0)));
+  } else {
+    isD = lane < N;
+    isE = HAS_E && lane >= C::cE && lane < C::cA;
+    isA = lane >= C::cA && lane < C::cB;
+    isB = lane >= C::cB && lane < C::cY;
+    isY = HAS_Y && lane == C::cY;
+    cc = isD ? lane : (isE ? lane - C::cE : (isA ? lane - C::cA : (isB ? lane - C::cB : 0)));
+  }
+  const bool isF = ROWB ? (isE || isA || isB || isY) : (lane >= N && lane < C::NC);   // lanes that hold a factor column (E / GA / GB / v)
   // ---- this lane's column: col[r] = sm[p0 + r s0] + sm[p1 + r] ----
   int p0 = io.oZero, s0 = 0, p1 = io.oZero;
   if (isD) { p0 = io.oD + cc * N; s0 = 1; p1 = io.oR + cc * N; }                       // symmetric: row = column
@@ -406,9 +511,13 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
 #pragma unroll
     for (int k = 0; k < (PRE ? N : 1); ++k) ld_row<N>(sm + io.oUa + k * N, uap[k]);            // UaT[k][:] = Ua[:, k]
   }
-  // ---- Gauss-Jordan, pivot columns broadcast with v_readlane ----
+  // ---- Gauss-Jordan ----
+  double mp = 1.0;                                         // log-pivots of this node: mantissa product, exponent sum
+  int es = 0, bad = 0;
+  if constexpr (ROWB) gj_rowb<PIVOT, N, 0>(col, mp, es, bad);
+  else {
+  // pivot columns broadcast with v_readlane
   double pivs[N];
-  int bad = 0;
 #pragma unroll
   for (int p = 0; p < N; ++p) {
     if (PIVOT) {
@@ -447,16 +556,15 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
       if (r != p) col[r] = fma(-ap[r], f, col[r]);
     col[p] = f;
   }
-  CHAIN_STAMP(TOP && HAS_E);
-  // ---- log-pivots (wave-uniform values; every lane keeps the same accumulator) ----
-  {
-    double mp = 1.0;
-    int es = 0;
 #pragma unroll
-    for (int p = 0; p < N; ++p) {
-      mp *= __builtin_amdgcn_frexp_mant(pivs[p]);
-      es += __builtin_amdgcn_frexp_exp(pivs[p]);
-    }
+  for (int p = 0; p < N; ++p) {
+    mp *= __builtin_amdgcn_frexp_mant(pivs[p]);
+    es += __builtin_amdgcn_frexp_exp(pivs[p]);
+  }
+  }
+  CHAIN_STAMP(TOP && HAS_E);
+  // ---- log-pivots (uniform over the wave -- ROWB: over the lanes of the tile; lane 0 is the one that is read) ----
+  {
     const double t = lp.m * mp;
     lp.m = __builtin_amdgcn_frexp_mant(t);
     lp.e += es + __builtin_amdgcn_frexp_exp(t);
@@ -465,14 +573,14 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
   CHAIN_STAMP(TOP && HAS_E);
   // ---- factors: E / GA / GB / v of this node ----
   if (TOP) {                                               // kept in LDS, row-major, for the backward recursion of this pass
-    if (lane >= N && lane < C::NC) {
+    if (isF) {
       const int o = isE ? io.oEl + cc : (isA ? io.oGAl + cc : (isB ? io.oGBl + cc : io.ovl));
       const int so = isY ? 1 : N;
 #pragma unroll
       for (int r = 0; r < N; ++r) sm[o + r * so] = col[r];
     }
   } else {                                                 // to the workspace (column-contiguous = transposed), read by pass C
-    if (lane >= N && lane < C::NC) {
+    if (isF) {
       double* g = isE ? gE + cc * N : (isA ? gGA + cc * N : (isB ? gGB + cc * N : gv));
       st_row<N>(g, col);
     }
@@ -543,6 +651,111 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
     }
   }
   CHAIN_STAMP(TOP && HAS_E);
+}
+
+// ---- forward elimination of TWO nodes by one wave (ROWB layout; crowded levels, forward_body) ----
+// A node in the two-row layout is 32 lanes, so lanes 0-31 eliminate one node and lanes 32-63 another: half as many waves
+// issue on a level where the eliminations queue for the SIMDs.  Same arithmetic per node as eliminate<ROWB> (bit for bit).
+// jv: the node's slot in this lane's half, -1 for an idle half (odd count) -- its lanes run the Gauss-Jordan on zeros and write
+// nothing.  What eliminate takes as wave-uniform ElimIO is formed per lane from jv and the uniform bases, where it is used; a
+// node of a paired level always has a left neighbour, a missing right neighbour (has_b, per half) reads zeros for its Ub columns
+// and adds nothing.  Log-pivots: (mantissa product, exponent sum, bad) of the node goes to LDS slot `slot` of olp; the wave that
+// would have eliminated the node folds it behind the level's barrier (forward_body), so the association of the pass's pivot
+// product stays what it is with one node per wave.
+struct ElimBases {
+  int oDl, oRl, oCt, oNU, oEl, oGAl, oGBl, ovl, oyl, oyR, oZero;
+};
+template <bool PIVOT, bool HAS_E, bool HAS_Y, bool TOP, int N>
+__device__ __forceinline__ void eliminate2(double* sm, const int lane, const int jv, const int slot, const bool lam0, const int h2,
+                                           const bool has_b, const ElimBases B, double* wE, double* wGA, double* wGB, double* wv,
+                                           const int st, const int olp) {
+  // wE / wGA / wGB / wv: the workspace arrays at the segment's first node (slot j lies st nodes further per slot); null in the top pass
+  constexpr int nn = N * N;
+  constexpr int G0 = 16 - 2 * N, l1 = 16 + N, l2 = l1 + N - G0;
+  static_assert(G0 > 0 && G0 <= N && 2 * N - G0 + (HAS_E ? N : 1) <= 16, "two-row layout");
+  const int l = lane & 31;
+  const bool on = jv >= 0;
+  const int j = on ? jv : h2;                                       // (idle half: valid addresses, nothing written)
+  const bool split0 = l >= 16 - G0 && l < 16, split1 = l >= l1 && l < l2;
+  const bool isD = on && (l < N || (l >= 16 && l < l1));
+  const bool isE = on && HAS_E && l >= N && l < 2 * N;
+  const bool isA = on && (HAS_E ? (split0 || split1) : (l >= N && l < 2 * N));
+  const bool isB = on && (HAS_E ? (l >= l2 && l < l2 + N) : (split0 || split1));
+  const bool isY = on && HAS_Y && l == l2;
+  const int cs = split0 ? l - (16 - G0) : l - l1 + G0;
+  const int cc = isD ? (l < N ? l : l - 16) : (isE ? l - N : (isA ? (HAS_E ? cs : l - N) : (isB ? (HAS_E ? l - l2 : cs) : 0)));
+  const bool isF = isE || isA || isB || isY;
+  const int ja = j - h2, jb = j + h2;
+  const int oUa = lam0 ? B.oCt + ja * nn : B.oNU + (j - h2 / 2) * nn;
+  int p0 = B.oZero, s0 = 0, p1 = B.oZero;
+  if (isD) { p0 = B.oDl + j * nn + cc * N; s0 = 1; p1 = B.oRl + j * nn + cc * N; }
+  else if (isA) { p0 = oUa + cc; s0 = N; }
+  else if (isB) { if (has_b) { p0 = (lam0 ? B.oCt + j * nn : B.oNU + (j + h2 / 2) * nn) + cc * N; s0 = 1; } }
+  else if (isY) { p0 = B.oyl + j * N; s0 = 1; p1 = B.oyR + j * N; }
+  double col[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) col[r] = sm[p0 + r * s0] + sm[p1 + r];
+  if (HAS_E) {
+#pragma unroll
+    for (int r = 0; r < N; ++r) col[r] = isE ? (r == cc ? 1.0 : 0.0) : col[r];
+  }
+  double mp = 1.0;
+  int es = 0, bad = 0;
+  gj_rowb<PIVOT, N, 0>(col, mp, es, bad);
+  // rows of Ua: requested BEHIND the Gauss-Jordan here (eliminate asks for them in front of it).  The per-lane offsets of two
+  // nodes take the registers that prefetch lives in -- with it this function spilled 36 bytes per lane -- and on a paired level
+  // a second wave of the SIMD covers the round trip.
+  __builtin_amdgcn_sched_barrier(0);
+  double uap[N][N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) ld_row<N>(sm + oUa + k * N, uap[k]);
+  if (on && l == 0) { sm[olp + slot] = mp; ((int*)(sm + olp + 32))[slot] = es * 2 + bad; }
+  // ---- factors ----
+  if (isF) {
+    if (TOP) {
+      const int o = (isE ? B.oEl + cc : (isA ? B.oGAl + cc : (isB ? B.oGBl + cc : B.ovl))) + j * (isY ? N : nn);
+      const int so = isY ? 1 : N;
+#pragma unroll
+      for (int r = 0; r < N; ++r) sm[o + r * so] = col[r];
+    } else {
+      const size_t xo = (size_t)j * st;
+      double* g = isY ? wv + xo * N : (isE ? wE : (isA ? wGA : wGB)) + xo * nn + cc * N;
+      st_row<N>(g, col);
+    }
+  }
+  // ---- Schur products: t = -Ua col, s = -Ub^T col ----
+  double t[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) t[r] = 0.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+#pragma unroll
+    for (int r = 0; r < N; ++r) t[r] = fma(-uap[k][r], col[k], t[r]);
+  }
+  const int oUb = lam0 ? B.oCt + j * nn : B.oNU + (j + h2 / 2) * nn;   // (no right neighbour: whatever lies there; nothing is kept)
+  double ubl[N][N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) ld_row<N>(sm + oUb + r * N, ubl[r]);
+  __builtin_amdgcn_sched_barrier(0);
+  if (isA || isY) {                                        // D_a -= Ua GA (column c) ; y_a -= Ua v
+    double* o = sm + (isY ? B.oyR + ja * N : B.oRl + ja * nn + cc * N);
+#pragma unroll
+    for (int r = 0; r < N; ++r) lds_add(o + r, t[r]);
+  }
+  if (has_b && isB) st_row<N>(sm + B.oNU + j * nn + cc * N, t);    // A[a,b] = -Ua GB
+  double sv[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc = fma(-ubl[r][k], col[k], acc);
+    sv[r] = acc;
+  }
+  if (has_b && (isB || isY)) {                             // D_b -= Ub^T GB (column c) ; y_b -= Ub^T v
+    double* o = sm + (isY ? B.oyl + jb * N : B.oDl + jb * nn + cc * N);
+#pragma unroll
+    for (int r = 0; r < N; ++r) lds_add(o + r, sv[r]);
+  }
 }
 
 // ---- backward step of one node: selected inverse; lane = element (r, c) ----
@@ -622,12 +835,12 @@ __device__ __forceinline__ void marginal_node(double* sm, const int lane, const 
 
 // LDS footprint (doubles)
 template <bool HAS_E, bool HAS_Y, bool TOP, int N>
-__host__ __device__ constexpr size_t fwd_lds_doubles(int S) {
+__host__ __device__ constexpr size_t fwd_lds_doubles(int S, bool rowb = false) {   // rowb: the two-row form (N = 6) runs this pass
   constexpr int nn = N * N;
   size_t w = (size_t)2 * (S + 1) * nn + (size_t)2 * S * nn;              // Dl, Rl, Ct, NUt
   if (TOP) w += (size_t)3 * S * nn + (HAS_E ? (size_t)S * nn : 0);       // El, GAl, GBl (+ SRt of the backward recursion)
   if (HAS_Y) w += (size_t)2 * (S + 1) * N + (TOP ? (size_t)(2 * S + 1) * N : 0);   // yl, yRl (+ vl, xl)
-  return w + N + (N & 1) + 128;                                          // zero block, log-det reduction
+  return w + N + (N & 1) + 128 + (rowb ? 96 : 0);                        // zero block, log-det reduction, eliminate2's log-pivot slots
 }
 template <bool HAS_E, int N>
 __host__ __device__ constexpr size_t bwd_lds_doubles(int S) {
@@ -689,7 +902,7 @@ __device__ __forceinline__ bool pred_fail_here(LazyPred& p) {
 }
 
 // ---- passes A / B: one workgroup per segment ----
-template <bool PIVOT, bool HAS_E, bool HAS_Y, bool TOP, int N>
+template <bool PIVOT, bool HAS_E, bool HAS_Y, bool TOP, int N, bool ROWB = false>
 __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& AL, const int bid, double* sm) {
   constexpr int nn = N * N;
   LazyPred lpred = pred_issue(a.pred, a.pred_val);              // checked in front of the first store (device_common.hpp)
@@ -712,6 +925,7 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
   const int oxl = ovl + ((HAS_Y && TOP) ? S * N : 0);     // top: [S+1][N]
   const int oZero = oxl + ((HAS_Y && TOP) ? (S + 1) * N : 0);
   const int oRed = oZero + N + (N & 1);
+  [[maybe_unused]] const int oLp2 = oRed + 128;     // N = 6: [2][32 doubles + 32 ints] log-pivots of the nodes of a paired level, by level parity
   CHAIN_STAMP(TOP && HAS_E);
   const int cnt = min(S, (T - x0 + st - 1) >> a.level0);    // local nodes that exist (x0 < T for every launched block)
   const int xn = x0 + S * st;
@@ -920,6 +1134,36 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
   for (int lam = 0; lam < a.m; ++lam) {
     const int h2 = 1 << lam;
     const int nel = (cnt + h2 - 1) >> (lam + 1);            // odd multiples of h2 below cnt
+    // A crowded level -- more eliminations than two per SIMD -- runs two nodes per wave (eliminate2); the decision is uniform
+    // over the workgroup.  (Never the last level of a pass, which has one elimination: no coupling leaves for the workspace.)
+    if constexpr (ROWB) {
+      if (nel > nwaves / 2 && nel <= 32) {
+        const int npair = (nel + 1) >> 1, half = lane >> 5;
+        const int olp = oLp2 + (lam & 1) * 48;
+        const ElimBases EB{oDl, oRl, oCt, oNU, oEl, oGAl, oGBl, ovl, oyl, oyR, oZero};
+        for (int q = wave; q < npair; q += nwaves) {
+          const int u = q + half * npair;                   // lanes 0-31: node q of the level, lanes 32-63: node q + npair
+          const int jv = u < nel ? (2 * u + 1) * h2 : -1;
+          const bool has_b = jv >= 0 && ((jv + h2 < cnt) || (jv + h2 == S && ext_right));
+          const size_t go = (size_t)x0 * nn;
+          eliminate2<PIVOT, HAS_E, HAS_Y, TOP, N>(sm, lane, jv, u, lam == 0, h2, has_b, EB, TOP ? nullptr : ws_mat<N>(a, W_E) + go,
+                                                  TOP ? nullptr : ws_mat<N>(a, W_GA) + go, TOP ? nullptr : ws_mat<N>(a, W_GB) + go,
+                                                  TOP ? nullptr : ws_vec<N>(a, V_V) + (size_t)x0 * N, st, olp);
+        }
+        lds_barrier();
+        // the wave that eliminates node u with one node per wave folds its log-pivots, in that order
+        for (int u = wave; u < nel; u += nwaves) {
+          const double mp = sm[olp + u];
+          const int eb = ((const int*)(sm + olp + 32))[u];
+          const double t = lp.m * mp;
+          lp.m = __builtin_amdgcn_frexp_mant(t);
+          lp.e += (eb >> 1) + __builtin_amdgcn_frexp_exp(t);
+          lp.bad |= eb & 1;
+        }
+        CHAIN_STAMP(TOP && HAS_E);
+        continue;
+      }
+    }
     for (int u = wave; u < nel; u += nwaves) {
       const int j = (2 * u + 1) * h2, x = x0 + j * st;
       const int ja = j - h2, jb = j + h2;
@@ -936,8 +1180,8 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
       const size_t gx = (size_t)x * nn;
       // the coupling created at the last level joins this segment's first node and the next one's: the next pass loads it
       double* gNU = (!TOP && lam == a.m - 1 && has_b) ? ws_mat<N>(a, W_NU) + gx : nullptr;
-      eliminate<PIVOT, HAS_E, HAS_Y, TOP, N>(sm, lane, io, ws_mat<N>(a, W_E) + gx, ws_mat<N>(a, W_GA) + gx, ws_mat<N>(a, W_GB) + gx,
-                                             ws_vec<N>(a, V_V) + (size_t)x * N, gNU, lp);
+      eliminate<PIVOT, HAS_E, HAS_Y, TOP, N, ROWB>(sm, lane, io, ws_mat<N>(a, W_E) + gx, ws_mat<N>(a, W_GA) + gx, ws_mat<N>(a, W_GB) + gx,
+                                                   ws_vec<N>(a, V_V) + (size_t)x * N, gNU, lp);
     }
     lds_barrier();
     CHAIN_STAMP(TOP && HAS_E);
@@ -966,7 +1210,7 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
       io.oD = oDl; io.oR = oRl; io.oUa = -1; io.oUb = -1; io.oRa = 0; io.oDb = 0; io.oNU = 0;
       io.oy = oyl; io.oyR = oyR; io.oyRa = 0; io.oyb = 0; io.oZero = oZero;
       io.oEl = oEl; io.oGAl = oGAl; io.oGBl = oGBl; io.ovl = ovl;
-      eliminate<PIVOT, HAS_E, HAS_Y, true, N>(sm, lane, io, nullptr, nullptr, nullptr, nullptr, nullptr, lp);
+      eliminate<PIVOT, HAS_E, HAS_Y, true, N, ROWB>(sm, lane, io, nullptr, nullptr, nullptr, nullptr, nullptr, lp);
     }
     // ---- 1/2 log det: this pass's waves leave their accumulated pivots in LDS; the LAST wave folds them with the earlier
     // passes' partial products (reduced at the start of this pass, below) and takes the one logarithm -- beside the first
@@ -1220,8 +1464,10 @@ __global__ __launch_bounds__(chain_threads(N)) void chain_forward_kernel(ChainAr
   constexpr int KA_LINES = (2 * sizeof(ChainArgs) + 8 + sizeof(AsmList) + 63) / 64;
   static_assert(KA_LINES == 13, "kernarg_warm: one specialisation per argument block size");
   kernarg_warm<KA_LINES>();
-  if ((int)blockIdx.x < nb0) chain::forward_body<false, true, false, TOP, N>(a0, AL, (int)blockIdx.x, sm);    // (predicate: inside)
-  else chain::forward_body<true, false, true, TOP, N>(a1, AL, (int)blockIdx.x - nb0, sm);
+  // N = 6: the two-row layout with DPP row-broadcast pivots (ROWB); chain_pair 0 and passes without a crowded level take
+  // chain_forward_readlane_kernel below
+  if ((int)blockIdx.x < nb0) chain::forward_body<false, true, false, TOP, N, N == 6>(a0, AL, (int)blockIdx.x, sm);    // (predicate: inside)
+  else chain::forward_body<true, false, true, TOP, N, N == 6>(a1, AL, (int)blockIdx.x - nb0, sm);
 }
 
 template <int N>
@@ -1248,8 +1494,8 @@ __global__ __launch_bounds__(chain_threads(N)) void chain_top_back_kernel(ChainA
   kernarg_warm<KA_LINES>();
   const int b = (int)blockIdx.x;
   if (b < nbt) {
-    if (b < nb0) chain::forward_body<false, true, false, true, N>(a0, AL, b, sm);
-    else chain::forward_body<true, false, true, true, N>(a1, AL, b - nb0, sm);
+    if (b < nb0) chain::forward_body<false, true, false, true, N, N == 6>(a0, AL, b, sm);
+    else chain::forward_body<true, false, true, true, N, N == 6>(a1, AL, b - nb0, sm);
     return;
   }
   const int bc = b - nbt;
@@ -1257,6 +1503,36 @@ __global__ __launch_bounds__(chain_threads(N)) void chain_top_back_kernel(ChainA
   c.level0 = cp.level0; c.m = cp.m; c.S = cp.S; c.first = cp.first; c.par = cp.par; c.lp_off = cp.lp_off;
   if (bc < nb0c) chain::backward_body<true, false, N>(c, bc, sm);
   else chain::backward_body<false, true, N>(c, bc - nb0c, sm);
+}
+
+// ---- N = 6, the v_readlane form of the forward bodies (one node per wave): option chain_pair 0, and every pass in which no
+// level is crowded (chain_launch decides per pass: without a crowded level the two-row layout only costs its longer prologue).
+// Kernels of their own, not a branch inside the ones above: with both forms in one kernel the register allocation of either
+// suffered (scratch), and the doubled code slowed the top pass by 3 us whichever form ran.  The kernels above -- the ones the
+// code-object tests look at -- hold the form that runs by default.
+template <bool TOP>
+__global__ __launch_bounds__(chain_threads(6)) void chain_forward_readlane_kernel(ChainArgs a0, ChainArgs a1, int nb0, AsmList AL) {
+  extern __shared__ double sm[];
+  kernarg_warm<13>();
+  if ((int)blockIdx.x < nb0) chain::forward_body<false, true, false, TOP, 6, false>(a0, AL, (int)blockIdx.x, sm);
+  else chain::forward_body<true, false, true, TOP, 6, false>(a1, AL, (int)blockIdx.x - nb0, sm);
+}
+
+__global__ __launch_bounds__(chain_threads(6)) void chain_top_back_readlane_kernel(ChainArgs a0, ChainArgs a1, int nb0, AsmList AL,
+                                                                                  ChainPassDev cp, int nbt, int nb0c) {
+  extern __shared__ double sm[];
+  kernarg_warm<14>();
+  const int b = (int)blockIdx.x;
+  if (b < nbt) {
+    if (b < nb0) chain::forward_body<false, true, false, true, 6, false>(a0, AL, b, sm);
+    else chain::forward_body<true, false, true, true, 6, false>(a1, AL, b - nb0, sm);
+    return;
+  }
+  const int bc = b - nbt;
+  ChainArgs c = bc < nb0c ? a0 : a1;
+  c.level0 = cp.level0; c.m = cp.m; c.S = cp.S; c.first = cp.first; c.par = cp.par; c.lp_off = cp.lp_off;
+  if (bc < nb0c) chain::backward_body<true, false, 6>(c, bc, sm);
+  else chain::backward_body<false, true, 6>(c, bc - nb0c, sm);
 }
 
 }  // namespace gvi

@@ -399,6 +399,9 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *   GVI_CHAIN_WAVE       chain_wave          1        lane-per-node chain kernel for T <= 65, n <= 2         bit-identical
  *   GVI_ASM_DENSE        asm_dense           1        assemble-on-load of one binary + one unary set as ONE  bit-identical
  *                                                     batch of loads (0: the generic loop over the sets)
+ *   GVI_CHAIN_PAIR       chain_pair          1        n = 5, 6 chain passes with a crowded level: DPP         bit-identical
+ *                                                     row-broadcast pivots, two nodes per wave there (0: the
+ *                                                     v_readlane kernels, one node per wave, in every pass)
  *   GVI_CHAIN_MERGE      chain_merge         1        top pass + first backward pass of the chain in one     bit-identical
  *                                                     launch (0: one launch per pass)
  *   GVI_FUSE_TRIAL       (gvi_ngd_set_mode)  2        0 reference pass order, 1 fused trial, 2 adaptive      identical iterates
@@ -443,13 +446,18 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * lane-per-node kernel (one wave per chain operation) instead of the generic block-cyclic-reduction kernels.
  * asm_dense (default 1; process-wide, environment GVI_ASM_DENSE): an assemble-on-load over at most one binary (d = 2n) and one
  * unary (d = n) chain-structured set issues all loads of a thread's round before the first use; 0 keeps the generic set loop.
+ * chain_pair (default 1; process-wide, environment GVI_CHAIN_PAIR): chains of block size 5 or 6 run the forward eliminations of every
+ * pass that has a level with more than eight eliminations per workgroup (any chain of 18 or more states) in the two-row tile layout,
+ * whose pivot columns are broadcast inside a 16-lane row by DPP (row_newbcast) instead of v_readlane, with two nodes per wave on
+ * those levels; the other passes, and every pass under 0, keep one node per wave on v_readlane (kernels of their own).
+ * Same arithmetic, same association of the log-pivot product: every result is bit-identical.
  * chain_merge (default 1; environment GVI_CHAIN_MERGE): a chain of more than one pass runs its top pass and the backward
  * recursion of the last segmented pass in ONE launch (the backward workgroups wait for a device word the top pass's workgroup
  * releases); 0: one launch per pass.  The wait is bounded (1 s); on a time-out the waiting workgroups take NaN for what they
  * would have read, so the affected marginals / solution are NaN and the step is rejected -- value 2 is the test of that path
  * (the word is stored wrong on purpose).
  * Names: split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, dual_chain, warm_start, no_scost, target_waves,
- * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge, asm_dense,
+ * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge, asm_dense, chain_pair,
  * trust_table_degree, safe_publish, sample_sweep, solve_lds. */
 gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value);
 

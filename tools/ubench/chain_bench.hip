@@ -2,7 +2,8 @@
 // operations of an NGD iteration side by side:
 //   factorisation of Lam (1/2 log det + tridiagonal blocks of the inverse)  ||  pivoted solve V x = -g
 // Build:  hipcc --offload-arch=gfx950 -O3 -std=c++20 -I gaussianvi_amd/csrc tools/ubench/chain_bench.hip -o tools/ubench/chain_bench
-// Run:    tools/ubench/chain_bench [T=1025] [n=6] [reps=200]        (ASM_LEG=0: without the assemble-on-load leg)
+// Run:    tools/ubench/chain_bench [T=1025] [n=6] [reps=200]        (ASM_LEG=0: without the assemble-on-load leg; CHAIN_PAIR=0:
+//         the v_readlane eliminations in every leg but the chain_pair A/B)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -199,6 +200,29 @@ static int run(int T, int n, int reps) {
     printf("run-to-run differing words: %d\n", diff);
     fail |= diff != 0;
   }
+  // chain_pair 1 against 0 (N = 6: two-row eliminations with DPP row-broadcast pivots against the v_readlane form): every output word
+  const bool pair_default = chain_pair_enabled();
+  {
+    const size_t nout = btD + btU + (size_t)T * n + 1;
+    std::vector<double> R[2];
+    for (int leg = 0; leg < 2; ++leg) {
+      chain_pair_enabled() = leg == 0;
+      clear_out();
+      CK(hipMemsetAsync(ws0, 0xff, chain_ws_doubles(T, NP) * 8, st)); CK(hipMemsetAsync(ws1, 0xff, chain_ws_doubles(T, NP) * 8, st));
+      CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync()));
+      CK(hipStreamSynchronize(st));
+      R[leg].resize(nout);
+      double* o = R[leg].data();
+      CK(hipMemcpy(o, dSig, (btD + btU) * 8, hipMemcpyDeviceToHost)); o += btD + btU;
+      CK(hipMemcpy(o, dx_, (size_t)T * n * 8, hipMemcpyDeviceToHost)); o += (size_t)T * n;
+      CK(hipMemcpy(o, dhld, 8, hipMemcpyDeviceToHost));
+    }
+    chain_pair_enabled() = pair_default;
+    size_t diff = 0, nan = 0;
+    for (size_t i = 0; i < nout; ++i) { diff += memcmp(&R[0][i], &R[1][i], 8) != 0; nan += R[0][i] != R[0][i]; }
+    printf("chain_pair 1 vs 0 differing words: %zu of %zu (NaN: %zu)\n", diff, nout, nan);
+    fail |= diff != 0 || nan != 0;
+  }
 #ifdef GVI_CHAIN_TIMING
   {
     // shader-clock stamps of thread 0 of the top pass (factorisation): label every delta by hand from the stamp order in
@@ -299,6 +323,13 @@ static int run(int T, int n, int reps) {
     CK(hipEventElapsedTime(&ms, e0, e1));
     printf("%-28s %8.2f us per call\n", name, 1e3 * ms / reps);
   };
+  for (int rep = 0; rep < 3; ++rep) {                // interleaved: chain_pair 1, 0, 1, 0, 1, 0
+    chain_pair_enabled() = true;
+    time_it("factor || solve chain_pair=1", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
+    chain_pair_enabled() = false;
+    time_it("factor || solve chain_pair=0", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
+  }
+  chain_pair_enabled() = pair_default;
   time_it("factor || solve", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
   time_it("factor only", [&]() { CK(chain_launch(n, pl, a0, a1, true, false, st, nullptr, next_sync())); });
   time_it("solve only", [&]() { CK(chain_launch(n, pl, a0, a1, false, true, st, nullptr, next_sync())); });
@@ -332,6 +363,7 @@ static int run(int T, int n, int reps) {
 
 int main(int argc, char** argv) {
   const int T = argc > 1 ? atoi(argv[1]) : 1025, n = argc > 2 ? atoi(argv[2]) : 6, reps = argc > 3 ? atoi(argv[3]) : 200;
+  if (const char* e = getenv("CHAIN_PAIR")) chain_pair_enabled() = atoi(e) != 0;      // the default of every leg but the chain_pair A/B
   if (!chain_supported(n)) { fprintf(stderr, "n must be in 1..16\n"); return 2; }
   const int rc = run(T, n, reps);
   printf(rc ? "FAILED\n" : "OK\n");
