@@ -98,6 +98,14 @@ SIGNATURES = {
     "gvi_bt_cov_columns": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gvi_ngd_cov_columns": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gvi_ngd_cov_columns_dev": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_interp_set": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gvi_interp_info": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "gvi_bt_interp": [C.c_void_p] + [C.c_void_p] * 5,
+    "gvi_ngd_interp": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "gvi_ngd_interp_dev": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "gvi_bt_interp_samples": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p],
+    "gvi_ngd_sample_interp": [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p],
+    "gvi_ngd_sample_interp_dev": [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p],
     "gvi_profile_enable": [C.c_void_p, C.c_int],
     "gvi_profile_last": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)],
     "gvi_profile_geometry": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)],

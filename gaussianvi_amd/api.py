@@ -430,6 +430,73 @@ class Context:
         nodes = self._nodes(nodes)
         self._ck(self.lib.gvi_ngd_cov_columns_dev(self.h, nodes.size, _p(nodes), C.c_void_p(ptr)))
 
+    # ---- dense-time posterior: moments and samples between the support states ----
+    def interp_set(self, idx, A, B, c=None, Qt=None):
+        """Upload and prepare the query set: idx [Q] (left support state), A, B [Q][n][n], c [Q][n] or None (zero),
+        Qt [Q][n][n] or None (no noise).  An empty idx clears the set."""
+        idx = self._nodes(idx)
+        Q, n = idx.size, self.n
+        A, B = _f64(A), _f64(B)
+        assert A.size == Q * n * n and B.size == Q * n * n, "A and B must hold Q * n * n numbers"
+        if c is not None:
+            c = _f64(c)
+            assert c.size == Q * n, "c must hold Q * n numbers"
+        if Qt is not None:
+            Qt = _f64(Qt)
+            assert Qt.size == Q * n * n, "Qt must hold Q * n * n numbers"
+        self._ck(self.lib.gvi_interp_set(self.h, Q, _p(idx), _p(A), _p(B), _p(c), _p(Qt)))
+
+    def interp_info(self):
+        """(queries held, queries marked bad by the Cholesky rule)."""
+        Q, nbad = C.c_int(), C.c_int()
+        self._ck(self.lib.gvi_interp_info(self.h, C.byref(Q), C.byref(nbad)))
+        return Q.value, nbad.value
+
+    def bt_interp(self, mu, SigD, SigU):
+        """(mean_q [Q][n], cov_q [Q][n][n]) of the query set from the marginals (mu, SigD, SigU)."""
+        mu, SigD, SigU = _f64(mu), _f64(SigD), _f64(SigU)
+        Q = self.interp_info()[0]
+        mean, cov = np.empty((Q, self.n)), np.empty((Q, self.n, self.n))
+        self._ck(self.lib.gvi_bt_interp(self.h, _p(mu), _p(SigD), _p(SigU), _p(mean), _p(cov)))
+        return mean, cov
+
+    def ngd_interp(self):
+        """bt_interp of the resident marginals (the state stays on the device)."""
+        Q = self.interp_info()[0]
+        mean, cov = np.empty((Q, self.n)), np.empty((Q, self.n, self.n))
+        self._ck(self.lib.gvi_ngd_interp(self.h, _p(mean), _p(cov)))
+        return mean, cov
+
+    def ngd_interp_dev(self, mean_ptr, cov_ptr):
+        """Into device memory (Q * n and Q * n * n doubles), asynchronous on the context stream."""
+        self._ck(self.lib.gvi_ngd_interp_dev(self.h, C.c_void_p(mean_ptr), C.c_void_p(cov_ptr)))
+
+    def bt_interp_samples(self, X, noise_seed=0, first=0, eps=None):
+        """Xq [S][Q][n] from support samples X [S][T][n]; eps ([S][Q][n]) replaces the generated normals."""
+        X = _f64(X)
+        assert X.size % (self.T * self.n) == 0, "X must hold S * T * n numbers"
+        S, Q = X.size // (self.T * self.n), self.interp_info()[0]
+        if eps is not None:
+            eps = _f64(eps)
+            assert eps.size == S * Q * self.n, "eps must hold S * Q * n numbers"
+        Xq = np.empty((S, Q, self.n))
+        self._ck(self.lib.gvi_bt_interp_samples(self.h, S, _p(X), int(noise_seed), int(first), _p(eps), _p(Xq)))
+        return Xq
+
+    def ngd_sample_interp(self, S, seed=0, noise_seed=0, first=0, want_X=True):
+        """(X [S][T][n] or None, Xq [S][Q][n]): support samples of the resident state (those of ngd_sample) and their
+        interpolation, all on the device."""
+        Q = self.interp_info()[0]
+        X = np.empty((int(S), self.T, self.n)) if want_X else None
+        Xq = np.empty((int(S), Q, self.n))
+        self._ck(self.lib.gvi_ngd_sample_interp(self.h, int(S), int(seed), int(noise_seed), int(first), _p(X), _p(Xq)))
+        return X, Xq
+
+    def ngd_sample_interp_dev(self, S, xq_ptr, seed=0, noise_seed=0, first=0, x_ptr=None):
+        """Into device memory at xq_ptr (S * Q * n doubles) and, if given, x_ptr (S * T * n doubles); asynchronous."""
+        self._ck(self.lib.gvi_ngd_sample_interp_dev(self.h, int(S), int(seed), int(noise_seed), int(first),
+                                                    C.c_void_p(x_ptr) if x_ptr else None, C.c_void_p(xq_ptr)))
+
     # ---- measurement ----
     def profile_enable(self, on=True):
         self._ck(self.lib.gvi_profile_enable(self.h, int(on)))

@@ -29,6 +29,7 @@
 #include "kernels_orbit_psi.hpp"
 #include "kernels_sample.hpp"
 #include "kernels_solve.hpp"
+#include "kernels_interp.hpp"
 #include "orbits.hpp"
 #include "spgh.hpp"
 
@@ -298,6 +299,11 @@ struct gvi_ctx {
   // (smp_io), plus the node list of the columns
   DevMem slv_idx;
   bool solve_lds = true;              // option "solve_lds" = 0: the sweep keeps its vectors in the output buffer whatever the size
+  // dense-time queries (kernels_interp.hpp): the prepared set of gvi_interp_set in buffers of its own -- the samplers and the
+  // solves overwrite smp_ws / smp_io, which only stage the inputs and outputs of a call here
+  DevMem itp_ops, itp_qt, itp_idx, itp_bad;
+  int itp_Q = 0, itp_nbad = 0;
+  bool itp_noise = false;             // the set was given a Qt array
 };
 
 namespace {
@@ -1246,6 +1252,7 @@ gvi_status gvi_chain_set(gvi_ctx* ctx, int T, int n) {
   GVICK(sync(ctx));
   ctx->T = T; ctx->n = n;
   ctx->sets.clear();
+  ctx->itp_Q = 0; ctx->itp_nbad = 0; ctx->itp_noise = false;
   ctx->ngd.ready = false;
   ctx->ngd.have_trial = false;
   ctx->dist.ranges_valid = false;
@@ -3850,6 +3857,219 @@ gvi_status gvi_ngd_cov_columns_dev(gvi_ctx* ctx, int ncols, const int32_t* nodes
   if (ncols == 0) return GVI_OK;
   HIPCK(ctx, hipSetDevice(ctx->device));
   return ngd_cov_columns_to(ctx, ncols, nodes, C_dev);
+}
+
+// ---- dense-time posterior: moments and samples between the support states (kernels_interp.hpp) ----
+gvi_status gvi_interp_set(gvi_ctx* ctx, int Q, const int32_t* idx, const double* A, const double* B, const double* c,
+                          const double* Qt) {
+  if (!ctx) return GVI_ERR_ARG;
+  if (Q < 0) return fail(ctx, GVI_ERR_ARG, "Q < 0");
+  if (ctx->T < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_chain_set first");
+  if (Q > 0 && (!idx || !A || !B)) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (ctx->n > INTERP_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  for (int q = 0; q < Q; ++q)
+    if (idx[q] < 0 || idx[q] > ctx->T - 2) return fail(ctx, GVI_ERR_ARG, "idx outside [0, T - 2]");
+  if ((int64_t)Q * ctx->n > INT32_MAX) return fail(ctx, GVI_ERR_ARG, "Q * state_dim exceeds 2^31 - 1");
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  GVICK(sync(ctx));                       // a queued _dev call may still read the set being replaced
+  ctx->itp_Q = 0; ctx->itp_nbad = 0; ctx->itp_noise = false;
+  if (Q == 0) return GVI_OK;
+  const size_t n = ctx->n, nn = n * n, Qnn = (size_t)Q * nn, Qn = (size_t)Q * n;
+  DevMem raw;                             // A | B | c: only the packed form is kept
+  HIPCK(ctx, raw.ensure((2 * Qnn + Qn) * 8));
+  HIPCK(ctx, ctx->itp_ops.ensure(Qn * (3 * n + 1) * 8));
+  HIPCK(ctx, ctx->itp_idx.ensure((size_t)Q * sizeof(int32_t)));
+  HIPCK(ctx, ctx->itp_bad.ensure((size_t)Q * sizeof(int32_t)));
+  if (Qt) HIPCK(ctx, ctx->itp_qt.ensure(Qnn * 8));
+  double* dA = raw.d();
+  double* dB = dA + Qnn;
+  double* dc = dB + Qnn;
+  GVICK(h2d(ctx, dA, A, Qnn * 8));
+  GVICK(h2d(ctx, dB, B, Qnn * 8));
+  if (c) GVICK(h2d(ctx, dc, c, Qn * 8));
+  if (Qt) GVICK(h2d(ctx, ctx->itp_qt.p, Qt, Qnn * 8));
+  GVICK(h2d(ctx, ctx->itp_idx.p, idx, (size_t)Q * sizeof(int32_t)));
+  InterpPrepArgs pa{};
+  pa.Q = Q; pa.n = (int)n; pa.A = dA; pa.B = dB; pa.c = c ? dc : nullptr; pa.Qt = Qt ? ctx->itp_qt.d() : nullptr;
+  pa.ops = ctx->itp_ops.d(); pa.bad = ctx->itp_bad.i();
+  hipLaunchKernelGGL(interp_prepare_kernel, dim3(Q), dim3(64), 0, ctx->stream, pa);
+  HIPCK(ctx, hipGetLastError());
+  std::vector<int32_t> bad(Q);
+  GVICK(d2h(ctx, bad.data(), ctx->itp_bad.p, (size_t)Q * sizeof(int32_t)));
+  GVICK(sync(ctx));                       // raw is released on return
+  int nbad = 0;
+  for (int q = 0; q < Q; ++q) nbad += bad[q] != 0;
+  ctx->itp_Q = Q; ctx->itp_nbad = nbad; ctx->itp_noise = Qt != nullptr;
+  return GVI_OK;
+}
+
+gvi_status gvi_interp_info(gvi_ctx* ctx, int* Q, int* nbad) {
+  if (!ctx) return GVI_ERR_ARG;
+  if (Q) *Q = ctx->itp_Q;
+  if (nbad) *nbad = ctx->itp_nbad;
+  return GVI_OK;
+}
+
+static gvi_status interp_check(gvi_ctx* ctx) {
+  if (!ctx) return GVI_ERR_ARG;
+  if (ctx->T < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_chain_set first");
+  return GVI_OK;
+}
+
+static gvi_status interp_have_set(gvi_ctx* ctx) {
+  if (ctx->itp_Q < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_interp_set first");
+  return GVI_OK;
+}
+
+// mean_q / cov_q (device, either may be null) of the prepared set from device (mu, SigD, SigU), on the context stream
+static gvi_status run_interp_moments(gvi_ctx* c, const double* mu, const double* SigD, const double* SigU, double* mean_q,
+                                     double* cov_q) {
+  InterpMomArgs ma{};
+  ma.Q = c->itp_Q; ma.n = c->n; ma.idx = c->itp_idx.i(); ma.ops = c->itp_ops.d();
+  ma.Qt = c->itp_noise ? c->itp_qt.d() : nullptr;
+  ma.mu = mu; ma.SigD = SigD; ma.SigU = SigU; ma.mean = mean_q; ma.cov = cov_q;
+  hipLaunchKernelGGL(interp_moments_kernel, dim3(c->itp_Q), dim3(64), 0, c->stream, ma);
+  HIPCK(c, hipGetLastError());
+  return GVI_OK;
+}
+
+// samples per workgroup of the sweep: a power of two <= INTERP_TILE_MAX, grown only while the grid keeps INTERP_TARGET_BLOCKS
+static int interp_tile(int S, int Q, int n) {
+  const int64_t qblocks = ((int64_t)Q + INTERP_SWEEP_WAVES * (64 / n) - 1) / (INTERP_SWEEP_WAVES * (64 / n));
+  int tile = 1;
+  while (tile < INTERP_TILE_MAX && qblocks * ((S + 2 * tile - 1) / (2 * tile)) >= INTERP_TARGET_BLOCKS) tile *= 2;
+  return tile;
+}
+
+// Xq [S][Q][n] (device) from X [S][T][n] (device), on the context stream
+static gvi_status run_interp_sweep(gvi_ctx* c, int S, const double* X, uint64_t noise_seed, int64_t first, const double* eps,
+                                   double* Xq) {
+  const int n = c->n, Q = c->itp_Q;
+  InterpSweepArgs sa{};
+  sa.T = c->T; sa.n = n; sa.Q = Q; sa.S = S; sa.tile = interp_tile(S, Q, n);
+  sa.noise = c->itp_noise ? 1 : 0; sa.noise_seed = noise_seed; sa.first = first;
+  sa.idx = c->itp_idx.i(); sa.ops = c->itp_ops.d(); sa.bad = c->itp_bad.i(); sa.eps = eps; sa.X = X; sa.Xq = Xq;
+  const int qpb = INTERP_SWEEP_WAVES * (64 / n);
+  const dim3 grid((unsigned)((Q + qpb - 1) / qpb), (unsigned)((S + sa.tile - 1) / sa.tile)), blk(INTERP_SWEEP_WAVES * 64);
+  if (grid.y > 65535u) return fail(c, GVI_ERR_ARG, "S exceeds 65535 sample tiles");
+  if (n <= 4) hipLaunchKernelGGL(interp_sweep_kernel<4>, grid, blk, 0, c->stream, sa);
+  else if (n <= 8) hipLaunchKernelGGL(interp_sweep_kernel<8>, grid, blk, 0, c->stream, sa);
+  else hipLaunchKernelGGL(interp_sweep_kernel<16>, grid, blk, 0, c->stream, sa);
+  HIPCK(c, hipGetLastError());
+  return GVI_OK;
+}
+
+gvi_status gvi_bt_interp(gvi_ctx* ctx, const double* mu, const double* SigD, const double* SigU, double* mean_q, double* cov_q) {
+  GVICK(interp_check(ctx));
+  if (!mu || !SigD || !SigU || !mean_q || !cov_q) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  GVICK(interp_have_set(ctx));
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t T = ctx->T, n = ctx->n, nn = n * n, Q = ctx->itp_Q;
+  HIPCK(ctx, ctx->smp_io.ensure((T * n + (2 * T - 1) * nn + Q * n + Q * nn) * 8));
+  double* dmu = ctx->smp_io.d();
+  double* dSD = dmu + T * n;
+  double* dSU = dSD + T * nn;
+  double* dm = dSU + (T - 1) * nn;
+  double* dc = dm + Q * n;
+  GVICK(h2d(ctx, dmu, mu, T * n * 8));
+  GVICK(h2d(ctx, dSD, SigD, T * nn * 8));
+  GVICK(h2d(ctx, dSU, SigU, (T - 1) * nn * 8));
+  GVICK(run_interp_moments(ctx, dmu, dSD, dSU, dm, dc));
+  GVICK(d2h(ctx, mean_q, dm, Q * n * 8));
+  GVICK(d2h(ctx, cov_q, dc, Q * nn * 8));
+  return sync(ctx);
+}
+
+// the resident marginals never leave HBM; no ChainArgs is built and nothing the iteration reads is written
+static gvi_status ngd_interp_to(gvi_ctx* ctx, double* mean_dev, double* cov_dev) {
+  NgdState& g = ctx->ngd;
+  const size_t Tnn = (size_t)ctx->T * nn_(ctx);
+  return run_interp_moments(ctx, g.mu[g.cur].d(), g.Sig[g.cur].d(), g.Sig[g.cur].d() + Tnn, mean_dev, cov_dev);
+}
+
+gvi_status gvi_ngd_interp(gvi_ctx* ctx, double* mean_q, double* cov_q) {
+  GVICK(interp_check(ctx));
+  if (!mean_q || !cov_q) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  GVICK(ngd_check(ctx));
+  GVICK(interp_have_set(ctx));
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t n = ctx->n, Q = ctx->itp_Q;
+  HIPCK(ctx, ctx->smp_io.ensure((Q * n + Q * n * n) * 8));
+  double* dm = ctx->smp_io.d();
+  double* dc = dm + Q * n;
+  GVICK(ngd_interp_to(ctx, dm, dc));
+  GVICK(d2h(ctx, mean_q, dm, Q * n * 8));
+  GVICK(d2h(ctx, cov_q, dc, Q * n * n * 8));
+  return sync(ctx);
+}
+
+gvi_status gvi_ngd_interp_dev(gvi_ctx* ctx, double* mean_q_dev, double* cov_q_dev) {
+  GVICK(interp_check(ctx));
+  if (!mean_q_dev || !cov_q_dev) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  GVICK(ngd_check(ctx));
+  GVICK(interp_have_set(ctx));
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  return ngd_interp_to(ctx, mean_q_dev, cov_q_dev);
+}
+
+gvi_status gvi_bt_interp_samples(gvi_ctx* ctx, int S, const double* X, uint64_t noise_seed, int64_t first, const double* eps,
+                                 double* Xq) {
+  GVICK(sample_check(ctx, S));
+  if (!X || !Xq) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
+  GVICK(interp_have_set(ctx));
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t SX = (size_t)S * ctx->T * ctx->n, SQ = (size_t)S * ctx->itp_Q * ctx->n;
+  HIPCK(ctx, ctx->smp_io.ensure((SX + SQ + (eps ? SQ : 0)) * 8));
+  double* dX = ctx->smp_io.d();
+  double* dXq = dX + SX;
+  double* deps = eps ? dXq + SQ : nullptr;
+  GVICK(h2d(ctx, dX, X, SX * 8));
+  if (eps) GVICK(h2d(ctx, deps, eps, SQ * 8));
+  GVICK(run_interp_sweep(ctx, S, dX, noise_seed, first, deps, dXq));
+  GVICK(d2h(ctx, Xq, dXq, SQ * 8));
+  return sync(ctx);
+}
+
+static gvi_status ngd_sample_interp_check(gvi_ctx* ctx, int S, int64_t first, const void* Xq) {
+  GVICK(sample_check(ctx, S));
+  if (!Xq) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
+  GVICK(ngd_check(ctx));
+  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  return interp_have_set(ctx);
+}
+
+gvi_status gvi_ngd_sample_interp(gvi_ctx* ctx, int S, uint64_t seed, uint64_t noise_seed, int64_t first, double* X, double* Xq) {
+  GVICK(ngd_sample_interp_check(ctx, S, first, Xq));
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t SX = (size_t)S * ctx->T * ctx->n, SQ = (size_t)S * ctx->itp_Q * ctx->n;
+  HIPCK(ctx, ctx->smp_io.ensure((SX + SQ) * 8));
+  double* dX = ctx->smp_io.d();
+  double* dXq = dX + SX;
+  GVICK(ngd_sample_to(ctx, S, seed, first, dX));
+  if (!ctx->sample_sweep) return sync(ctx);
+  GVICK(run_interp_sweep(ctx, S, dX, noise_seed, first, nullptr, dXq));
+  if (X) GVICK(d2h(ctx, X, dX, SX * 8));
+  GVICK(d2h(ctx, Xq, dXq, SQ * 8));
+  return sync(ctx);
+}
+
+gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_t noise_seed, int64_t first, double* X_dev,
+                                     double* Xq_dev) {
+  GVICK(ngd_sample_interp_check(ctx, S, first, Xq_dev));
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  double* dX = X_dev;
+  if (!dX) {                              // the support samples are not asked for: they stay in the staging buffer
+    HIPCK(ctx, ctx->smp_io.ensure((size_t)S * ctx->T * ctx->n * 8));
+    dX = ctx->smp_io.d();
+  }
+  GVICK(ngd_sample_to(ctx, S, seed, first, dX));
+  if (!ctx->sample_sweep) return GVI_OK;
+  return run_interp_sweep(ctx, S, dX, noise_seed, first, nullptr, Xq_dev);
 }
 
 }  // extern "C"

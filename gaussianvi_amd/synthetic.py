@@ -54,6 +54,31 @@ def _minacc(nd, qc, dt):
     return Phi, Qinv
 
 
+def minacc_interpolation(nd, qc, dt, tau):
+    """(A, B, Qt) of the constant-velocity prior of _minacc at time tau in [0, dt] between two support states:
+    x(tau) | x_i, x_i+1 ~ N(A x_i + B x_i+1, Qt) with Psi = Q(tau) Phi(dt - tau)^T Q(dt)^-1, A = Phi(tau) - Psi Phi(dt), B = Psi,
+    Qt = Q(tau) - Psi Phi(dt - tau) Q(tau) (Barfoot, Tong, Sarkka, RSS 2014).  The end points return exactly (I, 0, 0) and
+    (0, I, 0): evaluated numerically Qt is rounding noise of either sign there."""
+    n = 2 * nd
+    if tau == 0:
+        return np.eye(n), np.zeros((n, n)), np.zeros((n, n))
+    if tau == dt:
+        return np.zeros((n, n)), np.eye(n), np.zeros((n, n))
+    assert 0 < tau < dt, "tau outside [0, dt]"
+    I, Z = np.eye(nd), np.zeros((nd, nd))
+
+    def Phi(t):
+        return np.block([[I, t * I], [Z, I]])
+
+    def Q(t):
+        return qc * np.block([[t ** 3 / 3 * I, t ** 2 / 2 * I], [t ** 2 / 2 * I, t * I]])
+
+    Psi = Q(tau) @ Phi(dt - tau).T @ _minacc(nd, qc, dt)[1]
+    A = Phi(tau) - Psi @ Phi(dt)
+    Qt = Q(tau) - Psi @ Phi(dt - tau) @ Q(tau)
+    return A, Psi, (Qt + Qt.T) / 2
+
+
 def _ltv_system(rng, nd):
     """Four (A, B) pairs -- one per piece-wise-constant sub-interval -- of a seeded stable second-order system
     x'' = -Kp x - Kd x' + B2 u (state [x, x']): the hA / hB entries LTV_GP reads (gp/LTV_prior.h:57-61)."""

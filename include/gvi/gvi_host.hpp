@@ -558,6 +558,32 @@ class MinimumAccGP : public LinearFactor {
     _invQ.set_block(nd, 0, _invQc * (-6.0 / std::pow(_delta_t, 2)));
     _invQ.set_block(nd, nd, _invQc * (4.0 / _delta_t));
   }
+  // The prior's conditional at time tau in [0, delta_t] after this factor's first state (no reference counterpart; gvi_hip.h,
+  // "dense-time posterior"): x(tau) | x_i, x_i+1 ~ N(A x_i + B x_i+1, Qt) with Psi = Q(tau) Phi(dt - tau)^T Q(dt)^-1,
+  // A = Phi(tau) - Psi Phi(dt), B = Psi, Qt = Q(tau) - Psi Phi(dt - tau) Q(tau).  The end points return exactly (I, 0, 0) and
+  // (0, I, 0): evaluated numerically Qt is rounding noise of either sign there.
+  inline void interpolation(double tau, MatrixXd& A, MatrixXd& B, MatrixXd& Qt) const {
+    const int nd = _dim, n = _dim_state;
+    if (!(tau >= 0.0 && tau <= _delta_t)) throw std::invalid_argument("MinimumAccGP::interpolation: tau outside [0, delta_t]");
+    if (tau == 0.0 || tau == _delta_t) {
+      A = tau == 0.0 ? MatrixXd::Identity(n, n) : MatrixXd::Zero(n, n);
+      B = tau == 0.0 ? MatrixXd::Zero(n, n) : MatrixXd::Identity(n, n);
+      Qt = MatrixXd::Zero(n, n);
+      return;
+    }
+    auto phi = [&](double t) { MatrixXd P = MatrixXd::Identity(n, n); for (int i = 0; i < nd; ++i) P(i, nd + i) = t; return P; };
+    MatrixXd Qtau = MatrixXd::Zero(n, n);
+    Qtau.set_block(0, 0, _Qc * (std::pow(tau, 3) / 3));
+    Qtau.set_block(0, nd, _Qc * (std::pow(tau, 2) / 2));
+    Qtau.set_block(nd, 0, _Qc * (std::pow(tau, 2) / 2));
+    Qtau.set_block(nd, nd, _Qc * tau);
+    const MatrixXd Prest = phi(_delta_t - tau);
+    const MatrixXd Psi = Qtau * Prest.transpose() * _invQ;
+    A = phi(tau) - Psi * _Phi;
+    B = Psi;
+    const MatrixXd Qn = Qtau - Psi * Prest * Qtau;
+    Qt = (Qn + Qn.transpose()) * 0.5;
+  }
   VectorXd get_mu() const override { return _target_mu; }
   MatrixXd get_precision() const override { return _invQ; }
   MatrixXd get_covariance() const override { return _invQ.inverse(); }
@@ -1454,6 +1480,77 @@ class GVIGH {
     return covariance_columns(std::vector<int>{j}).block(i * _dim_state, 0, _dim_state, _dim_state);
   }
 
+  // ---- the posterior between the support states (no reference counterpart; gvi_hip.h, "dense-time posterior") ----
+  // Query q is the time whose left support state is states[q], with the prior's conditional operators A[q], B[q] (n x n),
+  // c[q] (n; an empty list: zero) and Qt[q] (n x n; an empty list: no noise) -- e.g. MinimumAccGP::interpolation.  The set is
+  // uploaded once and kept on the device; an empty `states` clears it.  LTV_GP has no interpolation() here (Phi and the
+  // Gramian to an interior time need the embedded RKF45 run to that time): a caller that has its operators passes them in.
+  void set_interpolation(const std::vector<int>& states, const std::vector<MatrixXd>& A, const std::vector<MatrixXd>& B,
+                         const std::vector<VectorXd>& c = {}, const std::vector<MatrixXd>& Qt = {}) {
+    const int n = _dim_state, Q = (int)states.size();
+    if ((int)A.size() != Q || (int)B.size() != Q || (!c.empty() && (int)c.size() != Q) || (!Qt.empty() && (int)Qt.size() != Q))
+      throw GviError(GVI_ERR_ARG, "set_interpolation: one operator per query");
+    auto pack = [&](const std::vector<MatrixXd>& M, std::vector<double>& out) {
+      out.resize((size_t)Q * n * n);
+      for (int q = 0; q < Q; ++q) {
+        if (M[q].rows() != n || M[q].cols() != n) throw GviError(GVI_ERR_ARG, "set_interpolation: operators must be n x n");
+        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) out[((size_t)q * n + i) * n + j] = M[q](i, j);
+      }
+    };
+    std::vector<int32_t> idx(states.begin(), states.end());
+    std::vector<double> a, b, cc, qt;
+    pack(A, a); pack(B, b);
+    if (!Qt.empty()) pack(Qt, qt);
+    if (!c.empty()) {
+      cc.resize((size_t)Q * n);
+      for (int q = 0; q < Q; ++q) {
+        if (c[q].size() != n) throw GviError(GVI_ERR_ARG, "set_interpolation: c must have n entries");
+        for (int i = 0; i < n; ++i) cc[(size_t)q * n + i] = c[q](i);
+      }
+    }
+    _dev->check(gvi_interp_set(_dev->get(), Q, idx.data(), a.data(), b.data(), c.empty() ? nullptr : cc.data(),
+                               Qt.empty() ? nullptr : qt.data()));
+    _n_queries = Q;
+  }
+  // means: n x Q (column q = mean of query q), covs: n x Q n (block column q = its covariance).  DeviceResident: from the
+  // resident marginals (gvi_ngd_interp); FactorWise: from the host blocks (gvi_bt_interp); the same numbers for both paths.
+  void interpolate(MatrixXd& means, MatrixXd& covs) {
+    const int n = _dim_state, Q = _n_queries;
+    std::vector<double> m((size_t)Q * n), cv((size_t)Q * n * n);
+    if (_exec == Execution::DeviceResident) {
+      sync_resident();
+      _dev->check(gvi_ngd_interp(_dev->get(), m.data(), cv.data()));
+    } else {
+      _dev->check(gvi_bt_interp(_dev->get(), _mu.data(), _SigD.data(), _SigU.data(), m.data(), cv.data()));
+    }
+    means = MatrixXd(n, Q); covs = MatrixXd(n, Q * n);
+    for (int q = 0; q < Q; ++q)
+      for (int i = 0; i < n; ++i) {
+        means(i, q) = m[(size_t)q * n + i];
+        for (int j = 0; j < n; ++j) covs(i, q * n + j) = cv[((size_t)q * n + i) * n + j];
+      }
+  }
+  // Q n x n_samples: column j holds the interpolated states of sample j of stream `seed` (the support samples of sample(),
+  // same seed), query after query; the conditional noise comes from stream `noise_seed`.  DeviceResident: the support samples
+  // are drawn and interpolated on the device (gvi_ngd_sample_interp); FactorWise: gvi_bt_sample + gvi_bt_interp_samples.
+  MatrixXd sample_interpolated(int n_samples, uint64_t seed = 0, uint64_t noise_seed = 1) {
+    if (n_samples < 0) throw GviError(GVI_ERR_ARG, "n_samples < 0");
+    const int rows = _n_queries * _dim_state;
+    std::vector<double> Xq((size_t)n_samples * rows);
+    if (_exec == Execution::DeviceResident) {
+      sync_resident();
+      _dev->check(gvi_ngd_sample_interp(_dev->get(), n_samples, seed, noise_seed, 0, nullptr, Xq.data()));
+    } else {
+      std::vector<double> X((size_t)n_samples * _dim);
+      _dev->check(gvi_bt_sample(_dev->get(), _D.data(), _U.data(), _mu.data(), n_samples, seed, 0, nullptr, X.data()));
+      _dev->check(gvi_bt_interp_samples(_dev->get(), n_samples, X.data(), noise_seed, 0, nullptr, Xq.data()));
+    }
+    MatrixXd M(rows, n_samples);
+    for (int j = 0; j < n_samples; ++j)
+      for (int i = 0; i < rows; ++i) M(i, j) = Xq[(size_t)j * rows + i];
+    return M;
+  }
+
   // inverse(mat) (gvibase/GVI-GH.h:161-165): the block-tridiagonal part of mat^-1 (EigenWrapper::inv_sparse /
   // inverse_GBP), computed by the device's selected inverse
   inline SpMat inverse(const SpMat& mat) {
@@ -1726,6 +1823,7 @@ class GVIGH {
   VIMPResults _res_recorder;
   std::string _prefix;
   bool _save = false, _all_device = true, _resident_stale = true;
+  int _n_queries = 0;
   Execution _exec = Execution::DeviceResident;
 };
 

@@ -350,6 +350,50 @@ gvi_status gvi_bt_cov_columns(gvi_ctx* ctx, const double* D, const double* U, in
 gvi_status gvi_ngd_cov_columns(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C);
 gvi_status gvi_ngd_cov_columns_dev(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C_dev);
 
+/* ---- dense-time posterior: mean, covariance and samples of q at times BETWEEN the support states (no reference counterpart:
+ *      the reference evaluates q at its support states only).  Where every non-prior factor touches
+ *      support states only, the state at a time tau in [t_i, t_i+1] is, under q, the Gauss-Markov prior's conditional on
+ *      (x_i, x_i+1):  x(tau) = A x_i + B x_i+1 + c + L eps,  L L^T = Qt,  eps ~ N(0, I), so
+ *          mean_q = A mu_i + B mu_i+1 + c
+ *          cov_q  = A S_ii A^T + A S_i,i+1 B^T + (A S_i,i+1 B^T)^T + B S_i+1,i+1 B^T + Qt        (S = Lambda^-1)
+ *      exactly.  A query is (idx = i, A, B, c, Qt), all row-major n x n / n; the SET of queries is uploaded once
+ *      (gvi_interp_set), prepared on the device and kept in the context in buffers of its own; the query calls move no operator
+ *      data.  Queries need not be sorted and may repeat.  gvi_chain_set clears the set.
+ *      Cholesky rule of Qt (semidefinite, fixed, lower triangle of Qt only): column k has the pivot
+ *      p = Qt_kk - sum_{j<k} L_kj^2 and thr = 64 * 2^-52 * Qt_kk;  |p| <= thr: column k of L is zero;  p > thr: the ordinary
+ *      column;  p NaN, p < -thr or Qt_kk < 0: the query is BAD -- every sample entry of a bad query is NaN, its mean and
+ *      covariance are still computed from what was given (cov_q adds Qt itself, not L L^T).  An all-zero or rank-deficient Qt
+ *      is legal and adds no noise in its null directions; Qt = NULL means no noise for any query, c = NULL means zero.
+ *      Noise numbering: the normal of (sample j, query q, component k) is number (first + j) Q n + q n + k of stream
+ *      `noise_seed` of the generator documented above (gvi_randn), so a batch split across calls or ranks gives the same
+ *      bits; the support samples keep their own numbering ((first + j) T n + t n + k of stream `seed`).
+ *      idx[q] outside [0, T - 2], a negative count or a required NULL buffer: GVI_ERR_ARG (gvi_interp_set then leaves the set
+ *      unchanged); before gvi_chain_set, gvi_ngd_* before gvi_ngd_init, or a query call before gvi_interp_set (or after the
+ *      set was cleared): GVI_ERR_STATE; n > 16: GVI_ERR_UNSUPPORTED; Q = 0 clears the set; S = 0 is a no-op; a resident
+ *      Lambda that is not positive definite makes Xq NaN as it makes X NaN.  Results are bit-identical from run to run. ---- */
+/* idx [Q], A, B [Q][n][n], c [Q][n] or NULL, Qt [Q][n][n] or NULL: host arrays.  One prepare launch; synchronous. */
+gvi_status gvi_interp_set(gvi_ctx* ctx, int Q, const int32_t* idx, const double* A, const double* B, const double* c,
+                          const double* Qt);
+/* Queries held and how many of them the Cholesky rule marked bad; either pointer may be NULL. */
+gvi_status gvi_interp_info(gvi_ctx* ctx, int* Q, int* nbad);
+/* mean_q [Q][n], cov_q [Q][n][n] from given marginals mu [T][n], SigD [T][n][n], SigU [T-1][n][n] (SigU[i] = block (i, i + 1)
+ * of the covariance, as gvi_bt_marginals returns it): host buffers, a pure operator. */
+gvi_status gvi_bt_interp(gvi_ctx* ctx, const double* mu, const double* SigD, const double* SigU, double* mean_q, double* cov_q);
+/* The same from the resident mu / SigD / SigU after gvi_ngd_init / _step / _run / prox_*; the state stays in HBM and the
+ * iteration is not disturbed.  The _dev twin writes device memory, asynchronously on the context stream. */
+gvi_status gvi_ngd_interp(gvi_ctx* ctx, double* mean_q, double* cov_q);
+gvi_status gvi_ngd_interp_dev(gvi_ctx* ctx, double* mean_q_dev, double* cov_q_dev);
+/* Xq [S][Q][n] from support samples X [S][T][n]; host buffers.  eps ([S][Q][n], optional): the normals to use instead of the
+ * generator (noise_seed / first are then ignored). */
+gvi_status gvi_bt_interp_samples(gvi_ctx* ctx, int S, const double* X, uint64_t noise_seed, int64_t first, const double* eps,
+                                 double* Xq);
+/* Draws the support samples of the resident state itself (the numbers of gvi_ngd_sample(S, seed, first)) and interpolates them
+ * on the device.  X ([S][T][n]) may be NULL when only Xq is wanted.  The _dev twin writes device memory, asynchronously on the
+ * context stream. */
+gvi_status gvi_ngd_sample_interp(gvi_ctx* ctx, int S, uint64_t seed, uint64_t noise_seed, int64_t first, double* X, double* Xq);
+gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_t noise_seed, int64_t first, double* X_dev,
+                                     double* Xq_dev);
+
 /* ---- measurement hooks (bench.py): HIP-event time of the last moments / cost kernel launch of a
  *      set, in milliseconds, measured on the context stream; enable before the launches.
  *      on = 1: only the dominant launch (set 0, full moments pass) is bracketed -- an event pair costs
