@@ -105,6 +105,15 @@ def fused_launches():
     return tuple(int(v) for v in c)
 
 
+def block3_launches():
+    """Launches of the planning graph's one-launch factor stage (factor_block3_kernel) by this process
+    (gvi_debug_block3_launches)."""
+    lib = _lib.load()
+    c = C.c_int64()
+    _ck_global(lib, lib.gvi_debug_block3_launches(C.byref(c)))
+    return c.value
+
+
 class Context:
     def __init__(self, device: int = 0, dtype: int = GVI_F64):
         self.lib = _lib.load()

@@ -749,6 +749,10 @@ void launch_orbit_pair(const OrbitArgs& a0, const OrbitArgs& a1, int m, int smax
 // Read-only bookkeeping for the tests (gvi_debug_fused_launches); no kernel sees it.
 inline std::atomic<long long>* fused_launches() { static std::atomic<long long> c[3]; return c; }
 
+// Launches of factor_block3_kernel in this process.  Read-only bookkeeping for the tests (gvi_debug_block3_launches); no
+// kernel sees it.
+inline std::atomic<long long>& block3_launches() { static std::atomic<long long> c; return c; }
+
 // the full pass of the resident iteration as one launch (kernels_fused.hpp)
 template <int M, int SMAX, int WAVES, int D0, int D1>
 gvi_status launch_fused_t(gvi_ctx* c, const FusedArgs& A, unsigned grid, size_t lds, int dmax, int copies, int items, hipEvent_t e0, hipEvent_t e1) {
@@ -2555,6 +2559,7 @@ static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, bool
   }
   const unsigned nblk = (unsigned)(block3_blocks(s0.K, A.s[0].a.nchunk) + block3_blocks(s1.K, A.s[1].a.nchunk) + block3_blocks(s2.K, A.s[2].a.nchunk));
   hipLaunchKernelGGL(factor_block3_kernel, dim3(nblk + extra), dim3(256), 4 * block3_lds_doubles() * 8, ctx->stream, A);
+  ++block3_launches();
   HIPCK(ctx, hipGetLastError());
   if (prof) { HIPCK(ctx, hipEventRecord(s1.ev[0][1], ctx->stream)); s1.ev_set[0] = true; }
   *done = true;
@@ -3376,6 +3381,12 @@ gvi_status gvi_debug_asm_launches(int64_t* dense, int64_t* generic) {
 gvi_status gvi_debug_fused_launches(int64_t counts[3]) {
   if (!counts) return fail(nullptr, GVI_ERR_ARG, "NULL");
   for (int i = 0; i < 3; ++i) counts[i] = fused_launches()[i].load();
+  return GVI_OK;
+}
+
+gvi_status gvi_debug_block3_launches(int64_t* count) {
+  if (!count) return fail(nullptr, GVI_ERR_ARG, "NULL");
+  *count = block3_launches().load();
   return GVI_OK;
 }
 

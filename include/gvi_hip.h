@@ -423,6 +423,10 @@ gvi_status gvi_debug_asm_launches(int64_t* dense, int64_t* generic);
  * <6,6,2,12,6> (n = 6, degree 6 / 7), counts[2] <2,4,4,4,2> (n = 2).  Read-only; a pass that took the three-launch route
  * counts nowhere. */
 gvi_status gvi_debug_fused_launches(int64_t counts[3]);
+/* Test hook of the planning graph's one-launch factor stage (priors d = 8, hinge on the SDF d = 4, anchors d = 4, each set at
+ * most four chunks per factor; options "fused" and "pair_fuse" on): how many launches of it this PROCESS has issued since the
+ * library was loaded.  Read-only; a pass that took the three launches (products, moments, epilogue) does not count. */
+gvi_status gvi_debug_block3_launches(int64_t* count);
 /* Kernel variant override for A/B runs: 0 = auto (sum-of-squares sets with m = 6 / 12 on a table that decomposes into sign
  * orbits take the sign-orbit kernel; otherwise 5 / 2 / 1 as instantiated), 1 = generic LDS kernel, 2 = register kernel
  * (psi operands in LDS), 5 = register kernel with psi operands in SGPRs, 6 = sign-orbit kernel where supported, 7 = auto, with

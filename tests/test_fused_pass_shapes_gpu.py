@@ -287,33 +287,40 @@ def _counted(fn, *args):
     return out, tuple(b - a for a, b in zip(c0, c1))
 
 
-def _a_then_b(ctx, P, fn, *args):
-    """fn on state A and then on state B of the same context: B's result, the launch counts of B's sequence, A's result"""
+def _a_then_b(ctx, P, counted, fn, *args):
+    """fn on state A and then on state B of the same context: B's result, the launch counts of B's sequence (counted: a
+    module's own counter), A's result"""
     ctx.ngd_init(*P["A"])
     outA = fn(*args)
     ctx.ngd_init(*P["B"])
-    out, counts = _counted(fn, *args)
+    out, counts = counted(fn, *args)
     return out, counts, outA
 
 
-def _run_sequences(P, options=None):
+def _geometry(ctx, P):
+    return [ctx.profile_geometry(sid)["nchunk"] for sid in range(len(ctx.sets))]
+
+
+def _run_sequences(P, options=None, context=None, counted=_counted, geometry=_geometry):
     """S1, S1 without the fused gather, S2 with the full pass at the trial point and with the cost pass, S3: everything of
-    state B, after the same sequence on state A in the same context"""
-    ctx = _context(P, options)
+    state B, after the same sequence on state A in the same context.  context, counted, geometry: how a module builds its
+    context, counts its kernel's launches and reads the chunking back (after S1: nchunk_s1, at the end: nchunk)"""
+    ctx = (context or _context)(P, options)
     R = {}
     try:
-        R["s1"], R["n1"], a = _a_then_b(ctx, P, _s1, ctx)
+        R["s1"], R["n1"], a = _a_then_b(ctx, P, counted, _s1, ctx)
         R["g1A"] = a["g"]
+        R["nchunk_s1"] = geometry(ctx, P)
         ctx.set_option("fuse_gather", 0)
-        R["s1ng"], R["n1ng"], _ = _a_then_b(ctx, P, _s1, ctx)
+        R["s1ng"], R["n1ng"], _ = _a_then_b(ctx, P, counted, _s1, ctx)
         ctx.set_option("fuse_gather", 1)
         for mode in (1, 0):
             ctx.ngd_set_mode(1, mode)
-            R["s2", mode], R["n2", mode], a = _a_then_b(ctx, P, _s2, ctx)
+            R["s2", mode], R["n2", mode], a = _a_then_b(ctx, P, counted, _s2, ctx)
             R["g2A", mode] = a[0]["g"]
         ctx.ngd_set_mode(1, 2)
-        R["s3"], R["n3"], _ = _a_then_b(ctx, P, ctx.ngd_step, 0.55, 10)
-        R["nchunk"] = [ctx.profile_geometry(sid)["nchunk"] for sid in range(len(ctx.sets))]
+        R["s3"], R["n3"], _ = _a_then_b(ctx, P, counted, ctx.ngd_step, 0.55, 10)
+        R["nchunk"] = geometry(ctx, P)
     finally:
         ctx.close()
     return R
@@ -328,19 +335,27 @@ def _vtol(P):
     return TIGHT if max(s["p"] for s in P["sets"]) <= 3 else 1e-8      # V at GH degree >= 5
 
 
-def _check_gradients(tag, row, gr, gA):
-    """g, V_D, V_U, dmu (and the per-factor costs, where the sequence read them) of state B against the references"""
-    P = _problem(row)
-    for rname, ref in _refs(row):
+def _cost_err(c, cr):
+    """Per-factor relative error of the costs; a factor whose reference cost is 0 exactly (a hinge factor with every sigma point
+    outside the hinge) has no relative error: there the absolute one, relative to the set's largest cost"""
+    c, cr = np.asarray(c), np.asarray(cr)
+    zero = cr == 0.0
+    return np.where(zero, np.abs(c) / np.abs(cr).max(), np.abs(c / np.where(zero, 1.0, cr) - 1.0)).max()
+
+
+def _check_gradients(tag, P, refs, regular, gr, gA):
+    """g, V_D, V_U, dmu (and the per-factor costs, where the sequence read them) of state B against the references
+    (refs: [(name, reference)]; regular: V is not singular by construction)"""
+    for rname, ref in refs:
         _hold(f"{tag} g vs {rname}", rel(gr["g"], ref["g"]), TIGHT)
         _hold(f"{tag} VD vs {rname}", rel(gr["VD"], ref["VD"]), _vtol(P))
         if any(s["kind"] == "b" for s in P["sets"]):
             _hold(f"{tag} VU vs {rname}", rel(gr["VU"], ref["VU"]), _vtol(P))
-        if row not in SINGULAR:
+        if regular:
             _hold(f"{tag} dmu vs {rname}", rel(gr["dmu"], ref["dmu"]), TIGHT)
         if "costs" in gr:
             for sid, (c, cr) in enumerate(zip(gr["costs"], ref["costs"])):
-                _hold(f"{tag} costs of set {sid} vs {rname}, per factor", np.abs(c / cr - 1.0).max(), TIGHT)
+                _hold(f"{tag} costs of set {sid} vs {rname}, per factor", _cost_err(c, cr), TIGHT)
     free = np.ones(P["T"] - 1, dtype=bool)
     for s in P["sets"]:
         if s["kind"] == "b":
@@ -349,16 +364,15 @@ def _check_gradients(tag, row, gr, gA):
     assert far_at_every_node(gr["g"], gA, P["T"]) > 1e-3
 
 
-def _check_trial(tag, row, gr, st, cost):
-    P = _problem(row)
+def _check_trial(tag, P, refs, regular, gr, st, cost):
     muB, DB, UB = P["B"]
     # formed from the device's own V by the factorisation's first pass (one fused against two rounded operations)
     _hold(f"{tag} D vs D_B + step (V_dev - D_B)", rel(st["D"], DB + STEP * (gr["VD"] - DB)), 1e-14)
     _hold(f"{tag} U vs U_B + step (V_dev - U_B)", rel(st["U"], UB + STEP * (gr["VU"] - UB)), 1e-14)
-    for rname, ref in _refs(row):
+    for rname, ref in refs:
         for k in ("D", "U", "SigD", "SigU"):
             _hold(f"{tag} trial {k} vs {rname}", rel(st[k], ref[k]), _vtol(P))
-        if row not in SINGULAR:
+        if regular:
             _hold(f"{tag} mu vs {rname}", rel(st["mu"], ref["mu"]), TIGHT)
             _hold(f"{tag} trial cost vs {rname}", abs(cost / ref["cost"] - 1.0), TIGHT)
 
@@ -372,22 +386,31 @@ def _check_step(tag, row, r3):
         _hold(f"{tag} new_cost vs {rname}", abs(r3["new_cost"] / ref["cost"] - 1.0), TIGHT)
 
 
-def _check_all(tag, row, R):
-    _check_gradients(f"{tag} S1", row, R["s1"], R["g1A"])
+def _check_sequences(tag, P, refs, regular, R, check_step):
+    """S1 (and its bits without the gather), S2 under both trial modes and, by check_step(tag, r3), S3"""
+    _check_gradients(f"{tag} S1", P, refs, regular, R["s1"], R["g1A"])
     for k in ("g", "VD", "VU", "dmu"):                             # the no-gather entry: same numbers, bit for bit
         assert np.array_equal(R["s1"][k], R["s1ng"][k], equal_nan=True), (tag, "fuse_gather 0", k)
     for c, cng in zip(R["s1"]["costs"], R["s1ng"]["costs"]):
         assert np.array_equal(c, cng), (tag, "fuse_gather 0", "costs")
     for mode in (1, 0):
         gr, st, cost = R["s2", mode]
-        _check_gradients(f"{tag} S2 mode (1, {mode})", row, gr, R["g2A", mode])
-        _check_trial(f"{tag} S2 mode (1, {mode})", row, gr, st, cost)
-    _check_step(f"{tag} S3", row, R["s3"])
+        _check_gradients(f"{tag} S2 mode (1, {mode})", P, refs, regular, gr, R["g2A", mode])
+        _check_trial(f"{tag} S2 mode (1, {mode})", P, refs, regular, gr, st, cost)
+    check_step(f"{tag} S3", R["s3"])
 
 
-def _bits_equal(R, R0, what):
-    for k in ("g", "VD", "VU", "dmu"):
-        assert np.array_equal(R["s1"][k], R0["s1"][k], equal_nan=True), (what, "S1", k)
+def _check_all(tag, row, R):
+    _check_sequences(tag, _problem(row), _refs(row), row not in SINGULAR, R, lambda t, r3: _check_step(t, row, r3))
+
+
+def _bits_equal(R, R0, what, whole_s1=False):
+    """whole_s1: S1's per-factor costs and the run without the gather as well (routes that share their chunking)"""
+    for s1 in ("s1", "s1ng") if whole_s1 else ("s1",):
+        for k in ("g", "VD", "VU", "dmu"):
+            assert np.array_equal(R[s1][k], R0[s1][k], equal_nan=True), (what, s1, k)
+        for sid, (c, c0) in enumerate(zip(R[s1]["costs"], R0[s1]["costs"]) if whole_s1 else ()):
+            assert np.array_equal(c, c0, equal_nan=True), (what, s1, "costs", sid)
     for mode in (1, 0):
         (gr, st, cost), (gr0, st0, cost0) = R["s2", mode], R0["s2", mode]
         for k in ("g", "VD", "VU", "dmu"):
