@@ -95,5 +95,17 @@ int main(int argc, char** argv) {
     for (int t = 0; t < T; t += 4) std::printf(" (%.9f, %.9f)", mu(t * n), mu(t * n + 1));
     std::printf("\n");
   }
+  // Score sampled trajectories of the final q on the device (gvi_hip.h, "costs of sampled trajectories"): cost under the
+  // factors, importance weights exp(-J - log q) and their effective sample size, clearance of the obstacle factors (set 1:
+  // the sets are formed in the order the factors were given).
+  const int S = 256;
+  const MatrixXd Jq = opt.sample_costs(S, 7);
+  const VectorXd clr = opt.sample_clearance(S, 7, 1);
+  double meanJ = 0.0, lmax = -INFINITY, sw = 0.0, sw2 = 0.0;
+  int hits = 0;
+  for (int j = 0; j < S; ++j) { meanJ += Jq(0, j) / S; lmax = std::fmax(lmax, -Jq(0, j) - Jq(1, j)); hits += clr(j) < 0.0; }
+  for (int j = 0; j < S; ++j) { const double w = std::exp(-Jq(0, j) - Jq(1, j) - lmax); sw += w; sw2 += w * w; }
+  std::printf("samples %d mean J %.9f effective sample size %.3f share with negative clearance %.4f\n", S, meanJ, sw * sw / sw2,
+              (double)hits / S);
   return 0;
 }

@@ -107,6 +107,13 @@ SIGNATURES = {
     "gvi_bt_interp_samples": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p],
     "gvi_ngd_sample_interp": [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p],
     "gvi_ngd_sample_interp_dev": [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p],
+    "gvi_sample_factor_costs": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_sample_clearance": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_sample_clearance_dev": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_sample_costs": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_sample_costs_dev": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gvi_ngd_sample_costs": [C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_int] + [C.c_void_p] * 4,
+    "gvi_ngd_sample_costs_dev": [C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_int] + [C.c_void_p] * 4,
     "gvi_profile_enable": [C.c_void_p, C.c_int],
     "gvi_profile_last": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)],
     "gvi_profile_geometry": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)],

@@ -506,6 +506,59 @@ class Context:
         self._ck(self.lib.gvi_ngd_sample_interp_dev(self.h, int(S), int(seed), int(noise_seed), int(first),
                                                     C.c_void_p(x_ptr) if x_ptr else None, C.c_void_p(xq_ptr)))
 
+    # ---- costs of sampled trajectories ----
+    def _samples(self, X):
+        X = _f64(X)
+        assert X.size % (self.T * self.n) == 0, "X must hold S * T * n numbers"
+        return X, X.size // (self.T * self.n)
+
+    def sample_factor_costs(self, sid, X):
+        """cost [S][K] of set sid at the samples X [S][T][n]: psi_k(x[start_k n : start_k n + d]) / temperature_k."""
+        X, S = self._samples(X)
+        out = np.empty((S, self.sets[sid][0]))
+        self._ck(self.lib.gvi_sample_factor_costs(self.h, sid, S, _p(X), _p(out)))
+        return out
+
+    def sample_clearance(self, sid, X):
+        """clr [S][K] of a hinge-on-SDF set: min over the factor's check points of sdf(p_b) - r_b."""
+        X, S = self._samples(X)
+        out = np.empty((S, self.sets[sid][0]))
+        self._ck(self.lib.gvi_sample_clearance(self.h, sid, S, _p(X), _p(out)))
+        return out
+
+    def sample_clearance_dev(self, sid, S, x_ptr, clr_ptr):
+        """Device buffers (S * T * n and S * K doubles), asynchronous on the context stream."""
+        self._ck(self.lib.gvi_sample_clearance_dev(self.h, sid, int(S), C.c_void_p(x_ptr), C.c_void_p(clr_ptr)))
+
+    def sample_costs(self, X):
+        """J [S]: the sum of every factor's cost over every set, in the documented fixed order."""
+        X, S = self._samples(X)
+        out = np.empty(S)
+        self._ck(self.lib.gvi_sample_costs(self.h, S, _p(X), _p(out)))
+        return out
+
+    def sample_costs_dev(self, S, x_ptr, j_ptr):
+        """Device buffers (S * T * n and S doubles), asynchronous on the context stream."""
+        self._ck(self.lib.gvi_sample_costs_dev(self.h, int(S), C.c_void_p(x_ptr), C.c_void_p(j_ptr)))
+
+    def ngd_sample_costs(self, S, seed=0, first=0, clearance_set=-1, want_X=True, want_logq=True):
+        """dict(X [S][T][n] or None, J [S], logq [S] or None, clr_min [S] or None) of samples of the resident state (those
+        of ngd_sample), drawn and evaluated on the device."""
+        S = int(S)
+        X = np.empty((S, self.T, self.n)) if want_X else None
+        J = np.empty(S)
+        logq = np.empty(S) if want_logq else None
+        clr = np.empty(S) if clearance_set >= 0 else None
+        self._ck(self.lib.gvi_ngd_sample_costs(self.h, S, int(seed), int(first), int(clearance_set), _p(X), _p(J), _p(logq), _p(clr)))
+        return dict(X=X, J=J, logq=logq, clr_min=clr)
+
+    def ngd_sample_costs_dev(self, S, j_ptr, seed=0, first=0, clearance_set=-1, x_ptr=None, logq_ptr=None, clr_min_ptr=None):
+        """Into device memory (S doubles each; x_ptr: S * T * n); asynchronous on the context stream.  Without x_ptr the
+        samples stay in a buffer of the context."""
+        opt = lambda ptr: C.c_void_p(ptr) if ptr else None
+        self._ck(self.lib.gvi_ngd_sample_costs_dev(self.h, int(S), int(seed), int(first), int(clearance_set), opt(x_ptr),
+                                                   C.c_void_p(j_ptr), opt(logq_ptr), opt(clr_min_ptr)))
+
     # ---- measurement ----
     def profile_enable(self, on=True):
         self._ck(self.lib.gvi_profile_enable(self.h, int(on)))

@@ -30,6 +30,7 @@
 #include "kernels_sample.hpp"
 #include "kernels_solve.hpp"
 #include "kernels_interp.hpp"
+#include "kernels_sample_cost.hpp"
 #include "orbits.hpp"
 #include "spgh.hpp"
 
@@ -304,6 +305,8 @@ struct gvi_ctx {
   DevMem itp_ops, itp_qt, itp_idx, itp_bad;
   int itp_Q = 0, itp_nbad = 0;
   bool itp_noise = false;             // the set was given a Qt array
+  // costs of sampled trajectories (kernels_sample_cost.hpp): the per-factor cost / clearance matrices and the staged results
+  DevMem scost_ws;
 };
 
 namespace {
@@ -3706,6 +3709,27 @@ gvi_status gvi_ngd_sample_dev(gvi_ctx* ctx, int S, uint64_t seed, int64_t first,
   return ngd_sample_to(ctx, S, seed, first, X_dev);
 }
 
+// logq [S] (device) of the device samples X under N(mu, (D, U)^-1), on the context stream: the chain kernels' half log-det
+// (arguments and a workspace of its own: no mix, no predicate, no back pass) into dh [1], the quadratic forms into dQ [S][T]
+static gvi_status run_logpdf(gvi_ctx* ctx, const double* dD, const double* dU, const double* dmu, int S, const double* dX,
+                             double* dQ, double* dh, double* dl) {
+  const int T = ctx->T, n = ctx->n, NP = chain_padded(n);
+  HIPCK(ctx, ctx->smp_cws.ensure(chain_ws_doubles(T, NP) * 8));
+  HIPCK(ctx, ctx->smp_cwsi.ensure(chain_lp_entries(T) * sizeof(int)));
+  ChainArgs a{};
+  a.T = T; a.n = n; a.need_back = 0;
+  a.D = dD; a.U = dU; a.rhs_scale = 1.0;
+  a.ws = ctx->smp_cws.d(); a.wsi = (int*)ctx->smp_cwsi.p; a.hld = dh;
+  const hipError_t e = chain_launch(n, chain_plan(T, n), a, a, true, false, ctx->stream);
+  if (e == hipErrorInvalidValue) return fail(ctx, GVI_ERR_UNSUPPORTED, "chain kernels: block size / LDS budget");
+  HIPCK(ctx, e);
+  const int64_t items = (int64_t)S * T;
+  hipLaunchKernelGGL(logpdf_quad_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, T, n, S, dD, dU, dmu, dX, dQ);
+  hipLaunchKernelGGL(logpdf_reduce_kernel, dim3(S), dim3(256), 0, ctx->stream, T, n, dQ, dh, dl);
+  HIPCK(ctx, hipGetLastError());
+  return GVI_OK;
+}
+
 gvi_status gvi_bt_logpdf(gvi_ctx* ctx, const double* D, const double* U, const double* mu, int S, const double* X, double* logq) {
   GVICK(sample_check(ctx, S));
   if (!D || (!U && ctx->T > 1) || !mu || !X || !logq) return fail(ctx, GVI_ERR_ARG, "NULL argument");
@@ -3727,20 +3751,7 @@ gvi_status gvi_bt_logpdf(gvi_ctx* ctx, const double* D, const double* U, const d
   if (T > 1) GVICK(h2d(ctx, dU, U, (size_t)(T - 1) * nn * 8));
   GVICK(h2d(ctx, dmu, mu, Tn * 8));
   GVICK(h2d(ctx, dX, X, SX * 8));
-  // the existing half log-det (chain kernels), on arguments and a workspace of its own: no mix, no predicate, no back pass
-  HIPCK(ctx, ctx->smp_cws.ensure(chain_ws_doubles(T, NP) * 8));
-  HIPCK(ctx, ctx->smp_cwsi.ensure(chain_lp_entries(T) * sizeof(int)));
-  ChainArgs a{};
-  a.T = T; a.n = n; a.need_back = 0;
-  a.D = dD; a.U = dU; a.rhs_scale = 1.0;
-  a.ws = ctx->smp_cws.d(); a.wsi = (int*)ctx->smp_cwsi.p; a.hld = dh;
-  const hipError_t e = chain_launch(n, chain_plan(T, n), a, a, true, false, ctx->stream);
-  if (e == hipErrorInvalidValue) return fail(ctx, GVI_ERR_UNSUPPORTED, "chain kernels: block size / LDS budget");
-  HIPCK(ctx, e);
-  const int64_t items = (int64_t)S * T;
-  hipLaunchKernelGGL(logpdf_quad_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, T, n, S, dD, dU, dmu, dX, dQ);
-  hipLaunchKernelGGL(logpdf_reduce_kernel, dim3(S), dim3(256), 0, ctx->stream, T, n, dQ, dh, dl);
-  HIPCK(ctx, hipGetLastError());
+  GVICK(run_logpdf(ctx, dD, dU, dmu, S, dX, dQ, dh, dl));
   GVICK(d2h(ctx, logq, dl, (size_t)S * 8));
   return sync(ctx);
 }
@@ -4081,6 +4092,223 @@ gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_
   GVICK(ngd_sample_to(ctx, S, seed, first, dX));
   if (!ctx->sample_sweep) return GVI_OK;
   return run_interp_sweep(ctx, S, dX, noise_seed, first, nullptr, Xq_dev);
+}
+
+// ---- costs of sampled trajectories (kernels_sample_cost.hpp) ----
+static bool hinge_kind(int kind) { return kind >= KIND_HINGE_SDF_2D && kind <= KIND_HINGE_SDF_3D_ARM; }
+
+static gvi_status scost_check_set(gvi_ctx* ctx, const FactorSet& s, bool clearance) {
+  if (s.kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_UNSUPPORTED, "a PSI_HOST_CALLBACK set has no device psi");
+  if (clearance && !hinge_kind(s.kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "clearance needs a hinge-on-SDF set");
+  if (scost_sumsq(s.kind) && s.d > SCOST_DMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
+  if (s.kind == KIND_HINGE_SDF_3D_ARM && !s.arm.p)
+    return fail(ctx, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");
+  if (hinge_kind(s.kind) && s.sdf_rows == 0)
+    return fail(ctx, GVI_ERR_STATE, "HINGE_SDF set without a grid: call gvi_factors_set_sdf2d / gvi_factors_set_sdf3d");
+  return GVI_OK;
+}
+
+// every set of the context can be evaluated on the device (gvi_sample_costs / gvi_ngd_sample_costs)
+static gvi_status scost_check_all(gvi_ctx* ctx, int clearance_set) {
+  if ((int)ctx->sets.size() > MAX_FSETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
+  for (int i = 0; i < (int)ctx->sets.size(); ++i) GVICK(scost_check_set(ctx, *ctx->sets[i], i == clearance_set));
+  return GVI_OK;
+}
+
+static int64_t scost_total_factors(const gvi_ctx* ctx) {
+  int64_t K = 0;
+  for (auto& s : ctx->sets) K += s->K;
+  return K;
+}
+
+// ONE launch over the sets [lo, hi): cost (device, or null) is [S][ld] with the sets' columns side by side from column 0;
+// clr (device, or null) is [S][ld_clr] of set clr_set.  X is a device buffer; everything on the context stream.
+static gvi_status run_sample_cost(gvi_ctx* c, int lo, int hi, int S, const double* X, double* cost, int64_t ld, int clr_set,
+                                  double* clr, int64_t ld_clr) {
+  SampleCostList L{};
+  L.T = c->T; L.n = c->n; L.S = S; L.X = X;
+  int64_t nb = 0, koff = 0;
+  int dmax = 0;
+  for (int i = lo; i < hi; ++i) {
+    FactorSet& s = *c->sets[i];
+    double* cp = cost ? cost + koff : nullptr;
+    double* kp = i == clr_set ? clr : nullptr;
+    koff += s.K;
+    if (s.K == 0 || (!cp && !kp)) continue;
+    const int j = L.nsets++;
+    L.f[j] = s.dev(); L.start[j] = s.dstart.i();
+    L.cost[j] = cp; L.clr[j] = kp; L.ld_cost[j] = ld; L.ld_clr[j] = ld_clr;
+    L.boff[j] = (int)nb;
+    if (scost_sumsq(s.kind)) {
+      // tiles of 4 G factors; the samples are cut into chunks only as far as the grid needs them (a block loads its rows of A once)
+      const int F = SCOST_WAVES * (64 / scost_group(s.m));
+      const int ft = (s.K + F - 1) / F;
+      const int nsc = std::max(1, std::min(S, (SCOST_TARGET_BLOCKS + ft - 1) / ft));
+      L.ftiles[j] = ft;
+      L.schunk[j] = (S + nsc - 1) / nsc;
+      nb += (int64_t)ft * ((S + L.schunk[j] - 1) / L.schunk[j]);
+      dmax = std::max(dmax, s.d);
+    } else {
+      nb += ((int64_t)s.K * S + SCOST_THREADS - 1) / SCOST_THREADS;
+    }
+    if (nb > 0x7fffffffLL) return fail(c, GVI_ERR_ARG, "S * K exceeds the grid");
+  }
+  L.boff[L.nsets] = (int)nb;
+  if (L.nsets == 0) return GVI_OK;
+  const dim3 grid((unsigned)nb), blk(SCOST_THREADS);
+  if (dmax <= 4) hipLaunchKernelGGL(sample_cost_kernel<4>, grid, blk, 0, c->stream, L);
+  else if (dmax <= 8) hipLaunchKernelGGL(sample_cost_kernel<8>, grid, blk, 0, c->stream, L);
+  else if (dmax <= 12) hipLaunchKernelGGL(sample_cost_kernel<12>, grid, blk, 0, c->stream, L);
+  else if (dmax <= 16) hipLaunchKernelGGL(sample_cost_kernel<16>, grid, blk, 0, c->stream, L);
+  else if (dmax <= 24) hipLaunchKernelGGL(sample_cost_kernel<24>, grid, blk, 0, c->stream, L);
+  else hipLaunchKernelGGL(sample_cost_kernel<32>, grid, blk, 0, c->stream, L);
+  HIPCK(c, hipGetLastError());
+  return GVI_OK;
+}
+
+// J [S] and, for clr_set >= 0 with clr_min != null, clr_min [S] (device buffers) of the device samples X: the launch over
+// every set into the matrices of scost_ws (behind `head` doubles the caller keeps for itself), then the ordered reduction
+static gvi_status run_sample_costs_total(gvi_ctx* c, int S, const double* X, double* J, int clr_set, double* clr_min, size_t head) {
+  const int64_t Kt = scost_total_factors(c), Kc = (clr_set >= 0 && clr_min) ? c->sets[clr_set]->K : 0;
+  double* cm = c->scost_ws.d() + head;
+  double* km = cm + (size_t)S * Kt;
+  const bool want_clr = clr_set >= 0 && clr_min;
+  GVICK(run_sample_cost(c, 0, (int)c->sets.size(), S, X, cm, Kt, want_clr ? clr_set : -1, km, Kc));
+  SampleCostReduceArgs ra{};
+  ra.Kt = (int)Kt; ra.Kc = (int)Kc; ra.cost = cm; ra.clr = want_clr ? km : nullptr; ra.J = J; ra.clr_min = clr_min;
+  hipLaunchKernelGGL(sample_cost_reduce_kernel, dim3(S), dim3(256), 0, c->stream, ra);
+  HIPCK(c, hipGetLastError());
+  return GVI_OK;
+}
+
+static size_t scost_total_doubles(const gvi_ctx* c, int S, int clr_set) {
+  return (size_t)S * (size_t)(scost_total_factors(c) + (clr_set >= 0 ? c->sets[clr_set]->K : 0));
+}
+
+static gvi_status scost_set_check(gvi_ctx* ctx, int set_id, int S, const void* X, const void* out, bool clearance) {
+  GVICK(sample_check(ctx, S));
+  if (!X || !out) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (set_id < 0 || set_id >= (int)ctx->sets.size()) return fail(ctx, GVI_ERR_ARG, "bad set id");
+  return scost_check_set(ctx, *ctx->sets[set_id], clearance);
+}
+
+// cost / clearance matrix [S][K] of one set from host samples
+static gvi_status sample_set_matrix(gvi_ctx* ctx, int set_id, int S, const double* X, double* out, bool clearance) {
+  GVICK(scost_set_check(ctx, set_id, S, X, out, clearance));
+  const size_t K = ctx->sets[set_id]->K, SX = (size_t)S * ctx->T * ctx->n;
+  if (S == 0 || K == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  HIPCK(ctx, ctx->smp_io.ensure(SX * 8));
+  HIPCK(ctx, ctx->scost_ws.ensure((size_t)S * K * 8));
+  GVICK(h2d(ctx, ctx->smp_io.p, X, SX * 8));
+  double* dm = ctx->scost_ws.d();
+  GVICK(run_sample_cost(ctx, set_id, set_id + 1, S, ctx->smp_io.d(), clearance ? nullptr : dm, (int64_t)K, clearance ? set_id : -1,
+                        dm, (int64_t)K));
+  GVICK(d2h(ctx, out, dm, (size_t)S * K * 8));
+  return sync(ctx);
+}
+
+gvi_status gvi_sample_factor_costs(gvi_ctx* ctx, int set_id, int S, const double* X, double* cost) {
+  return sample_set_matrix(ctx, set_id, S, X, cost, false);
+}
+
+gvi_status gvi_sample_clearance(gvi_ctx* ctx, int set_id, int S, const double* X, double* clr) {
+  return sample_set_matrix(ctx, set_id, S, X, clr, true);
+}
+
+gvi_status gvi_sample_clearance_dev(gvi_ctx* ctx, int set_id, int S, const double* X_dev, double* clr_dev) {
+  GVICK(scost_set_check(ctx, set_id, S, X_dev, clr_dev, true));
+  const int64_t K = ctx->sets[set_id]->K;
+  if (S == 0 || K == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  return run_sample_cost(ctx, set_id, set_id + 1, S, X_dev, nullptr, K, set_id, clr_dev, K);
+}
+
+gvi_status gvi_sample_costs(gvi_ctx* ctx, int S, const double* X, double* J) {
+  GVICK(sample_check(ctx, S));
+  if (!X || !J) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  GVICK(scost_check_all(ctx, -1));
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t SX = (size_t)S * ctx->T * ctx->n;
+  HIPCK(ctx, ctx->smp_io.ensure(SX * 8));
+  HIPCK(ctx, ctx->scost_ws.ensure((S + scost_total_doubles(ctx, S, -1)) * 8));
+  GVICK(h2d(ctx, ctx->smp_io.p, X, SX * 8));
+  double* dJ = ctx->scost_ws.d();
+  GVICK(run_sample_costs_total(ctx, S, ctx->smp_io.d(), dJ, -1, nullptr, (size_t)S));
+  GVICK(d2h(ctx, J, dJ, (size_t)S * 8));
+  return sync(ctx);
+}
+
+gvi_status gvi_sample_costs_dev(gvi_ctx* ctx, int S, const double* X_dev, double* J_dev) {
+  GVICK(sample_check(ctx, S));
+  if (!X_dev || !J_dev) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  GVICK(scost_check_all(ctx, -1));
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  HIPCK(ctx, ctx->scost_ws.ensure(scost_total_doubles(ctx, S, -1) * 8));
+  return run_sample_costs_total(ctx, S, X_dev, J_dev, -1, nullptr, 0);
+}
+
+static gvi_status ngd_sample_costs_check(gvi_ctx* ctx, int S, int64_t first, int clearance_set, const void* J) {
+  GVICK(sample_check(ctx, S));
+  if (!J) return fail(ctx, GVI_ERR_ARG, "NULL argument");
+  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
+  if (clearance_set >= (int)ctx->sets.size()) return fail(ctx, GVI_ERR_ARG, "bad set id");
+  GVICK(ngd_check(ctx));
+  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
+  return scost_check_all(ctx, clearance_set < 0 ? -1 : clearance_set);
+}
+
+// sampler -> cost launch + reduction -> log-density, all on the context stream and on device buffers; the cost matrices and
+// the log-density's scratch sit in scost_ws behind `head` doubles
+static gvi_status ngd_sample_costs_to(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, int clr_set, double* dX, double* dJ,
+                                      double* dlogq, double* dclr, size_t head) {
+  NgdState& g = ctx->ngd;
+  GVICK(ngd_sample_to(ctx, S, seed, first, dX));
+  if (!ctx->sample_sweep) return GVI_OK;
+  GVICK(run_sample_costs_total(ctx, S, dX, dJ, clr_set, dclr, head));
+  if (!dlogq) return GVI_OK;
+  double* dQ = ctx->scost_ws.d() + head + scost_total_doubles(ctx, S, clr_set);
+  double* dh = dQ + (size_t)S * ctx->T;
+  const double* Lam = g.Lam[g.cur].d();
+  return run_logpdf(ctx, Lam, Lam + (size_t)ctx->T * nn_(ctx), g.mu[g.cur].d(), S, dX, dQ, dh, dlogq);
+}
+
+gvi_status gvi_ngd_sample_costs(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, int clearance_set, double* X, double* J,
+                                double* logq, double* clr_min) {
+  GVICK(ngd_sample_costs_check(ctx, S, first, clearance_set, J));
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const int cs = (clearance_set >= 0 && clr_min) ? clearance_set : -1;
+  const size_t SX = (size_t)S * ctx->T * ctx->n, head = 3 * (size_t)S;
+  HIPCK(ctx, ctx->smp_io.ensure(SX * 8));
+  HIPCK(ctx, ctx->scost_ws.ensure((head + scost_total_doubles(ctx, S, cs) + (size_t)S * ctx->T + 1) * 8));
+  double* dJ = ctx->scost_ws.d();
+  double* dl = dJ + S;
+  double* dc = dl + S;
+  GVICK(ngd_sample_costs_to(ctx, S, seed, first, cs, ctx->smp_io.d(), dJ, logq ? dl : nullptr, cs >= 0 ? dc : nullptr, head));
+  if (!ctx->sample_sweep) return sync(ctx);
+  if (X) GVICK(d2h(ctx, X, ctx->smp_io.p, SX * 8));
+  GVICK(d2h(ctx, J, dJ, (size_t)S * 8));
+  if (logq) GVICK(d2h(ctx, logq, dl, (size_t)S * 8));
+  if (cs >= 0) GVICK(d2h(ctx, clr_min, dc, (size_t)S * 8));
+  return sync(ctx);
+}
+
+gvi_status gvi_ngd_sample_costs_dev(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, int clearance_set, double* X_dev,
+                                    double* J_dev, double* logq_dev, double* clr_min_dev) {
+  GVICK(ngd_sample_costs_check(ctx, S, first, clearance_set, J_dev));
+  if (S == 0) return GVI_OK;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const int cs = (clearance_set >= 0 && clr_min_dev) ? clearance_set : -1;
+  double* dX = X_dev;
+  if (!dX) {                              // the samples are not asked for: they stay in the staging buffer
+    HIPCK(ctx, ctx->smp_io.ensure((size_t)S * ctx->T * ctx->n * 8));
+    dX = ctx->smp_io.d();
+  }
+  HIPCK(ctx, ctx->scost_ws.ensure((scost_total_doubles(ctx, S, cs) + (size_t)S * ctx->T + 1) * 8));
+  return ngd_sample_costs_to(ctx, S, seed, first, cs, dX, J_dev, logq_dev, cs >= 0 ? clr_min_dev : nullptr, 0);
 }
 
 }  // extern "C"

@@ -813,30 +813,51 @@ __device__ __forceinline__ double hinge_sq(double sd, double thr, double slope, 
   return err * err * sigma;
 }
 
+// Check points of the hinge-on-SDF kinds.  Each *_points function walks the check points b of one factor at one state and
+// calls visit(sd_b, r_b) with the signed distance at the point and the radius of its ball; psi (the sum of the hinges) and the
+// clearance (min_b sd_b - r_b, costs of sampled trajectories: kernels_sample_cost.hpp) are two visitors of the SAME points
+// in the same arithmetic.
+
 // planar point robot (CudaOperation_PlanarPR::cost_obstacle_planar, helpers/CudaOperation.h:491-523): one ball at
 // (x0, x1), slope 1.  p = [sigma, eps, r].
+template <typename V>
+__device__ __forceinline__ void hinge_sdf2d_points(const FactorDev& f, const double* p, double px, double py, V&& visit) {
+  visit(sdf2d_lookup(f, px, py), p[2]);
+}
 __device__ inline double psi_hinge_sdf2d(const FactorDev& f, const double* p, double px, double py) {
-  return hinge_sq(sdf2d_lookup(f, px, py), p[1] + p[2], 1.0, p[0]);
+  double cost = 0.0;
+  hinge_sdf2d_points(f, p, px, py, [&](double sd, double r) { cost = hinge_sq(sd, p[1] + r, 1.0, p[0]); });
+  return cost;
 }
 
 // planar quadrotor body (CudaOperation_Quad::cost_obstacle_planar / vec_balls, helpers/CudaOperation.h:565-606):
 // pose (x, z, phi) = x[0:3]; n_balls check points along the body axis starting at
 // pos - (L - 1.5 r)/2 (cos phi, sin phi), spaced L/n_balls.  p = [sigma, eps, r, slope, n_balls, L].
-__device__ inline double psi_hinge_sdf2d_body(const FactorDev& f, const double* p, double px, double pz, double phi) {
+template <typename V>
+__device__ __forceinline__ void hinge_sdf2d_body_points(const FactorDev& f, const double* p, double px, double pz, double phi, V&& visit) {
   double sn, cs;
   sincos(phi, &sn, &cs);
-  const double r = p[2], L = p[5], thr = p[1] + r;
+  const double r = p[2], L = p[5];
   const int nb = (int)p[4];
   const double lx = px - (L - r * 1.5) * cs / 2.0, lz = pz - (L - r * 1.5) * sn / 2.0;
+  for (int i = 0; i < nb; ++i) visit(sdf2d_lookup(f, lx + L * cs / nb * i, lz + L * sn / nb * i), r);
+}
+__device__ inline double psi_hinge_sdf2d_body(const FactorDev& f, const double* p, double px, double pz, double phi) {
+  const double thr = p[1] + p[2];
   double cost = 0.0;
-  for (int i = 0; i < nb; ++i)
-    cost += hinge_sq(sdf2d_lookup(f, lx + L * cs / nb * i, lz + L * sn / nb * i), thr, p[3], p[0]);
+  hinge_sdf2d_body_points(f, p, px, pz, phi, [&](double sd, double) { cost += hinge_sq(sd, thr, p[3], p[0]); });
   return cost;
 }
 
 // 3-D point robot (CudaOperation_3dpR::cost_obstacle_planar, helpers/CudaOperation.h:650-683).  p = [sigma, eps, r].
+template <typename V>
+__device__ __forceinline__ void hinge_sdf3d_points(const FactorDev& f, const double* p, double px, double py, double pz, V&& visit) {
+  visit(sdf3d_lookup(f, px, py, pz), p[2]);
+}
 __device__ inline double psi_hinge_sdf3d(const FactorDev& f, const double* p, double px, double py, double pz) {
-  return hinge_sq(sdf3d_lookup(f, px, py, pz), p[1] + p[2], 1.0, p[0]);
+  double cost = 0.0;
+  hinge_sdf3d_points(f, p, px, py, pz, [&](double sd, double r) { cost = hinge_sq(sd, p[1] + r, 1.0, p[0]); });
+  return cost;
 }
 
 // 7-DOF-style arm (CudaOperation_3dArm::cost_obstacle + ForwardKinematics, helpers/CudaOperation.h:325-399, 752-771):
@@ -844,14 +865,14 @@ __device__ inline double psi_hinge_sdf3d(const FactorDev& f, const double* p, do
 // (theta.size(), :753), cost = sigma sum_s hinge(eps + radius_s - sdf(p_s))^2.  The reference builds every DH matrix
 // from cosf / sinf (single precision, :388-395; products of two trig terms are float products) -- restated as such.
 // Frames are non-decreasing (checked on the host), so the chain is advanced once.  p = [sigma, eps].
-__device__ inline double psi_hinge_sdf3d_arm(const FactorDev& f, const double* p, const double* x, int d) {
+template <typename V>
+__device__ __forceinline__ void hinge_sdf3d_arm_points(const FactorDev& f, const double* x, int d, V&& visit) {
   const double* A = f.arm;
   const int nd = (int)A[0], ns = (int)A[1];
   const double *a = A + 2, *al = a + nd, *dl = al + nd, *tb = dl + nd, *fr = tb + nd, *ce = fr + ns, *ra = ce + 3 * ns;
   double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};           // rows 0..2 of the homogeneous transform
   const int nb = d < ns ? d : ns;
   int done = -1;                                                  // last joint folded into T
-  double cost = 0.0;
   for (int s = 0; s < nb; ++s) {
     const int frame = (int)fr[s];
     while (done < frame) {
@@ -876,9 +897,36 @@ __device__ inline double psi_hinge_sdf3d_arm(const FactorDev& f, const double* p
     const double px = T[3] + (T[0] * cx + T[1] * cy + T[2] * cz);
     const double py = T[7] + (T[4] * cx + T[5] * cy + T[6] * cz);
     const double pz = T[11] + (T[8] * cx + T[9] * cy + T[10] * cz);
-    cost += hinge_sq(sdf3d_lookup(f, px, py, pz), p[1] + ra[s], 1.0, p[0]);
+    visit(sdf3d_lookup(f, px, py, pz), ra[s]);
   }
+}
+__device__ inline double psi_hinge_sdf3d_arm(const FactorDev& f, const double* p, const double* x, int d) {
+  double cost = 0.0;
+  hinge_sdf3d_arm_points(f, x, d, [&](double sd, double r) { cost += hinge_sq(sd, p[1] + r, 1.0, p[0]); });
   return cost;
+}
+
+// psi and / or clearance of factor k of a hinge-on-SDF set at the state slice x [d].  psi is the kind's
+// psi_* function; the clearance walks the same *_points with a min-visitor.  eps and slope play no part in the clearance.
+__device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, const double* x, bool want_psi, bool want_clr,
+                                                    double& psi, double& clr) {
+  const double* p = f.raw + (size_t)k * f.raw_stride;
+  double c = __builtin_inf();
+  auto keep = [&](double sd, double r) { c = fmin(c, sd - r); };
+  if (f.kind == KIND_HINGE_SDF_2D) {
+    if (want_psi) psi = psi_hinge_sdf2d(f, p, x[0], x[1]);
+    if (want_clr) hinge_sdf2d_points(f, p, x[0], x[1], keep);
+  } else if (f.kind == KIND_HINGE_SDF_2D_BODY) {
+    if (want_psi) psi = psi_hinge_sdf2d_body(f, p, x[0], x[1], x[2]);
+    if (want_clr) hinge_sdf2d_body_points(f, p, x[0], x[1], x[2], keep);
+  } else if (f.kind == KIND_HINGE_SDF_3D) {
+    if (want_psi) psi = psi_hinge_sdf3d(f, p, x[0], x[1], x[2]);
+    if (want_clr) hinge_sdf3d_points(f, p, x[0], x[1], x[2], keep);
+  } else {
+    if (want_psi) psi = psi_hinge_sdf3d_arm(f, p, x, f.d);
+    if (want_clr) hinge_sdf3d_arm_points(f, x, f.d, keep);
+  }
+  if (want_clr) clr = c;
 }
 
 // ---------------------------------------------------------------------------------------------

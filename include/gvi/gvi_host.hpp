@@ -1551,6 +1551,55 @@ class GVIGH {
     return M;
   }
 
+  // ---- costs of sampled trajectories (no reference counterpart; gvi_hip.h, "costs of sampled trajectories") ----
+  // 2 x n_samples: row 0 = J(x_j), the sum of psi_k / temperature_k over every factor at sample j of stream `seed` (the
+  // samples of sample(), same seed), row 1 = log q(x_j): exp(-J - log q) is the sample's importance weight against q.
+  // DeviceResident: drawn and evaluated on the device, the samples never leave it (gvi_ngd_sample_costs); FactorWise:
+  // gvi_bt_sample + gvi_sample_costs + gvi_bt_logpdf on the host blocks; the same numbers for both paths.  Every factor needs
+  // a DevicePsi (an opaque host psi: GVI_ERR_UNSUPPORTED).
+  MatrixXd sample_costs(int n_samples, uint64_t seed = 0) {
+    if (n_samples < 0) throw GviError(GVI_ERR_ARG, "n_samples < 0");
+    std::vector<double> J((size_t)n_samples), lq((size_t)n_samples);
+    if (_exec == Execution::DeviceResident) {
+      sync_resident();
+      _dev->check(gvi_ngd_sample_costs(_dev->get(), n_samples, seed, 0, -1, nullptr, J.data(), lq.data(), nullptr));
+    } else {
+      std::vector<double> X((size_t)n_samples * _dim);
+      _dev->check(gvi_bt_sample(_dev->get(), _D.data(), _U.data(), _mu.data(), n_samples, seed, 0, nullptr, X.data()));
+      _dev->check(gvi_sample_costs(_dev->get(), n_samples, X.data(), J.data()));
+      _dev->check(gvi_bt_logpdf(_dev->get(), _D.data(), _U.data(), _mu.data(), n_samples, X.data(), lq.data()));
+    }
+    MatrixXd M(2, n_samples);
+    for (int j = 0; j < n_samples; ++j) { M(0, j) = J[(size_t)j]; M(1, j) = lq[(size_t)j]; }
+    return M;
+  }
+  // Minimum over the factors of set `factor_set` (the sets are formed in the order their first factor was given: factors
+  // of the same dimension, degree and psi group share one; hinge-on-SDF kinds only) of sdf(p_b) - r_b at sample j of stream `seed`: negative where the sampled trajectory touches an obstacle.
+  VectorXd sample_clearance(int n_samples, uint64_t seed, int factor_set) {
+    if (n_samples < 0) throw GviError(GVI_ERR_ARG, "n_samples < 0");
+    if (factor_set < 0 || factor_set >= (int)_sets.size()) throw GviError(GVI_ERR_ARG, "sample_clearance: no such factor set");
+    VectorXd out(n_samples);
+    if (_exec == Execution::DeviceResident) {
+      sync_resident();
+      std::vector<double> J((size_t)n_samples);
+      _dev->check(gvi_ngd_sample_costs(_dev->get(), n_samples, seed, 0, _batches[(size_t)factor_set]->set_id(), nullptr, J.data(), nullptr, out.data()));
+    } else {
+      const size_t K = _sets[(size_t)factor_set].members.size();
+      std::vector<double> X((size_t)n_samples * _dim), clr((size_t)n_samples * K);
+      _dev->check(gvi_bt_sample(_dev->get(), _D.data(), _U.data(), _mu.data(), n_samples, seed, 0, nullptr, X.data()));
+      _dev->check(gvi_sample_clearance(_dev->get(), _batches[(size_t)factor_set]->set_id(), n_samples, X.data(), clr.data()));
+      for (int j = 0; j < n_samples; ++j) {      // NaN-propagating minimum, as the device's
+        double m = INFINITY;
+        for (size_t k = 0; k < K; ++k) {
+          const double v = clr[(size_t)j * K + k];
+          m = (m != m || v != v) ? NAN : (v < m ? v : m);
+        }
+        out(j) = m;
+      }
+    }
+    return out;
+  }
+
   // inverse(mat) (gvibase/GVI-GH.h:161-165): the block-tridiagonal part of mat^-1 (EigenWrapper::inv_sparse /
   // inverse_GBP), computed by the device's selected inverse
   inline SpMat inverse(const SpMat& mat) {

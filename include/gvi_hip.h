@@ -394,6 +394,50 @@ gvi_status gvi_ngd_sample_interp(gvi_ctx* ctx, int S, uint64_t seed, uint64_t no
 gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_t noise_seed, int64_t first, double* X_dev,
                                      double* Xq_dev);
 
+/* ---- costs of sampled trajectories: the factors' psi, the total cost and the obstacle clearance evaluated at samples of q (no
+ *      reference counterpart: the reference evaluates psi at sigma points only).  The psi of every kind
+ *      is the device function the quadrature uses, so the closest reference lines are those of the kinds: src/1d_example.cpp:25-35
+ *      (RANGE_1D), gp/minimum_acc_prior.h:103-106 and gp/LTV_prior.h:223-226 (QUAD_PRIOR), gp/fixed_prior.h:28-30 (FIXED_PRIOR),
+ *      helpers/CudaOperation.h:491-523 (HINGE_SDF_2D), :565-606 (_2D_BODY), :650-683 (_3D), :325-399 and :752-771 (_3D_ARM).
+ *      For a sample x [T][n] and factor k of a set (start, d):  x_k = x[start_k n .. start_k n + d), the slice
+ *      gvi_gather_marginals takes;  cost_k(x) = psi_k(x_k) / temperature_k (the temperatures the iteration divides by: unit
+ *      under GVI_RULE_PROX_JKO);  J(x) = sum over the sets, over k, of cost_k(x).
+ *      The CLEARANCE of a hinge-on-SDF factor is min_b sdf(p_b) - r_b over the factor's check points b -- the points of its
+ *      psi, in the same arithmetic: the one ball of HINGE_SDF_2D / _3D, the n_balls body points of _2D_BODY, the first
+ *      min(d, nspheres) spheres with their own radii of _3D_ARM.  epsilon and slope play no part in it.  It is the continuous
+ *      quantity; the library returns no collided / not-collided indicator.
+ *      S = 0 is a no-op; S < 0, a required NULL buffer, first < 0 or a set id outside the context's sets: GVI_ERR_ARG; before
+ *      gvi_chain_set (gvi_ngd_*: before gvi_ngd_init): GVI_ERR_STATE, as is a hinge set whose grid (arm model) was never set; a
+ *      GVI_PSI_HOST_CALLBACK set: GVI_ERR_UNSUPPORTED, for its own call and for the calls over every set of a context that
+ *      holds one; a sum-of-squares set with d > 32, more than 8 sets, the resident calls with n > 16: GVI_ERR_UNSUPPORTED.
+ *      A sample whose slice for a factor holds a non-finite value gives NaN for that factor's cost and clearance (the psi /
+ *      SDF code is not entered, no index is formed from a NaN), hence for J and the minimum clearance; factors that do not
+ *      touch the bad entries stay finite.  A resident Lambda that is not positive definite makes X NaN, as for gvi_ngd_sample,
+ *      and therefore J, logq and clr_min.  Results are bit-identical from run to run, and a sample's results do not depend on
+ *      S or on the batch or call it is in, so a batch may be split by `first`.
+ *      Order of J: the cost rows of the sets are laid side by side, set 0 first, factor index ascending, K_total entries; thread t
+ *      of 256 adds entries t, t + 256, ... in ascending order, and the 256 partial sums are folded by halving (t += t + 128, then
+ *      64, ... 1).  The order depends on the sets only. ---- */
+/* cost [S][K] of one set at X [S][T][n]; host buffers, a pure operator. */
+gvi_status gvi_sample_factor_costs(gvi_ctx* ctx, int set_id, int S, const double* X, double* cost);
+/* clr [S][K]: hinge-on-SDF sets only, every other kind: GVI_ERR_UNSUPPORTED.  The _dev twin takes device buffers and is
+ * asynchronous on the context stream. */
+gvi_status gvi_sample_clearance(gvi_ctx* ctx, int set_id, int S, const double* X, double* clr);
+gvi_status gvi_sample_clearance_dev(gvi_ctx* ctx, int set_id, int S, const double* X_dev, double* clr_dev);
+/* J [S] over every set of the context: one launch over all sets, one ordered reduction. */
+gvi_status gvi_sample_costs(gvi_ctx* ctx, int S, const double* X, double* J);
+gvi_status gvi_sample_costs_dev(gvi_ctx* ctx, int S, const double* X_dev, double* J_dev);
+/* Draws the samples of the resident state on the device (the bits of gvi_ngd_sample(S, seed, first)), evaluates J, log q
+ * (the log-density path of gvi_bt_logpdf on the resident (mu, D, U)) and, for clearance_set >= 0, each sample's minimum
+ * clearance over that set's factors, clr_min [S] (clearance_set < 0: clr_min is not written).  X, logq and clr_min may be NULL;
+ * with X = NULL the samples live in a buffer of the context and never leave HBM.  The resident state and the iteration are
+ * not disturbed.  Under the timing-only option "sample_sweep" = 0 the calls run the sampler's factorisation alone and leave X,
+ * J, logq and clr_min untouched, as gvi_ngd_sample does with X. */
+gvi_status gvi_ngd_sample_costs(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, int clearance_set, double* X, double* J,
+                                double* logq, double* clr_min);
+gvi_status gvi_ngd_sample_costs_dev(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, int clearance_set, double* X_dev,
+                                    double* J_dev, double* logq_dev, double* clr_min_dev);
+
 /* ---- measurement hooks (bench.py): HIP-event time of the last moments / cost kernel launch of a
  *      set, in milliseconds, measured on the context stream; enable before the launches.
  *      on = 1: only the dominant launch (set 0, full moments pass) is bracketed -- an event pair costs
