@@ -156,6 +156,26 @@ struct NgdState {
   GatherPending gpend[2];
 };
 
+// State of the posterior queries (posterior_host.inc)
+struct Posterior {
+  // samplers / log-density (kernels_sample.hpp): workspaces of their own, so that a call between NGD steps touches nothing
+  // the iteration reads or writes
+  DevMem smp_ws, smp_io, smp_cws, smp_cwsi;
+  bool sample_sweep = true;           // option "sample_sweep" = 0: the samplers and the multi-solve run the factorisation only (tools/*_bench.py)
+  // multi-right-hand-side solve / covariance columns (kernels_solve.hpp): the sampler's factor workspace (smp_ws) and staging
+  // (smp_io), plus the node list of the columns
+  DevMem slv_idx;
+  bool solve_lds = true;              // option "solve_lds" = 0: the sweep keeps its vectors in the output buffer whatever the size
+  // dense-time queries (kernels_interp.hpp): the prepared set of gvi_interp_set in buffers of its own -- the samplers and the
+  // solves overwrite smp_ws / smp_io, which only stage the inputs and outputs of a call here
+  DevMem itp_ops, itp_qt, itp_idx, itp_bad;
+  int itp_Q = 0, itp_nbad = 0;
+  bool itp_noise = false;             // the set was given a Qt array
+  // costs of sampled trajectories (kernels_sample_cost.hpp): the per-factor cost / clearance matrices and the staged results
+  DevMem scost_ws;
+  void clear_interp() { itp_Q = 0; itp_nbad = 0; itp_noise = false; }
+};
+
 }  // namespace
 
 struct gvi_ctx {
@@ -292,21 +312,7 @@ struct gvi_ctx {
   bool safe_publish = false;          // option "safe_publish": checked publish + release / acquire arrival counters (device_common.hpp)
   DevMem dbg_log;                     // gvi_debug_cost_log: ring of the costs the epilogue tails published, indexed by sequence
   int dbg_mask = 0;
-  // samplers / log-density (kernels_sample.hpp): workspaces of their own, so that a call between NGD steps touches nothing
-  // the iteration reads or writes
-  DevMem smp_ws, smp_io, smp_cws, smp_cwsi;
-  bool sample_sweep = true;           // option "sample_sweep" = 0: the samplers and the multi-solve run the factorisation only (tools/*_bench.py)
-  // multi-right-hand-side solve / covariance columns (kernels_solve.hpp): the sampler's factor workspace (smp_ws) and staging
-  // (smp_io), plus the node list of the columns
-  DevMem slv_idx;
-  bool solve_lds = true;              // option "solve_lds" = 0: the sweep keeps its vectors in the output buffer whatever the size
-  // dense-time queries (kernels_interp.hpp): the prepared set of gvi_interp_set in buffers of its own -- the samplers and the
-  // solves overwrite smp_ws / smp_io, which only stage the inputs and outputs of a call here
-  DevMem itp_ops, itp_qt, itp_idx, itp_bad;
-  int itp_Q = 0, itp_nbad = 0;
-  bool itp_noise = false;             // the set was given a Qt array
-  // costs of sampled trajectories (kernels_sample_cost.hpp): the per-factor cost / clearance matrices and the staged results
-  DevMem scost_ws;
+  Posterior post;                     // state of the posterior queries (posterior_host.inc)
 };
 
 namespace {
@@ -1259,7 +1265,7 @@ gvi_status gvi_chain_set(gvi_ctx* ctx, int T, int n) {
   GVICK(sync(ctx));
   ctx->T = T; ctx->n = n;
   ctx->sets.clear();
-  ctx->itp_Q = 0; ctx->itp_nbad = 0; ctx->itp_noise = false;
+  ctx->post.clear_interp();
   ctx->ngd.ready = false;
   ctx->ngd.have_trial = false;
   ctx->dist.ranges_valid = false;
@@ -1673,16 +1679,31 @@ gvi_status gvi_bt_assemble(gvi_ctx* ctx, int nsets, const int* set_ids, const do
   return sync(ctx);
 }
 
+// Staging: the ONE place a buffer of doubles is sized and cut.  ensure() on the sum of the regions, then every region's pointer,
+// in the order given -- the size and the carve cannot disagree.  An empty region gets the pointer of the next one.
+struct Region { double** at; size_t doubles; };
+static gvi_status carve(gvi_ctx* ctx, DevMem& buf, std::initializer_list<Region> regions) {
+  size_t total = 0;
+  for (const Region& r : regions) total += r.doubles;
+  HIPCK(ctx, buf.ensure(total * 8));
+  double* p = buf.d();
+  for (const Region& r : regions) { *r.at = p; p += r.doubles; }
+  return GVI_OK;
+}
+
+// (D, U) of a host-pointer call into their regions, on the context stream; a single-state chain has no U
+static gvi_status put_chain(gvi_ctx* ctx, double* dD, double* dU, const double* D, const double* U) {
+  const size_t T = ctx->T, nn = nn_(ctx);
+  GVICK(h2d(ctx, dD, D, T * nn * 8));
+  if (T > 1) GVICK(h2d(ctx, dU, U, (T - 1) * nn * 8));
+  return GVI_OK;
+}
+
 static gvi_status stage_chain(gvi_ctx* ctx, const double* D, const double* U, size_t extra, double** dD, double** dU,
                               double** dextra) {
   const size_t T = ctx->T, nn = nn_(ctx);
-  HIPCK(ctx, ctx->scratch.ensure((bt_count(ctx) + extra) * 8));
-  *dD = ctx->scratch.d();
-  *dU = *dD + T * nn;
-  *dextra = *dU + (T - 1) * nn;
-  GVICK(h2d(ctx, *dD, D, T * nn * 8));
-  if (T > 1) GVICK(h2d(ctx, *dU, U, (T - 1) * nn * 8));
-  return GVI_OK;
+  GVICK(carve(ctx, ctx->scratch, {{dD, T * nn}, {dU, (T - 1) * nn}, {dextra, extra}}));
+  return put_chain(ctx, *dD, *dU, D, U);
 }
 
 gvi_status gvi_bt_solve(gvi_ctx* ctx, const double* D, const double* U, const double* rhs, double* x) {
@@ -3516,8 +3537,8 @@ gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value) {
   else if (n == "chain_wave") chain_wave_enabled() = value != 0;
   else if (n == "asm_dense") chain_asm_dense_enabled() = value != 0;
   else if (n == "chain_pair") chain_pair_enabled() = value != 0;
-  else if (n == "sample_sweep") ctx->sample_sweep = value != 0;
-  else if (n == "solve_lds") ctx->solve_lds = value != 0;
+  else if (n == "sample_sweep") ctx->post.sample_sweep = value != 0;
+  else if (n == "solve_lds") ctx->post.solve_lds = value != 0;
   else if (n == "chain_merge") { ctx->chain_merge = value != 0; ctx->chain_merge_fault = value == 2; }
   else if (n == "trust_table_degree") ctx->trust_table_degree = value != 0;
   else if (n == "safe_publish") {
@@ -3578,737 +3599,8 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant) {
   return GVI_OK;
 }
 
-// ---- sampling and log-density of q = N(mu, Lambda^-1) (kernels_sample.hpp) ----
-static gvi_status sample_check(gvi_ctx* ctx, int S) {
-  if (!ctx) return GVI_ERR_ARG;
-  if (S < 0) return fail(ctx, GVI_ERR_ARG, "S < 0");
-  if (ctx->T < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_chain_set first");
-  return GVI_OK;
-}
-
-// Factorisation of Lambda = (D, U) on the context stream: every node's R, GA, GB and the half log-det, left in smp_ws
-// (fa says where).  One launch of sample_factor_kernel per level.  Shared by the samplers and the multi-solve.
-static gvi_status run_sample_factor(gvi_ctx* c, const double* D, const double* U, SampleFactorArgs& fa) {
-  const int T = c->T, n = c->n, L = chain_levels(T);
-  const size_t nn = nn_(c), Tnn = (size_t)T * nn;
-  HIPCK(c, c->smp_ws.ensure((7 * Tnn + T + 1) * 8));
-  double* w = c->smp_ws.d();
-  fa = SampleFactorArgs{};
-  fa.T = T; fa.n = n; fa.L = L; fa.D = D; fa.U = U;
-  double* Db[2] = {w, w + Tnn};
-  double* Cb[2] = {w + 2 * Tnn, w + 3 * Tnn};
-  fa.R = w + 4 * Tnn; fa.GA = w + 5 * Tnn; fa.GB = w + 6 * Tnn; fa.lp = w + 7 * Tnn; fa.hld = fa.lp + T;
-  for (int l = 0; l <= L; ++l) {
-    fa.level = l;
-    fa.Dr = Db[(l + 1) & 1]; fa.Cr = Cb[(l + 1) & 1];
-    fa.Dw = Db[l & 1]; fa.Cw = Cb[l & 1];
-    const int alive = (int)(((int64_t)T + (1 << l) - 1) >> l);
-    hipLaunchKernelGGL(sample_factor_kernel, dim3(alive), dim3(64), 0, c->stream, fa);
-  }
-  HIPCK(c, hipGetLastError());
-  return GVI_OK;
-}
-
-// Factorisation and sweep of S samples into the device buffer X, all on the context stream.
-// Chain arguments of its own: no fused trial precision, no accept predicate, no selected inverse.
-static gvi_status run_sample(gvi_ctx* c, const double* D, const double* U, const double* mu, int S, uint64_t seed, int64_t first,
-                             const double* eps, double* X) {
-  if (c->n > SAMPLE_NMAX) return fail(c, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  if (S == 0) return GVI_OK;
-  const int T = c->T, n = c->n, L = chain_levels(T);
-  SampleFactorArgs fa;
-  GVICK(run_sample_factor(c, D, U, fa));
-  if (!c->sample_sweep) return GVI_OK;
-  SampleSweepArgs sa{};
-  sa.T = T; sa.n = n; sa.L = L; sa.S = S; sa.seed = seed; sa.first = first; sa.eps = eps;
-  sa.R = fa.R; sa.GA = fa.GA; sa.GB = fa.GB; sa.mu = mu; sa.hld = fa.hld; sa.X = X;
-  const size_t rowb = (size_t)T * n * 8;
-  const bool lds = rowb <= (size_t)SAMPLE_LDS_BYTES;
-  const int cap = lds ? std::min<int>(SAMPLE_TILE_MAX, (int)(SAMPLE_LDS_BYTES / rowb)) : SAMPLE_TILE_MAX;
-  sa.tile = std::max(1, std::min(cap, (S + 511) / 512));     // >= 512 workgroups while S allows, then longer tiles
-  const dim3 grid((unsigned)((S + sa.tile - 1) / sa.tile)), blk(SAMPLE_SWEEP_THREADS);
-  const size_t ldsb = lds ? (size_t)sa.tile * rowb : 0;
-  auto go = [&](auto kern) -> gvi_status {
-    if (lds) GVICK(allow_lds(c, (const void*)kern, SAMPLE_LDS_BYTES));
-    hipLaunchKernelGGL(kern, grid, blk, ldsb, c->stream, sa);
-    HIPCK(c, hipGetLastError());
-    return GVI_OK;
-  };
-  if (n <= 4) return lds ? go(sample_sweep_kernel<4, true>) : go(sample_sweep_kernel<4, false>);
-  if (n <= 8) return lds ? go(sample_sweep_kernel<8, true>) : go(sample_sweep_kernel<8, false>);
-  return lds ? go(sample_sweep_kernel<16, true>) : go(sample_sweep_kernel<16, false>);
-}
-
-gvi_status gvi_randn(gvi_ctx* ctx, uint64_t seed, int64_t first, int64_t count, double* out) {
-  if (!ctx) return GVI_ERR_ARG;
-  if (count < 0 || first < 0) return fail(ctx, GVI_ERR_ARG, "count < 0 or first < 0");
-  if (!out) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (count == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  HIPCK(ctx, ctx->smp_io.ensure((size_t)count * 8));
-  const int64_t pairs = ((first + count - 1) >> 1) - (first >> 1) + 1;
-  hipLaunchKernelGGL(randn_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, seed, first, count, ctx->smp_io.d());
-  HIPCK(ctx, hipGetLastError());
-  GVICK(d2h(ctx, out, ctx->smp_io.p, (size_t)count * 8));
-  return sync(ctx);
-}
-
-gvi_status gvi_bt_sample(gvi_ctx* ctx, const double* D, const double* U, const double* mu, int S, uint64_t seed, int64_t first,
-                         const double* eps, double* X) {
-  GVICK(sample_check(ctx, S));
-  if (!D || (!U && ctx->T > 1) || !mu || !X) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
-  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t T = ctx->T, nn = nn_(ctx), Tn = T * ctx->n, SX = (size_t)S * Tn;
-  HIPCK(ctx, ctx->smp_io.ensure((bt_count(ctx) + Tn + (eps ? SX : 0) + SX) * 8));
-  double* dD = ctx->smp_io.d();
-  double* dU = dD + T * nn;
-  double* dmu = dU + (T - 1) * nn;
-  double* dX = dmu + Tn;
-  double* deps = eps ? dX + SX : nullptr;
-  GVICK(h2d(ctx, dD, D, T * nn * 8));
-  if (T > 1) GVICK(h2d(ctx, dU, U, (T - 1) * nn * 8));
-  GVICK(h2d(ctx, dmu, mu, Tn * 8));
-  if (eps) GVICK(h2d(ctx, deps, eps, SX * 8));
-  GVICK(run_sample(ctx, dD, dU, dmu, S, seed, first, deps, dX));
-  GVICK(d2h(ctx, X, dX, SX * 8));
-  return sync(ctx);
-}
-
-static gvi_status ngd_sample_to(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, double* X_dev) {
-  NgdState& g = ctx->ngd;
-  const size_t Tnn = (size_t)ctx->T * nn_(ctx);
-  return run_sample(ctx, g.Lam[g.cur].d(), g.Lam[g.cur].d() + Tnn, g.mu[g.cur].d(), S, seed, first, nullptr, X_dev);
-}
-
-gvi_status gvi_ngd_sample(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, double* X) {
-  GVICK(sample_check(ctx, S));
-  if (!X) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
-  GVICK(ngd_check(ctx));
-  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t SX = (size_t)S * ctx->T * ctx->n;
-  HIPCK(ctx, ctx->smp_io.ensure(SX * 8));
-  GVICK(ngd_sample_to(ctx, S, seed, first, ctx->smp_io.d()));
-  GVICK(d2h(ctx, X, ctx->smp_io.p, SX * 8));
-  return sync(ctx);
-}
-
-gvi_status gvi_ngd_sample_dev(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, double* X_dev) {
-  GVICK(sample_check(ctx, S));
-  if (!X_dev) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
-  GVICK(ngd_check(ctx));
-  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  return ngd_sample_to(ctx, S, seed, first, X_dev);
-}
-
-// logq [S] (device) of the device samples X under N(mu, (D, U)^-1), on the context stream: the chain kernels' half log-det
-// (arguments and a workspace of its own: no mix, no predicate, no back pass) into dh [1], the quadratic forms into dQ [S][T]
-static gvi_status run_logpdf(gvi_ctx* ctx, const double* dD, const double* dU, const double* dmu, int S, const double* dX,
-                             double* dQ, double* dh, double* dl) {
-  const int T = ctx->T, n = ctx->n, NP = chain_padded(n);
-  HIPCK(ctx, ctx->smp_cws.ensure(chain_ws_doubles(T, NP) * 8));
-  HIPCK(ctx, ctx->smp_cwsi.ensure(chain_lp_entries(T) * sizeof(int)));
-  ChainArgs a{};
-  a.T = T; a.n = n; a.need_back = 0;
-  a.D = dD; a.U = dU; a.rhs_scale = 1.0;
-  a.ws = ctx->smp_cws.d(); a.wsi = (int*)ctx->smp_cwsi.p; a.hld = dh;
-  const hipError_t e = chain_launch(n, chain_plan(T, n), a, a, true, false, ctx->stream);
-  if (e == hipErrorInvalidValue) return fail(ctx, GVI_ERR_UNSUPPORTED, "chain kernels: block size / LDS budget");
-  HIPCK(ctx, e);
-  const int64_t items = (int64_t)S * T;
-  hipLaunchKernelGGL(logpdf_quad_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, T, n, S, dD, dU, dmu, dX, dQ);
-  hipLaunchKernelGGL(logpdf_reduce_kernel, dim3(S), dim3(256), 0, ctx->stream, T, n, dQ, dh, dl);
-  HIPCK(ctx, hipGetLastError());
-  return GVI_OK;
-}
-
-gvi_status gvi_bt_logpdf(gvi_ctx* ctx, const double* D, const double* U, const double* mu, int S, const double* X, double* logq) {
-  GVICK(sample_check(ctx, S));
-  if (!D || (!U && ctx->T > 1) || !mu || !X || !logq) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  const int NP = chain_padded(ctx->n);
-  if (!NP) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const int T = ctx->T, n = ctx->n;
-  const size_t nn = nn_(ctx), Tn = (size_t)T * n, SX = (size_t)S * Tn;
-  HIPCK(ctx, ctx->smp_io.ensure((bt_count(ctx) + Tn + SX + (size_t)S * T + S + 1) * 8));
-  double* dD = ctx->smp_io.d();
-  double* dU = dD + (size_t)T * nn;
-  double* dmu = dU + (size_t)(T - 1) * nn;
-  double* dX = dmu + Tn;
-  double* dQ = dX + SX;
-  double* dl = dQ + (size_t)S * T;
-  double* dh = dl + S;
-  GVICK(h2d(ctx, dD, D, (size_t)T * nn * 8));
-  if (T > 1) GVICK(h2d(ctx, dU, U, (size_t)(T - 1) * nn * 8));
-  GVICK(h2d(ctx, dmu, mu, Tn * 8));
-  GVICK(h2d(ctx, dX, X, SX * 8));
-  GVICK(run_logpdf(ctx, dD, dU, dmu, S, dX, dQ, dh, dl));
-  GVICK(d2h(ctx, logq, dl, (size_t)S * 8));
-  return sync(ctx);
-}
-
-
-// ---- multi-right-hand-side solve and block columns of Lambda^-1 (kernels_solve.hpp) ----
-static gvi_status solve_check(gvi_ctx* ctx, int count, const char* what) {
-  if (!ctx) return GVI_ERR_ARG;
-  if (count < 0) return fail(ctx, GVI_ERR_ARG, std::string(what) + " < 0");
-  if (ctx->T < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_chain_set first");
-  return GVI_OK;
-}
-
-static gvi_status solve_check_nodes(gvi_ctx* ctx, int ncols, const int32_t* nodes) {
-  for (int c = 0; c < ncols; ++c)
-    if (nodes[c] < 0 || nodes[c] >= ctx->T) return fail(ctx, GVI_ERR_ARG, "node outside [0, T)");
-  if ((int64_t)ncols * ctx->n > INT32_MAX) return fail(ctx, GVI_ERR_ARG, "ncols * state_dim exceeds 2^31 - 1");
-  return GVI_OK;
-}
-
-// Factorisation (run_sample_factor) and sweep of R right-hand sides into the device buffer X, all on the context stream.
-// B ([R][T][n], device) or, with B null, the unit columns of the device node list (R = ncols n, X = C[ncols][T][n][n]).
-// Like run_sample it builds no ChainArgs.
-static gvi_status run_solve(gvi_ctx* c, const double* D, const double* U, int R, const double* B, const int32_t* nodes, double* X) {
-  if (c->n > SOLVE_NMAX) return fail(c, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  if (R == 0) return GVI_OK;
-  const int T = c->T, n = c->n;
-  SampleFactorArgs fa;
-  GVICK(run_sample_factor(c, D, U, fa));
-  if (!c->sample_sweep) return GVI_OK;
-  SolveSweepArgs sa{};
-  sa.T = T; sa.n = n; sa.L = fa.L; sa.R = R; sa.B = B; sa.nodes = nodes;
-  sa.Rf = fa.R; sa.GA = fa.GA; sa.GB = fa.GB; sa.hld = fa.hld; sa.X = X;
-  const size_t rowb = (size_t)T * n * 8;
-  const bool lds = c->solve_lds && rowb <= (size_t)SOLVE_LDS_BYTES;
-  const int cap = lds ? std::min<int>(SOLVE_TILE_MAX, (int)(SOLVE_LDS_BYTES / rowb)) : SOLVE_TILE_MAX;
-  sa.tile = std::max(1, std::min(cap, (R + 511) / 512));     // >= 512 workgroups while R allows, then longer tiles
-  const dim3 grid((unsigned)((R + sa.tile - 1) / sa.tile)), blk(SOLVE_SWEEP_THREADS);
-  const size_t ldsb = lds ? (size_t)sa.tile * rowb : 0;
-  auto go = [&](auto kern) -> gvi_status {
-    if (lds) GVICK(allow_lds(c, (const void*)kern, SOLVE_LDS_BYTES));
-    hipLaunchKernelGGL(kern, grid, blk, ldsb, c->stream, sa);
-    HIPCK(c, hipGetLastError());
-    return GVI_OK;
-  };
-  if (n <= 4) return lds ? go(solve_sweep_kernel<4, true>) : go(solve_sweep_kernel<4, false>);
-  if (n <= 8) return lds ? go(solve_sweep_kernel<8, true>) : go(solve_sweep_kernel<8, false>);
-  return lds ? go(solve_sweep_kernel<16, true>) : go(solve_sweep_kernel<16, false>);
-}
-
-gvi_status gvi_bt_solve_multi(gvi_ctx* ctx, const double* D, const double* U, int R, const double* B, double* X) {
-  GVICK(solve_check(ctx, R, "R"));
-  if (!D || (!U && ctx->T > 1) || !B || !X) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (ctx->n > SOLVE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  if (R == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t T = ctx->T, nn = nn_(ctx), RX = (size_t)R * T * ctx->n;
-  HIPCK(ctx, ctx->smp_io.ensure((bt_count(ctx) + 2 * RX) * 8));
-  double* dD = ctx->smp_io.d();
-  double* dU = dD + T * nn;
-  double* dB = dU + (T - 1) * nn;
-  double* dX = dB + RX;
-  GVICK(h2d(ctx, dD, D, T * nn * 8));
-  if (T > 1) GVICK(h2d(ctx, dU, U, (T - 1) * nn * 8));
-  GVICK(h2d(ctx, dB, B, RX * 8));
-  GVICK(run_solve(ctx, dD, dU, R, dB, nullptr, dX));
-  GVICK(d2h(ctx, X, dX, RX * 8));
-  return sync(ctx);
-}
-
-// node list to the device (slv_idx), on the context stream
-static gvi_status solve_put_nodes(gvi_ctx* ctx, int ncols, const int32_t* nodes) {
-  HIPCK(ctx, ctx->slv_idx.ensure((size_t)ncols * sizeof(int32_t)));
-  return h2d(ctx, ctx->slv_idx.p, nodes, (size_t)ncols * sizeof(int32_t));
-}
-
-gvi_status gvi_bt_cov_columns(gvi_ctx* ctx, const double* D, const double* U, int ncols, const int32_t* nodes, double* C) {
-  GVICK(solve_check(ctx, ncols, "ncols"));
-  if (!D || (!U && ctx->T > 1) || !nodes || !C) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (ctx->n > SOLVE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  GVICK(solve_check_nodes(ctx, ncols, nodes));
-  if (ncols == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t T = ctx->T, nn = nn_(ctx), CX = (size_t)ncols * T * nn;
-  HIPCK(ctx, ctx->smp_io.ensure((bt_count(ctx) + CX) * 8));
-  double* dD = ctx->smp_io.d();
-  double* dU = dD + T * nn;
-  double* dC = dU + (T - 1) * nn;
-  GVICK(h2d(ctx, dD, D, T * nn * 8));
-  if (T > 1) GVICK(h2d(ctx, dU, U, (T - 1) * nn * 8));
-  GVICK(solve_put_nodes(ctx, ncols, nodes));
-  GVICK(run_solve(ctx, dD, dU, ncols * ctx->n, nullptr, (const int32_t*)ctx->slv_idx.p, dC));
-  GVICK(d2h(ctx, C, dC, CX * 8));
-  return sync(ctx);
-}
-
-static gvi_status ngd_cov_columns_to(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C_dev) {
-  NgdState& g = ctx->ngd;
-  const size_t Tnn = (size_t)ctx->T * nn_(ctx);
-  GVICK(solve_put_nodes(ctx, ncols, nodes));
-  return run_solve(ctx, g.Lam[g.cur].d(), g.Lam[g.cur].d() + Tnn, ncols * ctx->n, nullptr, (const int32_t*)ctx->slv_idx.p, C_dev);
-}
-
-gvi_status gvi_ngd_cov_columns(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C) {
-  GVICK(solve_check(ctx, ncols, "ncols"));
-  if (!nodes || !C) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  GVICK(ngd_check(ctx));
-  if (ctx->n > SOLVE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  GVICK(solve_check_nodes(ctx, ncols, nodes));
-  if (ncols == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t CX = (size_t)ncols * ctx->T * nn_(ctx);
-  HIPCK(ctx, ctx->smp_io.ensure(CX * 8));
-  GVICK(ngd_cov_columns_to(ctx, ncols, nodes, ctx->smp_io.d()));
-  GVICK(d2h(ctx, C, ctx->smp_io.p, CX * 8));
-  return sync(ctx);
-}
-
-gvi_status gvi_ngd_cov_columns_dev(gvi_ctx* ctx, int ncols, const int32_t* nodes, double* C_dev) {
-  GVICK(solve_check(ctx, ncols, "ncols"));
-  if (!nodes || !C_dev) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  GVICK(ngd_check(ctx));
-  if (ctx->n > SOLVE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  GVICK(solve_check_nodes(ctx, ncols, nodes));
-  if (ncols == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  return ngd_cov_columns_to(ctx, ncols, nodes, C_dev);
-}
-
-// ---- dense-time posterior: moments and samples between the support states (kernels_interp.hpp) ----
-gvi_status gvi_interp_set(gvi_ctx* ctx, int Q, const int32_t* idx, const double* A, const double* B, const double* c,
-                          const double* Qt) {
-  if (!ctx) return GVI_ERR_ARG;
-  if (Q < 0) return fail(ctx, GVI_ERR_ARG, "Q < 0");
-  if (ctx->T < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_chain_set first");
-  if (Q > 0 && (!idx || !A || !B)) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (ctx->n > INTERP_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  for (int q = 0; q < Q; ++q)
-    if (idx[q] < 0 || idx[q] > ctx->T - 2) return fail(ctx, GVI_ERR_ARG, "idx outside [0, T - 2]");
-  if ((int64_t)Q * ctx->n > INT32_MAX) return fail(ctx, GVI_ERR_ARG, "Q * state_dim exceeds 2^31 - 1");
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  GVICK(sync(ctx));                       // a queued _dev call may still read the set being replaced
-  ctx->itp_Q = 0; ctx->itp_nbad = 0; ctx->itp_noise = false;
-  if (Q == 0) return GVI_OK;
-  const size_t n = ctx->n, nn = n * n, Qnn = (size_t)Q * nn, Qn = (size_t)Q * n;
-  DevMem raw;                             // A | B | c: only the packed form is kept
-  HIPCK(ctx, raw.ensure((2 * Qnn + Qn) * 8));
-  HIPCK(ctx, ctx->itp_ops.ensure(Qn * (3 * n + 1) * 8));
-  HIPCK(ctx, ctx->itp_idx.ensure((size_t)Q * sizeof(int32_t)));
-  HIPCK(ctx, ctx->itp_bad.ensure((size_t)Q * sizeof(int32_t)));
-  if (Qt) HIPCK(ctx, ctx->itp_qt.ensure(Qnn * 8));
-  double* dA = raw.d();
-  double* dB = dA + Qnn;
-  double* dc = dB + Qnn;
-  GVICK(h2d(ctx, dA, A, Qnn * 8));
-  GVICK(h2d(ctx, dB, B, Qnn * 8));
-  if (c) GVICK(h2d(ctx, dc, c, Qn * 8));
-  if (Qt) GVICK(h2d(ctx, ctx->itp_qt.p, Qt, Qnn * 8));
-  GVICK(h2d(ctx, ctx->itp_idx.p, idx, (size_t)Q * sizeof(int32_t)));
-  InterpPrepArgs pa{};
-  pa.Q = Q; pa.n = (int)n; pa.A = dA; pa.B = dB; pa.c = c ? dc : nullptr; pa.Qt = Qt ? ctx->itp_qt.d() : nullptr;
-  pa.ops = ctx->itp_ops.d(); pa.bad = ctx->itp_bad.i();
-  hipLaunchKernelGGL(interp_prepare_kernel, dim3(Q), dim3(64), 0, ctx->stream, pa);
-  HIPCK(ctx, hipGetLastError());
-  std::vector<int32_t> bad(Q);
-  GVICK(d2h(ctx, bad.data(), ctx->itp_bad.p, (size_t)Q * sizeof(int32_t)));
-  GVICK(sync(ctx));                       // raw is released on return
-  int nbad = 0;
-  for (int q = 0; q < Q; ++q) nbad += bad[q] != 0;
-  ctx->itp_Q = Q; ctx->itp_nbad = nbad; ctx->itp_noise = Qt != nullptr;
-  return GVI_OK;
-}
-
-gvi_status gvi_interp_info(gvi_ctx* ctx, int* Q, int* nbad) {
-  if (!ctx) return GVI_ERR_ARG;
-  if (Q) *Q = ctx->itp_Q;
-  if (nbad) *nbad = ctx->itp_nbad;
-  return GVI_OK;
-}
-
-static gvi_status interp_check(gvi_ctx* ctx) {
-  if (!ctx) return GVI_ERR_ARG;
-  if (ctx->T < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_chain_set first");
-  return GVI_OK;
-}
-
-static gvi_status interp_have_set(gvi_ctx* ctx) {
-  if (ctx->itp_Q < 1) return fail(ctx, GVI_ERR_STATE, "call gvi_interp_set first");
-  return GVI_OK;
-}
-
-// mean_q / cov_q (device, either may be null) of the prepared set from device (mu, SigD, SigU), on the context stream
-static gvi_status run_interp_moments(gvi_ctx* c, const double* mu, const double* SigD, const double* SigU, double* mean_q,
-                                     double* cov_q) {
-  InterpMomArgs ma{};
-  ma.Q = c->itp_Q; ma.n = c->n; ma.idx = c->itp_idx.i(); ma.ops = c->itp_ops.d();
-  ma.Qt = c->itp_noise ? c->itp_qt.d() : nullptr;
-  ma.mu = mu; ma.SigD = SigD; ma.SigU = SigU; ma.mean = mean_q; ma.cov = cov_q;
-  hipLaunchKernelGGL(interp_moments_kernel, dim3(c->itp_Q), dim3(64), 0, c->stream, ma);
-  HIPCK(c, hipGetLastError());
-  return GVI_OK;
-}
-
-// samples per workgroup of the sweep: a power of two <= INTERP_TILE_MAX, grown only while the grid keeps INTERP_TARGET_BLOCKS
-static int interp_tile(int S, int Q, int n) {
-  const int64_t qblocks = ((int64_t)Q + INTERP_SWEEP_WAVES * (64 / n) - 1) / (INTERP_SWEEP_WAVES * (64 / n));
-  int tile = 1;
-  while (tile < INTERP_TILE_MAX && qblocks * ((S + 2 * tile - 1) / (2 * tile)) >= INTERP_TARGET_BLOCKS) tile *= 2;
-  return tile;
-}
-
-// Xq [S][Q][n] (device) from X [S][T][n] (device), on the context stream
-static gvi_status run_interp_sweep(gvi_ctx* c, int S, const double* X, uint64_t noise_seed, int64_t first, const double* eps,
-                                   double* Xq) {
-  const int n = c->n, Q = c->itp_Q;
-  InterpSweepArgs sa{};
-  sa.T = c->T; sa.n = n; sa.Q = Q; sa.S = S; sa.tile = interp_tile(S, Q, n);
-  sa.noise = c->itp_noise ? 1 : 0; sa.noise_seed = noise_seed; sa.first = first;
-  sa.idx = c->itp_idx.i(); sa.ops = c->itp_ops.d(); sa.bad = c->itp_bad.i(); sa.eps = eps; sa.X = X; sa.Xq = Xq;
-  const int qpb = INTERP_SWEEP_WAVES * (64 / n);
-  const dim3 grid((unsigned)((Q + qpb - 1) / qpb), (unsigned)((S + sa.tile - 1) / sa.tile)), blk(INTERP_SWEEP_WAVES * 64);
-  if (grid.y > 65535u) return fail(c, GVI_ERR_ARG, "S exceeds 65535 sample tiles");
-  if (n <= 4) hipLaunchKernelGGL(interp_sweep_kernel<4>, grid, blk, 0, c->stream, sa);
-  else if (n <= 8) hipLaunchKernelGGL(interp_sweep_kernel<8>, grid, blk, 0, c->stream, sa);
-  else hipLaunchKernelGGL(interp_sweep_kernel<16>, grid, blk, 0, c->stream, sa);
-  HIPCK(c, hipGetLastError());
-  return GVI_OK;
-}
-
-gvi_status gvi_bt_interp(gvi_ctx* ctx, const double* mu, const double* SigD, const double* SigU, double* mean_q, double* cov_q) {
-  GVICK(interp_check(ctx));
-  if (!mu || !SigD || !SigU || !mean_q || !cov_q) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  GVICK(interp_have_set(ctx));
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t T = ctx->T, n = ctx->n, nn = n * n, Q = ctx->itp_Q;
-  HIPCK(ctx, ctx->smp_io.ensure((T * n + (2 * T - 1) * nn + Q * n + Q * nn) * 8));
-  double* dmu = ctx->smp_io.d();
-  double* dSD = dmu + T * n;
-  double* dSU = dSD + T * nn;
-  double* dm = dSU + (T - 1) * nn;
-  double* dc = dm + Q * n;
-  GVICK(h2d(ctx, dmu, mu, T * n * 8));
-  GVICK(h2d(ctx, dSD, SigD, T * nn * 8));
-  GVICK(h2d(ctx, dSU, SigU, (T - 1) * nn * 8));
-  GVICK(run_interp_moments(ctx, dmu, dSD, dSU, dm, dc));
-  GVICK(d2h(ctx, mean_q, dm, Q * n * 8));
-  GVICK(d2h(ctx, cov_q, dc, Q * nn * 8));
-  return sync(ctx);
-}
-
-// the resident marginals never leave HBM; no ChainArgs is built and nothing the iteration reads is written
-static gvi_status ngd_interp_to(gvi_ctx* ctx, double* mean_dev, double* cov_dev) {
-  NgdState& g = ctx->ngd;
-  const size_t Tnn = (size_t)ctx->T * nn_(ctx);
-  return run_interp_moments(ctx, g.mu[g.cur].d(), g.Sig[g.cur].d(), g.Sig[g.cur].d() + Tnn, mean_dev, cov_dev);
-}
-
-gvi_status gvi_ngd_interp(gvi_ctx* ctx, double* mean_q, double* cov_q) {
-  GVICK(interp_check(ctx));
-  if (!mean_q || !cov_q) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  GVICK(ngd_check(ctx));
-  GVICK(interp_have_set(ctx));
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t n = ctx->n, Q = ctx->itp_Q;
-  HIPCK(ctx, ctx->smp_io.ensure((Q * n + Q * n * n) * 8));
-  double* dm = ctx->smp_io.d();
-  double* dc = dm + Q * n;
-  GVICK(ngd_interp_to(ctx, dm, dc));
-  GVICK(d2h(ctx, mean_q, dm, Q * n * 8));
-  GVICK(d2h(ctx, cov_q, dc, Q * n * n * 8));
-  return sync(ctx);
-}
-
-gvi_status gvi_ngd_interp_dev(gvi_ctx* ctx, double* mean_q_dev, double* cov_q_dev) {
-  GVICK(interp_check(ctx));
-  if (!mean_q_dev || !cov_q_dev) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  GVICK(ngd_check(ctx));
-  GVICK(interp_have_set(ctx));
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  return ngd_interp_to(ctx, mean_q_dev, cov_q_dev);
-}
-
-gvi_status gvi_bt_interp_samples(gvi_ctx* ctx, int S, const double* X, uint64_t noise_seed, int64_t first, const double* eps,
-                                 double* Xq) {
-  GVICK(sample_check(ctx, S));
-  if (!X || !Xq) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
-  GVICK(interp_have_set(ctx));
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t SX = (size_t)S * ctx->T * ctx->n, SQ = (size_t)S * ctx->itp_Q * ctx->n;
-  HIPCK(ctx, ctx->smp_io.ensure((SX + SQ + (eps ? SQ : 0)) * 8));
-  double* dX = ctx->smp_io.d();
-  double* dXq = dX + SX;
-  double* deps = eps ? dXq + SQ : nullptr;
-  GVICK(h2d(ctx, dX, X, SX * 8));
-  if (eps) GVICK(h2d(ctx, deps, eps, SQ * 8));
-  GVICK(run_interp_sweep(ctx, S, dX, noise_seed, first, deps, dXq));
-  GVICK(d2h(ctx, Xq, dXq, SQ * 8));
-  return sync(ctx);
-}
-
-static gvi_status ngd_sample_interp_check(gvi_ctx* ctx, int S, int64_t first, const void* Xq) {
-  GVICK(sample_check(ctx, S));
-  if (!Xq) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
-  GVICK(ngd_check(ctx));
-  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  return interp_have_set(ctx);
-}
-
-gvi_status gvi_ngd_sample_interp(gvi_ctx* ctx, int S, uint64_t seed, uint64_t noise_seed, int64_t first, double* X, double* Xq) {
-  GVICK(ngd_sample_interp_check(ctx, S, first, Xq));
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t SX = (size_t)S * ctx->T * ctx->n, SQ = (size_t)S * ctx->itp_Q * ctx->n;
-  HIPCK(ctx, ctx->smp_io.ensure((SX + SQ) * 8));
-  double* dX = ctx->smp_io.d();
-  double* dXq = dX + SX;
-  GVICK(ngd_sample_to(ctx, S, seed, first, dX));
-  if (!ctx->sample_sweep) return sync(ctx);
-  GVICK(run_interp_sweep(ctx, S, dX, noise_seed, first, nullptr, dXq));
-  if (X) GVICK(d2h(ctx, X, dX, SX * 8));
-  GVICK(d2h(ctx, Xq, dXq, SQ * 8));
-  return sync(ctx);
-}
-
-gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_t noise_seed, int64_t first, double* X_dev,
-                                     double* Xq_dev) {
-  GVICK(ngd_sample_interp_check(ctx, S, first, Xq_dev));
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  double* dX = X_dev;
-  if (!dX) {                              // the support samples are not asked for: they stay in the staging buffer
-    HIPCK(ctx, ctx->smp_io.ensure((size_t)S * ctx->T * ctx->n * 8));
-    dX = ctx->smp_io.d();
-  }
-  GVICK(ngd_sample_to(ctx, S, seed, first, dX));
-  if (!ctx->sample_sweep) return GVI_OK;
-  return run_interp_sweep(ctx, S, dX, noise_seed, first, nullptr, Xq_dev);
-}
-
-// ---- costs of sampled trajectories (kernels_sample_cost.hpp) ----
-static bool hinge_kind(int kind) { return kind >= KIND_HINGE_SDF_2D && kind <= KIND_HINGE_SDF_3D_ARM; }
-
-static gvi_status scost_check_set(gvi_ctx* ctx, const FactorSet& s, bool clearance) {
-  if (s.kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_UNSUPPORTED, "a PSI_HOST_CALLBACK set has no device psi");
-  if (clearance && !hinge_kind(s.kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "clearance needs a hinge-on-SDF set");
-  if (scost_sumsq(s.kind) && s.d > SCOST_DMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
-  if (s.kind == KIND_HINGE_SDF_3D_ARM && !s.arm.p)
-    return fail(ctx, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");
-  if (hinge_kind(s.kind) && s.sdf_rows == 0)
-    return fail(ctx, GVI_ERR_STATE, "HINGE_SDF set without a grid: call gvi_factors_set_sdf2d / gvi_factors_set_sdf3d");
-  return GVI_OK;
-}
-
-// every set of the context can be evaluated on the device (gvi_sample_costs / gvi_ngd_sample_costs)
-static gvi_status scost_check_all(gvi_ctx* ctx, int clearance_set) {
-  if ((int)ctx->sets.size() > MAX_FSETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
-  for (int i = 0; i < (int)ctx->sets.size(); ++i) GVICK(scost_check_set(ctx, *ctx->sets[i], i == clearance_set));
-  return GVI_OK;
-}
-
-static int64_t scost_total_factors(const gvi_ctx* ctx) {
-  int64_t K = 0;
-  for (auto& s : ctx->sets) K += s->K;
-  return K;
-}
-
-// ONE launch over the sets [lo, hi): cost (device, or null) is [S][ld] with the sets' columns side by side from column 0;
-// clr (device, or null) is [S][ld_clr] of set clr_set.  X is a device buffer; everything on the context stream.
-static gvi_status run_sample_cost(gvi_ctx* c, int lo, int hi, int S, const double* X, double* cost, int64_t ld, int clr_set,
-                                  double* clr, int64_t ld_clr) {
-  SampleCostList L{};
-  L.T = c->T; L.n = c->n; L.S = S; L.X = X;
-  int64_t nb = 0, koff = 0;
-  int dmax = 0;
-  for (int i = lo; i < hi; ++i) {
-    FactorSet& s = *c->sets[i];
-    double* cp = cost ? cost + koff : nullptr;
-    double* kp = i == clr_set ? clr : nullptr;
-    koff += s.K;
-    if (s.K == 0 || (!cp && !kp)) continue;
-    const int j = L.nsets++;
-    L.f[j] = s.dev(); L.start[j] = s.dstart.i();
-    L.cost[j] = cp; L.clr[j] = kp; L.ld_cost[j] = ld; L.ld_clr[j] = ld_clr;
-    L.boff[j] = (int)nb;
-    if (scost_sumsq(s.kind)) {
-      // tiles of 4 G factors; the samples are cut into chunks only as far as the grid needs them (a block loads its rows of A once)
-      const int F = SCOST_WAVES * (64 / scost_group(s.m));
-      const int ft = (s.K + F - 1) / F;
-      const int nsc = std::max(1, std::min(S, (SCOST_TARGET_BLOCKS + ft - 1) / ft));
-      L.ftiles[j] = ft;
-      L.schunk[j] = (S + nsc - 1) / nsc;
-      nb += (int64_t)ft * ((S + L.schunk[j] - 1) / L.schunk[j]);
-      dmax = std::max(dmax, s.d);
-    } else {
-      nb += ((int64_t)s.K * S + SCOST_THREADS - 1) / SCOST_THREADS;
-    }
-    if (nb > 0x7fffffffLL) return fail(c, GVI_ERR_ARG, "S * K exceeds the grid");
-  }
-  L.boff[L.nsets] = (int)nb;
-  if (L.nsets == 0) return GVI_OK;
-  const dim3 grid((unsigned)nb), blk(SCOST_THREADS);
-  if (dmax <= 4) hipLaunchKernelGGL(sample_cost_kernel<4>, grid, blk, 0, c->stream, L);
-  else if (dmax <= 8) hipLaunchKernelGGL(sample_cost_kernel<8>, grid, blk, 0, c->stream, L);
-  else if (dmax <= 12) hipLaunchKernelGGL(sample_cost_kernel<12>, grid, blk, 0, c->stream, L);
-  else if (dmax <= 16) hipLaunchKernelGGL(sample_cost_kernel<16>, grid, blk, 0, c->stream, L);
-  else if (dmax <= 24) hipLaunchKernelGGL(sample_cost_kernel<24>, grid, blk, 0, c->stream, L);
-  else hipLaunchKernelGGL(sample_cost_kernel<32>, grid, blk, 0, c->stream, L);
-  HIPCK(c, hipGetLastError());
-  return GVI_OK;
-}
-
-// J [S] and, for clr_set >= 0 with clr_min != null, clr_min [S] (device buffers) of the device samples X: the launch over
-// every set into the matrices of scost_ws (behind `head` doubles the caller keeps for itself), then the ordered reduction
-static gvi_status run_sample_costs_total(gvi_ctx* c, int S, const double* X, double* J, int clr_set, double* clr_min, size_t head) {
-  const int64_t Kt = scost_total_factors(c), Kc = (clr_set >= 0 && clr_min) ? c->sets[clr_set]->K : 0;
-  double* cm = c->scost_ws.d() + head;
-  double* km = cm + (size_t)S * Kt;
-  const bool want_clr = clr_set >= 0 && clr_min;
-  GVICK(run_sample_cost(c, 0, (int)c->sets.size(), S, X, cm, Kt, want_clr ? clr_set : -1, km, Kc));
-  SampleCostReduceArgs ra{};
-  ra.Kt = (int)Kt; ra.Kc = (int)Kc; ra.cost = cm; ra.clr = want_clr ? km : nullptr; ra.J = J; ra.clr_min = clr_min;
-  hipLaunchKernelGGL(sample_cost_reduce_kernel, dim3(S), dim3(256), 0, c->stream, ra);
-  HIPCK(c, hipGetLastError());
-  return GVI_OK;
-}
-
-static size_t scost_total_doubles(const gvi_ctx* c, int S, int clr_set) {
-  return (size_t)S * (size_t)(scost_total_factors(c) + (clr_set >= 0 ? c->sets[clr_set]->K : 0));
-}
-
-static gvi_status scost_set_check(gvi_ctx* ctx, int set_id, int S, const void* X, const void* out, bool clearance) {
-  GVICK(sample_check(ctx, S));
-  if (!X || !out) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (set_id < 0 || set_id >= (int)ctx->sets.size()) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  return scost_check_set(ctx, *ctx->sets[set_id], clearance);
-}
-
-// cost / clearance matrix [S][K] of one set from host samples
-static gvi_status sample_set_matrix(gvi_ctx* ctx, int set_id, int S, const double* X, double* out, bool clearance) {
-  GVICK(scost_set_check(ctx, set_id, S, X, out, clearance));
-  const size_t K = ctx->sets[set_id]->K, SX = (size_t)S * ctx->T * ctx->n;
-  if (S == 0 || K == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  HIPCK(ctx, ctx->smp_io.ensure(SX * 8));
-  HIPCK(ctx, ctx->scost_ws.ensure((size_t)S * K * 8));
-  GVICK(h2d(ctx, ctx->smp_io.p, X, SX * 8));
-  double* dm = ctx->scost_ws.d();
-  GVICK(run_sample_cost(ctx, set_id, set_id + 1, S, ctx->smp_io.d(), clearance ? nullptr : dm, (int64_t)K, clearance ? set_id : -1,
-                        dm, (int64_t)K));
-  GVICK(d2h(ctx, out, dm, (size_t)S * K * 8));
-  return sync(ctx);
-}
-
-gvi_status gvi_sample_factor_costs(gvi_ctx* ctx, int set_id, int S, const double* X, double* cost) {
-  return sample_set_matrix(ctx, set_id, S, X, cost, false);
-}
-
-gvi_status gvi_sample_clearance(gvi_ctx* ctx, int set_id, int S, const double* X, double* clr) {
-  return sample_set_matrix(ctx, set_id, S, X, clr, true);
-}
-
-gvi_status gvi_sample_clearance_dev(gvi_ctx* ctx, int set_id, int S, const double* X_dev, double* clr_dev) {
-  GVICK(scost_set_check(ctx, set_id, S, X_dev, clr_dev, true));
-  const int64_t K = ctx->sets[set_id]->K;
-  if (S == 0 || K == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  return run_sample_cost(ctx, set_id, set_id + 1, S, X_dev, nullptr, K, set_id, clr_dev, K);
-}
-
-gvi_status gvi_sample_costs(gvi_ctx* ctx, int S, const double* X, double* J) {
-  GVICK(sample_check(ctx, S));
-  if (!X || !J) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  GVICK(scost_check_all(ctx, -1));
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t SX = (size_t)S * ctx->T * ctx->n;
-  HIPCK(ctx, ctx->smp_io.ensure(SX * 8));
-  HIPCK(ctx, ctx->scost_ws.ensure((S + scost_total_doubles(ctx, S, -1)) * 8));
-  GVICK(h2d(ctx, ctx->smp_io.p, X, SX * 8));
-  double* dJ = ctx->scost_ws.d();
-  GVICK(run_sample_costs_total(ctx, S, ctx->smp_io.d(), dJ, -1, nullptr, (size_t)S));
-  GVICK(d2h(ctx, J, dJ, (size_t)S * 8));
-  return sync(ctx);
-}
-
-gvi_status gvi_sample_costs_dev(gvi_ctx* ctx, int S, const double* X_dev, double* J_dev) {
-  GVICK(sample_check(ctx, S));
-  if (!X_dev || !J_dev) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  GVICK(scost_check_all(ctx, -1));
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  HIPCK(ctx, ctx->scost_ws.ensure(scost_total_doubles(ctx, S, -1) * 8));
-  return run_sample_costs_total(ctx, S, X_dev, J_dev, -1, nullptr, 0);
-}
-
-static gvi_status ngd_sample_costs_check(gvi_ctx* ctx, int S, int64_t first, int clearance_set, const void* J) {
-  GVICK(sample_check(ctx, S));
-  if (!J) return fail(ctx, GVI_ERR_ARG, "NULL argument");
-  if (first < 0) return fail(ctx, GVI_ERR_ARG, "first < 0");
-  if (clearance_set >= (int)ctx->sets.size()) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  GVICK(ngd_check(ctx));
-  if (ctx->n > SAMPLE_NMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  return scost_check_all(ctx, clearance_set < 0 ? -1 : clearance_set);
-}
-
-// sampler -> cost launch + reduction -> log-density, all on the context stream and on device buffers; the cost matrices and
-// the log-density's scratch sit in scost_ws behind `head` doubles
-static gvi_status ngd_sample_costs_to(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, int clr_set, double* dX, double* dJ,
-                                      double* dlogq, double* dclr, size_t head) {
-  NgdState& g = ctx->ngd;
-  GVICK(ngd_sample_to(ctx, S, seed, first, dX));
-  if (!ctx->sample_sweep) return GVI_OK;
-  GVICK(run_sample_costs_total(ctx, S, dX, dJ, clr_set, dclr, head));
-  if (!dlogq) return GVI_OK;
-  double* dQ = ctx->scost_ws.d() + head + scost_total_doubles(ctx, S, clr_set);
-  double* dh = dQ + (size_t)S * ctx->T;
-  const double* Lam = g.Lam[g.cur].d();
-  return run_logpdf(ctx, Lam, Lam + (size_t)ctx->T * nn_(ctx), g.mu[g.cur].d(), S, dX, dQ, dh, dlogq);
-}
-
-gvi_status gvi_ngd_sample_costs(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, int clearance_set, double* X, double* J,
-                                double* logq, double* clr_min) {
-  GVICK(ngd_sample_costs_check(ctx, S, first, clearance_set, J));
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const int cs = (clearance_set >= 0 && clr_min) ? clearance_set : -1;
-  const size_t SX = (size_t)S * ctx->T * ctx->n, head = 3 * (size_t)S;
-  HIPCK(ctx, ctx->smp_io.ensure(SX * 8));
-  HIPCK(ctx, ctx->scost_ws.ensure((head + scost_total_doubles(ctx, S, cs) + (size_t)S * ctx->T + 1) * 8));
-  double* dJ = ctx->scost_ws.d();
-  double* dl = dJ + S;
-  double* dc = dl + S;
-  GVICK(ngd_sample_costs_to(ctx, S, seed, first, cs, ctx->smp_io.d(), dJ, logq ? dl : nullptr, cs >= 0 ? dc : nullptr, head));
-  if (!ctx->sample_sweep) return sync(ctx);
-  if (X) GVICK(d2h(ctx, X, ctx->smp_io.p, SX * 8));
-  GVICK(d2h(ctx, J, dJ, (size_t)S * 8));
-  if (logq) GVICK(d2h(ctx, logq, dl, (size_t)S * 8));
-  if (cs >= 0) GVICK(d2h(ctx, clr_min, dc, (size_t)S * 8));
-  return sync(ctx);
-}
-
-gvi_status gvi_ngd_sample_costs_dev(gvi_ctx* ctx, int S, uint64_t seed, int64_t first, int clearance_set, double* X_dev,
-                                    double* J_dev, double* logq_dev, double* clr_min_dev) {
-  GVICK(ngd_sample_costs_check(ctx, S, first, clearance_set, J_dev));
-  if (S == 0) return GVI_OK;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const int cs = (clearance_set >= 0 && clr_min_dev) ? clearance_set : -1;
-  double* dX = X_dev;
-  if (!dX) {                              // the samples are not asked for: they stay in the staging buffer
-    HIPCK(ctx, ctx->smp_io.ensure((size_t)S * ctx->T * ctx->n * 8));
-    dX = ctx->smp_io.d();
-  }
-  HIPCK(ctx, ctx->scost_ws.ensure((scost_total_doubles(ctx, S, cs) + (size_t)S * ctx->T + 1) * 8));
-  return ngd_sample_costs_to(ctx, S, seed, first, cs, dX, J_dev, logq_dev, cs >= 0 ? clr_min_dev : nullptr, 0);
-}
-
 }  // extern "C"
+
+// posterior queries: samples and log-density, many right-hand sides, dense-time posterior, costs of sampled trajectories
+// (textually part of this translation unit: the kernel headers define __global__ functions and cannot be included twice)
+#include "posterior_host.inc"
