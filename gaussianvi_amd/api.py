@@ -11,6 +11,7 @@ from . import _lib
 
 PSI_RANGE_1D, PSI_QUAD_PRIOR, PSI_FIXED_PRIOR, PSI_HOST_CALLBACK, PSI_HINGE_SDF_2D = 0, 1, 2, 3, 4
 PSI_HINGE_SDF_2D_BODY, PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM = 5, 6, 7
+PSI_HINGE_SDF_2D_SEG, PSI_HINGE_SDF_3D_SEG = 8, 9
 RULE_NGD, RULE_PROX_JKO = 0, 1
 GVI_F64, GVI_F32 = 0, 1
 
@@ -669,9 +670,9 @@ def context_for_chain(chain, device=0, specs=None, tables=None):
     for spec in (chain["specs"] if specs is None else specs):
         ids.append(ctx.factors_add(spec["d"], spec["p"], spec["start"], spec["kind"], spec["params"],
                                    spec["temperature"], table=(tables or {}).get((spec["d"], spec["p"]))))
-        if spec["kind"] in (PSI_HINGE_SDF_2D, PSI_HINGE_SDF_2D_BODY):
+        if spec["kind"] in (PSI_HINGE_SDF_2D, PSI_HINGE_SDF_2D_BODY, PSI_HINGE_SDF_2D_SEG):
             ctx.factors_set_sdf2d(ids[-1], spec["sdf_origin"], spec["sdf_cell"], spec["sdf_field"])
-        if spec["kind"] in (PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM):
+        if spec["kind"] in (PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM, PSI_HINGE_SDF_3D_SEG):
             ctx.factors_set_sdf3d(ids[-1], spec["sdf_origin"], spec["sdf_cell"], spec["sdf_field"])
         if spec["kind"] == PSI_HINGE_SDF_3D_ARM:
             ctx.factors_set_arm(ids[-1], spec["arm"])

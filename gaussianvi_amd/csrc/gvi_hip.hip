@@ -95,6 +95,7 @@ struct FactorSet {
   bool use_orbit = false;
   bool use_opsi = false;              // sign-orbit kernel for the non-polynomial psi kinds (kernels_orbit_psi.hpp)
   int arm_ndof = 0;
+  int seg_J = 0;                      // HINGE_SDF_*_SEG: check points per factor
   bool fused_pair = false;            // last resident launch went out fused with the other set
   bool closed_form = false;           // NGDFactorizedLinear route (no sigma points)
   bool chain_structured = false;      // start[k] == k (factor k on state k / states k, k + 1): assemble-on-load needs no CSR
@@ -127,7 +128,7 @@ struct FactorSet {
     f.A = A.d(); f.b = b.d(); f.sgn = sgn.d(); f.raw = raw.d(); f.raw_stride = raw_stride;
     f.temperature = unit_temperature ? ones.d() : temperature.d();
     f.S = S.d(); f.Sinv = Sinv.d(); f.Lam = Lam.d(); f.H = H.d(); f.Hq = Hq.p ? Hq.d() : nullptr; f.u0 = u0.d();
-    f.Vws = nullptr; f.warm = 0; f.jko_h = 0.0; f.jtol = jtol;
+    f.Vws = nullptr; f.warm = 0; f.seg_J = seg_J; f.jko_h = 0.0; f.jtol = jtol;
     // Cholesky factor instead of the symmetric root: sum-of-squares psi on a generated table of degree >= 3 (exact
     // quadrature -- kernels_factor.hpp, prep_chol_body), the instantiated dimensions, and not when the caller is going
     // to look at the sigma points themselves (force_sym: gvi_expand / gvi_moments_from_psi) or runs the JKO map
@@ -508,12 +509,16 @@ FactorSet* get_set(gvi_ctx* c, int id) {
   return c->sets[id].get();
 }
 
+static_assert(SEG_MAX_J == GVI_SEG_MAX_J, "the device's and the header's limit on check points per segment factor");
+
 // which (d, m) pairs have a register-kernel instantiation
 bool reg_supported(int kind, int d, int m) {
   if (kind == KIND_RANGE_1D) return d == 1;
   if (kind == KIND_HINGE_SDF_2D) return d == 2 || d == 4 || d == 6;
   if (kind == KIND_HINGE_SDF_2D_BODY) return d == 3 || d == 6;
   if (kind == KIND_HINGE_SDF_3D) return d == 3 || d == 6;
+  if (kind == KIND_HINGE_SDF_2D_SEG) return d == 4 || d == 8 || d == 12;
+  if (kind == KIND_HINGE_SDF_3D_SEG) return d == 6;   // d = 12: 256 VGPRs + 18 AGPR copies under launch_bounds(256) -> generic kernel
   if (kind == KIND_QUAD_PRIOR) return (d == 2 && m == 1) || (d == 4 && m == 2) || (d == 6 && m == 3) ||
                                       (d == 8 && m == 4) || (d == 12 && m == 6);
   if (kind == KIND_FIXED_PRIOR) return d == m && (d == 1 || d == 2 || d == 3 || d == 4 || d == 6 || d == 8 || d == 12);
@@ -621,6 +626,16 @@ bool dispatch_reg(const FactorSet& s, const MomArgs& a, dim3 grid, hipStream_t s
   if (s.kind == KIND_HINGE_SDF_3D) {
     if (d == 3) { launch_reg<3, PsiHingeSdf<3, KIND_HINGE_SDF_3D>>(a, grid, st); return true; }
     if (d == 6) { launch_reg<6, PsiHingeSdf<6, KIND_HINGE_SDF_3D>>(a, grid, st); return true; }
+  }
+  if (s.kind == KIND_HINGE_SDF_2D_SEG) {
+    switch (d) {
+      case 4: launch_reg<4, PsiHingeSeg<4, 2>>(a, grid, st); return true;
+      case 8: launch_reg<8, PsiHingeSeg<8, 2>>(a, grid, st); return true;
+      case 12: launch_reg<12, PsiHingeSeg<12, 2>>(a, grid, st); return true;
+    }
+  }
+  if (s.kind == KIND_HINGE_SDF_3D_SEG) {
+    if (d == 6) { launch_reg<6, PsiHingeSeg<6, 3>>(a, grid, st); return true; }
   }
   if (s.kind == KIND_QUAD_PRIOR) {
     switch (d) {
@@ -886,7 +901,7 @@ gvi_status run_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double*
   if (s.K == 0) { s.nchunk = 1; s.chunk = s.table->Np; s.use_reg = s.use_split = s.use_orbit = s.use_opsi = false; return GVI_OK; }   // empty shard
   if (s.kind == KIND_HINGE_SDF_3D_ARM && !psi_ext && !s.arm.p)
     return fail(c, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");
-  if (s.kind >= KIND_HINGE_SDF_2D && !psi_ext && s.sdf_rows == 0)
+  if (s.kind >= KIND_HINGE_SDF_2D && s.kind <= KIND_HINGE_SDF_3D_SEG && !psi_ext && s.sdf_rows == 0)
     return fail(c, GVI_ERR_STATE, "HINGE_SDF set without a grid: call gvi_factors_set_sdf2d / gvi_factors_set_sdf3d");
   bool reg = reg_supported(s.kind, s.d, s.m) && !psi_ext && c->variant != 1;
   if (c->variant == 2 && !reg && !psi_ext)
@@ -1287,7 +1302,7 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   for (int k = 0; k < K; ++k)
     if (start[k] < 0 || (int64_t)start[k] * n + d > (int64_t)ctx->T * n)
       return fail(ctx, GVI_ERR_ARG, "start index out of range");
-  int m = 0;
+  int m = 0, seg_J = 0;
   int64_t need = 0;
   switch (psi_kind) {
     case GVI_PSI_RANGE_1D: if (d != 1) return fail(ctx, GVI_ERR_ARG, "RANGE_1D needs d == 1"); need = 5; break;
@@ -1298,6 +1313,18 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
     case GVI_PSI_HINGE_SDF_2D_BODY: if (d < 3) return fail(ctx, GVI_ERR_ARG, "HINGE_SDF_2D_BODY needs d >= 3"); need = 6; break;
     case GVI_PSI_HINGE_SDF_3D: if (d < 3) return fail(ctx, GVI_ERR_ARG, "HINGE_SDF_3D needs d >= 3"); need = 3; break;
     case GVI_PSI_HINGE_SDF_3D_ARM: need = 2; break;
+    case GVI_PSI_HINGE_SDF_2D_SEG:
+    case GVI_PSI_HINGE_SDF_3D_SEG: {
+      // J is a property of the set: params_per_factor = 3 + J P (d + 1), exactly
+      const int64_t per = (int64_t)(psi_kind == GVI_PSI_HINGE_SDF_2D_SEG ? 2 : 3) * (d + 1);
+      const int64_t body = params_per_factor - 3;
+      if (body < per || body % per != 0 || body / per > SEG_MAX_J)
+        return fail(ctx, GVI_ERR_ARG, "HINGE_SDF_*_SEG needs params_per_factor = 3 + J P (d + 1) with 1 <= J <= 8 check points "
+                                      "(P = 2 for _2D_SEG, 3 for _3D_SEG)");
+      seg_J = (int)(body / per);
+      need = params_per_factor;
+      break;
+    }
     default: return fail(ctx, GVI_ERR_ARG, "unknown psi kind");
   }
   if (need > 0 && (!psi_params || params_per_factor < need))
@@ -1307,7 +1334,7 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   std::unique_ptr<FactorSet> s(new FactorSet);
   s->jtol = ctx->jacobi_tol;
   s->use_chol = ctx->chol_sqrt;
-  s->K = K; s->d = d; s->p = p; s->m = m; s->kind = psi_kind;
+  s->K = K; s->d = d; s->p = p; s->m = m; s->kind = psi_kind; s->seg_J = seg_J;
   if (K > 0) s->start.assign(start, start + K);
   // quadrature table: shared between sets with the same (d, p)
   if (tabZ) {
@@ -1365,7 +1392,8 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   GVICK(up(s->b, b.data(), b.size() * 8));
   GVICK(up(s->sgn, sg.data(), sg.size() * 8));
   s->all_pos = std::all_of(sg.begin(), sg.end(), [](double v) { return v == 1.0; });
-  if (psi_kind == GVI_PSI_RANGE_1D || psi_kind >= GVI_PSI_HINGE_SDF_2D) {
+  const bool raw_kind = psi_kind == GVI_PSI_RANGE_1D || (psi_kind >= GVI_PSI_HINGE_SDF_2D && psi_kind <= GVI_PSI_HINGE_SDF_3D_SEG);
+  if (raw_kind) {                       // raw_stride = the kind's own block (for the _SEG kinds: 3 + J P (d + 1))
     const int np = (int)need;
     std::vector<double> raw((size_t)K * np);
     for (int k = 0; k < K; ++k) memcpy(&raw[(size_t)k * np], psi_params + (size_t)k * params_per_factor, (size_t)np * 8);
@@ -1448,8 +1476,8 @@ gvi_status gvi_factors_set_sdf2d(gvi_ctx* ctx, int set_id, double origin_x, doub
                                  int cols, const double* data) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  if (s->kind != KIND_HINGE_SDF_2D && s->kind != KIND_HINGE_SDF_2D_BODY)
-    return fail(ctx, GVI_ERR_ARG, "set is not GVI_PSI_HINGE_SDF_2D / _2D_BODY");
+  if (s->kind != KIND_HINGE_SDF_2D && s->kind != KIND_HINGE_SDF_2D_BODY && s->kind != KIND_HINGE_SDF_2D_SEG)
+    return fail(ctx, GVI_ERR_ARG, "set is not GVI_PSI_HINGE_SDF_2D / _2D_BODY / _2D_SEG");
   if (rows < 2 || cols < 2 || !(cell_size > 0) || !data) return fail(ctx, GVI_ERR_ARG, "bad grid");
   HIPCK(ctx, hipSetDevice(ctx->device));
   GVICK(sync(ctx));
@@ -1465,8 +1493,8 @@ gvi_status gvi_factors_set_sdf3d(gvi_ctx* ctx, int set_id, const double* origin,
                                  int nz, const double* data) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  if (s->kind != KIND_HINGE_SDF_3D && s->kind != KIND_HINGE_SDF_3D_ARM)
-    return fail(ctx, GVI_ERR_ARG, "set is not GVI_PSI_HINGE_SDF_3D / _3D_ARM");
+  if (s->kind != KIND_HINGE_SDF_3D && s->kind != KIND_HINGE_SDF_3D_ARM && s->kind != KIND_HINGE_SDF_3D_SEG)
+    return fail(ctx, GVI_ERR_ARG, "set is not GVI_PSI_HINGE_SDF_3D / _3D_ARM / _3D_SEG");
   if (rows < 2 || cols < 2 || nz < 2 || !(cell_size > 0) || !data || !origin) return fail(ctx, GVI_ERR_ARG, "bad grid");
   HIPCK(ctx, hipSetDevice(ctx->device));
   GVICK(sync(ctx));

@@ -37,7 +37,10 @@
 namespace gvi {
 
 enum { KIND_RANGE_1D = 0, KIND_QUAD_PRIOR = 1, KIND_FIXED_PRIOR = 2, KIND_HOST_CALLBACK = 3, KIND_HINGE_SDF_2D = 4,
-       KIND_HINGE_SDF_2D_BODY = 5, KIND_HINGE_SDF_3D = 6, KIND_HINGE_SDF_3D_ARM = 7 };
+       KIND_HINGE_SDF_2D_BODY = 5, KIND_HINGE_SDF_3D = 6, KIND_HINGE_SDF_3D_ARM = 7, KIND_HINGE_SDF_2D_SEG = 8,
+       KIND_HINGE_SDF_3D_SEG = 9 };
+
+constexpr int SEG_MAX_J = 8;   // check points of one HINGE_SDF_*_SEG factor
 
 __host__ __device__ inline int npairs(int d) { return (d + 1) * (d + 2) / 2; }
 
@@ -87,6 +90,7 @@ struct FactorDev {
   int chol;
   double* Vws;              // [K][d][d] eigenvectors of the previous prep (warm start) or null
   int warm;                 // 1: start the Jacobi sweeps from Vws (resident NGD iteration only)
+  int seg_J;                // HINGE_SDF_*_SEG: check points per factor (1 .. SEG_MAX_J), else 0
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -906,6 +910,44 @@ __device__ inline double psi_hinge_sdf3d_arm(const FactorDev& f, const double* p
   return cost;
 }
 
+// Obstacle factor on a segment (no reference counterpart): J = f.seg_J check points, each a linear
+// read-out q_j = W_j x + c_j of the factor's slice x [d] (for d = 2n the pair of support states: W_j = the position rows of the
+// Gauss-Markov interpolation [A(tau_j) | B(tau_j)]), one ball of radius r at each, slope 1.
+// p = [sigma, eps, r | W_0 (P x d, row-major) | c_0 (P) | ... | W_{J-1} | c_{J-1}].  P = 2: the planar grid, P = 3: the 3-D field.
+template <int P, typename V>
+__device__ __forceinline__ void hinge_sdf_seg_points(const FactorDev& f, const double* p, const double* x, int d, V&& visit) {
+  const double* wc = p + 3;
+  for (int j = 0; j < f.seg_J; ++j, wc += P * (d + 1)) {
+    double q[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+      double v = wc[P * d + r];
+      for (int c = 0; c < d; ++c) v = fma(wc[r * d + c], x[c], v);
+      q[r] = v;
+    }
+    if constexpr (P == 2) visit(sdf2d_lookup(f, q[0], q[1]), p[2]);
+    else visit(sdf3d_lookup(f, q[0], q[1], q[P - 1]), p[2]);
+  }
+}
+template <typename V>
+__device__ __forceinline__ void hinge_sdf2d_seg_points(const FactorDev& f, const double* p, const double* x, int d, V&& visit) {
+  hinge_sdf_seg_points<2>(f, p, x, d, visit);
+}
+template <typename V>
+__device__ __forceinline__ void hinge_sdf3d_seg_points(const FactorDev& f, const double* p, const double* x, int d, V&& visit) {
+  hinge_sdf_seg_points<3>(f, p, x, d, visit);
+}
+__device__ inline double psi_hinge_sdf2d_seg(const FactorDev& f, const double* p, const double* x, int d) {
+  double cost = 0.0;
+  hinge_sdf2d_seg_points(f, p, x, d, [&](double sd, double r) { cost += hinge_sq(sd, p[1] + r, 1.0, p[0]); });
+  return cost;
+}
+__device__ inline double psi_hinge_sdf3d_seg(const FactorDev& f, const double* p, const double* x, int d) {
+  double cost = 0.0;
+  hinge_sdf3d_seg_points(f, p, x, d, [&](double sd, double r) { cost += hinge_sq(sd, p[1] + r, 1.0, p[0]); });
+  return cost;
+}
+
 // psi and / or clearance of factor k of a hinge-on-SDF set at the state slice x [d].  psi is the kind's
 // psi_* function; the clearance walks the same *_points with a min-visitor.  eps and slope play no part in the clearance.
 __device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, const double* x, bool want_psi, bool want_clr,
@@ -922,9 +964,18 @@ __device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, c
   } else if (f.kind == KIND_HINGE_SDF_3D) {
     if (want_psi) psi = psi_hinge_sdf3d(f, p, x[0], x[1], x[2]);
     if (want_clr) hinge_sdf3d_points(f, p, x[0], x[1], x[2], keep);
-  } else {
+  } else if (f.kind == KIND_HINGE_SDF_3D_ARM) {
     if (want_psi) psi = psi_hinge_sdf3d_arm(f, p, x, f.d);
     if (want_clr) hinge_sdf3d_arm_points(f, x, f.d, keep);
+  } else if (f.kind == KIND_HINGE_SDF_2D_SEG) {
+    if (want_psi) psi = psi_hinge_sdf2d_seg(f, p, x, f.d);
+    if (want_clr) hinge_sdf2d_seg_points(f, p, x, f.d, keep);
+  } else if (f.kind == KIND_HINGE_SDF_3D_SEG) {
+    if (want_psi) psi = psi_hinge_sdf3d_seg(f, p, x, f.d);
+    if (want_clr) hinge_sdf3d_seg_points(f, p, x, f.d, keep);
+  } else {                      // not a hinge-on-SDF kind: the host refuses such a set before any launch
+    if (want_psi) psi = __builtin_nan("");
+    c = __builtin_nan("");
   }
   if (want_clr) clr = c;
 }
@@ -1057,6 +1108,8 @@ __global__ __launch_bounds__(GEN_BS) void moments_generic_kernel(MomArgs a) {
       else if (f.kind == KIND_HINGE_SDF_2D_BODY) psi = psi_hinge_sdf2d_body(f, f.raw + (size_t)k * f.raw_stride, xr[0], xr[1], xr[2]);
       else if (f.kind == KIND_HINGE_SDF_3D) psi = psi_hinge_sdf3d(f, f.raw + (size_t)k * f.raw_stride, xr[0], xr[1], xr[2]);
       else if (f.kind == KIND_HINGE_SDF_3D_ARM) psi = psi_hinge_sdf3d_arm(f, f.raw + (size_t)k * f.raw_stride, xr, d);
+      else if (f.kind == KIND_HINGE_SDF_2D_SEG) psi = psi_hinge_sdf2d_seg(f, f.raw + (size_t)k * f.raw_stride, xr, d);
+      else if (f.kind == KIND_HINGE_SDF_3D_SEG) psi = psi_hinge_sdf3d_seg(f, f.raw + (size_t)k * f.raw_stride, xr, d);
       else {
         for (int r = 0; r < m; ++r) {
           double u = bsh[r];
@@ -1174,6 +1227,63 @@ struct PsiHingeSdf {
   }
 };
 template <int D> using PsiHingeSdf2D = PsiHingeSdf<D, KIND_HINGE_SDF_2D>;
+
+// Obstacle factor on a segment (hinge_sdf_seg_points): psi needs only the J check points, and at a sigma point
+// x = mu + S z they are q_j = (W_j mu + c_j) + (W_j S) z.  load forms G = W S (J P rows of D) and g = W mu + c ONCE per
+// (factor, chunk) into the wave's LDS slice -- J P D dot products of length D shared by the 64 lanes, from a.f.S (row-major)
+// and the raw block; eval is then P D FMAs against wave-uniform LDS reads plus one grid look-up per check point, and the full
+// x is never formed.  J is a run-time field (f.seg_J): the loop over j stays a loop, the FMAs inside it are unrolled.
+// hs: [J][P (D + 1)] = (G_j [P][D] | g_j [P]) in the raw block's own order, then [sigma, eps, r] at SEG_MAX_J P (D + 1).
+template <int D, int P>
+struct PsiHingeSeg {
+  static constexpr int STRIDE = P * (D + 1);
+  static constexpr int LDS = SEG_MAX_J * STRIDE + 3;
+  static constexpr bool GUARD = false;
+  __device__ static void load(const MomArgs& a, int k, double* hs, int lane) {
+    const double* raw = a.f.raw + (size_t)k * a.f.raw_stride;
+    const double* S = a.f.S + (size_t)k * D * D;
+    const double* mu = a.mu + (size_t)k * D;
+    const int J = a.f.seg_J < SEG_MAX_J ? a.f.seg_J : SEG_MAX_J;      // the host admits 1 .. SEG_MAX_J; keeps the LDS slice
+    for (int e = lane; e < J * STRIDE; e += 64) {
+      const int j = e / STRIDE, rem = e - j * STRIDE;
+      const double* Wj = raw + 3 + j * STRIDE;
+      double v;
+      if (rem < P * D) {                                              // G_j[r][c] = sum_e W_j[r][e] S[e][c]
+        const int r = rem / D, c = rem - r * D;
+        v = 0.0;
+#pragma unroll
+        for (int q = 0; q < D; ++q) v = fma(Wj[r * D + q], S[q * D + c], v);
+      } else {                                                        // g_j[r] = c_j[r] + W_j[r] mu
+        const int r = rem - P * D;
+        v = Wj[P * D + r];
+#pragma unroll
+        for (int q = 0; q < D; ++q) v = fma(Wj[r * D + q], mu[q], v);
+      }
+      hs[e] = v;
+    }
+    if (lane < 3) hs[SEG_MAX_J * STRIDE + lane] = raw[lane];
+  }
+  __device__ static double eval(const double (&z)[D], const double* hs, const MomArgs& a) {
+    const double sigma = hs[SEG_MAX_J * STRIDE], thr = hs[SEG_MAX_J * STRIDE + 1] + hs[SEG_MAX_J * STRIDE + 2];
+    const int J = a.f.seg_J < SEG_MAX_J ? a.f.seg_J : SEG_MAX_J;
+    double cost = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < J; ++j) {
+      const double* G = hs + j * STRIDE;
+      double q[P];
+#pragma unroll
+      for (int r = 0; r < P; ++r) {
+        double v = G[P * D + r];
+#pragma unroll
+        for (int c = 0; c < D; ++c) v = fma(G[r * D + c], z[c], v);
+        q[r] = v;
+      }
+      const double sd = P == 2 ? sdf2d_lookup(a.f, q[0], q[1]) : sdf3d_lookup(a.f, q[0], q[1], q[P - 1]);
+      cost += hinge_sq(sd, thr, 1.0, sigma);
+    }
+    return cost;
+  }
+};
 
 // (bx, by): the block's position in the (ceil(K / 4), nchunk) grid of the set -- the launch's own blockIdx, or a virtual one
 // when several sets share a launch (moments_planar3_kernel).  hs_: [4][Psi::LDS], red_: [4][16][65] doubles of LDS.

@@ -11,7 +11,7 @@ static const char MSG_NMAX[] = "state_dim > 16";
 static_assert(SAMPLE_NMAX == 16 && SOLVE_NMAX == 16 && INTERP_NMAX == 16, "one state_dim rule for every query");
 
 // ---- the check order ----
-static bool hinge_kind(int kind) { return kind >= KIND_HINGE_SDF_2D && kind <= KIND_HINGE_SDF_3D_ARM; }
+static bool hinge_kind(int kind) { return kind >= KIND_HINGE_SDF_2D && kind <= KIND_HINGE_SDF_3D_SEG; }
 
 static gvi_status scost_check_set(gvi_ctx* ctx, const FactorSet& s, bool clearance) {
   if (s.kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_UNSUPPORTED, "a PSI_HOST_CALLBACK set has no device psi");

@@ -7,6 +7,7 @@ the C-ABI works on.  psi parameter blocks use the C-ABI layouts of include/gvi_h
   QUAD_PRIOR  [Phi (n x n, row-major) | Qinv (n x n)]          d = 2n   (gp/minimum_acc_prior.h, gp/LTV_prior.h)
   FIXED_PRIOR [mu0 (d) | Kinv (d x d)]                         d = n    (gp/fixed_prior.h)
   RANGE_1D    [y, mu_p, f*b, sig_r_sq, sig_p_sq]               d = 1    (src/1d_example.cpp:25-35)
+  HINGE_SDF_2D_SEG / _3D_SEG  [sigma, eps, r | W_0 (P x d) | c_0 (P) | ... ]   d = n or 2n   (segment_params)
 """
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ import numpy as np
 
 PSI_RANGE_1D, PSI_QUAD_PRIOR, PSI_FIXED_PRIOR, PSI_HOST_CALLBACK, PSI_HINGE_SDF_2D = 0, 1, 2, 3, 4
 PSI_HINGE_SDF_2D_BODY, PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM = 5, 6, 7
+PSI_HINGE_SDF_2D_SEG, PSI_HINGE_SDF_3D_SEG = 8, 9
 
 CONFIGS = {
     # name: (cfg#, T, n, p, prior kind)
@@ -77,6 +79,46 @@ def minacc_interpolation(nd, qc, dt, tau):
     A = Phi(tau) - Psi @ Phi(dt)
     Qt = Q(tau) - Psi @ Phi(dt - tau) @ Q(tau)
     return A, Psi, (Qt + Qt.T) / 2
+
+
+def minacc_segment_readout(nd, qc, dt, taus, npos):
+    """(W [J][npos][2n], c [J][npos]) of the HINGE_SDF_*_SEG kinds for the constant-velocity prior of _minacc: check point j is
+    the first npos rows (the position) of x(tau_j) = A(tau_j) x_i + B(tau_j) x_i+1, so W_j = [A rows | B rows] of
+    minacc_interpolation and c_j = 0 (the prior has no input term)."""
+    n = 2 * nd
+    assert 1 <= npos <= n
+    W = np.zeros((len(taus), npos, 2 * n))
+    for j, tau in enumerate(taus):
+        A, B, _ = minacc_interpolation(nd, qc, dt, tau)
+        W[j, :, :n], W[j, :, n:] = A[:npos], B[:npos]
+    return W, np.zeros((len(taus), npos))
+
+
+def segment_params(sigma, eps, radius, W, c):
+    """Parameter blocks [K][3 + J P (d + 1)] of a HINGE_SDF_*_SEG set: [sigma, eps, r | W_0 | c_0 | ... | W_{J-1} | c_{J-1}].
+    W [J][P][d] and c [J][P] shared by the set, or [K][J][P][d] and [K][J][P] per factor; sigma, eps, radius scalars or [K]."""
+    W, c = np.asarray(W, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    sig, eps, radius = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (sigma, eps, radius))
+    K = max(sig.size, eps.size, radius.size, W.shape[0] if W.ndim == 4 else 1)
+    if W.ndim == 3:
+        W = np.broadcast_to(W, (K,) + W.shape)
+    if c.ndim == 2:
+        c = np.broadcast_to(c, (K,) + c.shape)
+    assert W.ndim == 4 and c.shape == W.shape[:3] and W.shape[0] == K
+    head = np.stack([np.broadcast_to(v, (K,)) for v in (sig, eps, radius)], axis=1)
+    body = np.concatenate([W.reshape(K, W.shape[1], -1), c], axis=2).reshape(K, -1)
+    return np.ascontiguousarray(np.concatenate([head, body], axis=1))
+
+
+def _segment_spec(obstacle, kind, T, n, nd, dt, taus, npos, p=None):
+    """The segment set beside the obstacle set `obstacle`: one factor per pair of neighbouring states (K = T - 1, start =
+    arange, d = 2n), check points at the times taus inside the segment, the obstacle set's sigma, eps, r and field; GH degree p
+    (default: the obstacle set's)."""
+    W, c = minacc_segment_readout(nd, QC, dt, taus, npos)
+    P = obstacle["params"]
+    return dict(kind=kind, d=2 * n, p=obstacle["p"] if p is None else p, start=np.arange(T - 1, dtype=np.int32),
+                params=segment_params(P[:T - 1, 0], P[:T - 1, 1], P[:T - 1, 2], W, c), temperature=np.ones(T - 1),
+                seg_W=W, seg_c=c, sdf_origin=obstacle["sdf_origin"], sdf_cell=obstacle["sdf_cell"], sdf_field=obstacle["sdf_field"])
 
 
 def _ltv_system(rng, nd):
@@ -264,11 +306,13 @@ def circle_sdf(origin, cell, rows, cols, centers, radii):
     return f
 
 
-def make_planar_chain(T=17, p=3, seed=0x5EED + 40, jitter=0.02, p_obstacle=None, horizon=None):
+def make_planar_chain(T=17, p=3, seed=0x5EED + 40, jitter=0.02, p_obstacle=None, horizon=None, segment_taus=None, segment_p=None):
     """Planar point-robot planning graph of the reference's own GPU workload: states
     [x, y, vx, vy] (n = 4), T-1 minimum-acceleration priors (d = 8), T hinge-on-SDF obstacle factors on
     every state (d = 4, helpers/CudaOperation.h:491-523) and two fixed-prior end anchors.  p_obstacle: GH degree of the
-    obstacle factors (default p + 1); horizon: total time (default (T - 1) / 4, i.e. dt = 0.25)."""
+    obstacle factors (default p + 1); horizon: total time (default (T - 1) / 4, i.e. dt = 0.25).  segment_taus: times in [0, dt]
+    of the check points of an additional HINGE_SDF_2D_SEG set on every pair of neighbouring states (d = 8), inserted behind the
+    obstacle set (specs = priors, obstacles, segments, anchors), at GH degree segment_p (default: the obstacle factors')."""
     rng = np.random.default_rng(seed)
     n, nd, K = 4, 2, T - 1
     dt = 0.25 if horizon is None else horizon / (T - 1)
@@ -300,6 +344,8 @@ def make_planar_chain(T=17, p=3, seed=0x5EED + 40, jitter=0.02, p_obstacle=None,
         dict(kind=PSI_FIXED_PRIOR, d=n, p=p, start=np.array([0, T - 1], dtype=np.int32),
              params=np.concatenate([anchors, Kinv.reshape(2, -1)], axis=1), temperature=np.ones(2), mu0=anchors, Kinv=Kinv),
     ]
+    if segment_taus is not None:
+        specs.insert(2, _segment_spec(specs[1], PSI_HINGE_SDF_2D_SEG, T, n, nd, dt, segment_taus, 2, segment_p))
     return dict(name="planar", T=T, n=n, specs=specs, mu0=mu0, D0=D0, U0=U0)
 
 
@@ -315,11 +361,12 @@ def sphere_sdf3d(origin, cell, rows, cols, nz, centers, radii):
     return f
 
 
-def make_obstacle_chain(kind: str, T=9, p=3, seed=0x5EED + 41):
+def make_obstacle_chain(kind: str, T=9, p=3, seed=0x5EED + 41, segment_taus=None, segment_p=None):
     """n = 6 planning graphs of the reference's other two obstacle workloads: "quad2d" (planar quadrotor,
     state [x, z, phi, vx, vz, w], body of 5 check points, helpers/CudaOperation.h:565-606) and "pr3d" (3-D point
     robot, state [x, y, z, v], trilinear field, :650-683): minimum-acceleration priors (d = 12), one obstacle
-    factor per state (d = 6) and two end anchors."""
+    factor per state (d = 6) and two end anchors.  segment_taus ("pr3d" only): as for make_planar_chain, a HINGE_SDF_3D_SEG set
+    (d = 12) behind the obstacle set."""
     rng = np.random.default_rng(seed + {"quad2d": 0, "pr3d": 1, "arm7": 2}[kind])
     nd = 7 if kind == "arm7" else 3
     n, K = 2 * nd, T - 1
@@ -366,6 +413,9 @@ def make_obstacle_chain(kind: str, T=9, p=3, seed=0x5EED + 41):
         dict(kind=PSI_FIXED_PRIOR, d=n, p=p, start=np.array([0, T - 1], dtype=np.int32),
              params=np.concatenate([anchors, Kinv.reshape(2, -1)], axis=1), temperature=np.ones(2), mu0=anchors, Kinv=Kinv),
     ]
+    if segment_taus is not None:
+        assert kind == "pr3d", "segment factors are built for the point robots"
+        specs.insert(2, _segment_spec(specs[1], PSI_HINGE_SDF_3D_SEG, T, n, nd, dt, segment_taus, 3, segment_p))
     return dict(name=kind, T=T, n=n, specs=specs, mu0=mu0, D0=D0, U0=U0)
 
 

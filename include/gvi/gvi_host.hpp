@@ -335,7 +335,40 @@ struct DevicePsi {
     p.params.insert(p.params.end(), Kinv.data(), Kinv.data() + Kinv.rows() * Kinv.cols());
     return p;
   }
-  bool same_group(const DevicePsi& o) const { return kind == o.kind && sdf2d == o.sdf2d && sdf3d == o.sdf3d && arm == o.arm; }
+  // Obstacle factor on a segment (GVI_PSI_HINGE_SDF_2D_SEG / _3D_SEG; no reference counterpart): J = W.size() check points
+  // W[j] x + c[j] of the factor's slice x, W[j] P x d (P = 2 / 3), c[j] of size P -- e.g. MinimumAccGP::segment_readout.
+  static DevicePsi hinge_sdf2d_segment(std::shared_ptr<const PlanarSDF> sdf, double sigma, double epsilon, double radius,
+                                       const std::vector<MatrixXd>& W, const std::vector<VectorXd>& c) {
+    DevicePsi p{GVI_PSI_HINGE_SDF_2D_SEG, segment_block(2, sigma, epsilon, radius, W, c)};
+    p.sdf2d = std::move(sdf);
+    return p;
+  }
+  static DevicePsi hinge_sdf3d_segment(std::shared_ptr<const SignedDistanceField> sdf, double sigma, double epsilon, double radius,
+                                       const std::vector<MatrixXd>& W, const std::vector<VectorXd>& c) {
+    DevicePsi p{GVI_PSI_HINGE_SDF_3D_SEG, segment_block(3, sigma, epsilon, radius, W, c)};
+    p.sdf3d = std::move(sdf);
+    return p;
+  }
+  // a set is homogeneous in its block size too: segment factors with different J stay apart
+  bool same_group(const DevicePsi& o) const {
+    const bool seg = kind == GVI_PSI_HINGE_SDF_2D_SEG || kind == GVI_PSI_HINGE_SDF_3D_SEG;
+    return kind == o.kind && sdf2d == o.sdf2d && sdf3d == o.sdf3d && arm == o.arm && (!seg || params.size() == o.params.size());
+  }
+  // [sigma, epsilon, radius | W_0 (P x d, row-major) | c_0 (P) | ...]: the kinds' parameter block (DevicePsi stays an aggregate)
+  static std::vector<double> segment_block(int P, double sigma, double epsilon, double radius, const std::vector<MatrixXd>& W,
+                                           const std::vector<VectorXd>& c) {
+    if (W.empty() || W.size() > (size_t)GVI_SEG_MAX_J || c.size() != W.size())
+      throw std::invalid_argument("segment factor: 1 .. GVI_SEG_MAX_J (8) check points, one offset c per read-out W");
+    std::vector<double> blk{sigma, epsilon, radius};
+    for (size_t j = 0; j < W.size(); ++j) {
+      if (W[j].rows() != P || W[j].cols() != W[0].cols() || c[j].size() != P)
+        throw std::invalid_argument("segment factor: every W must be P x d and every c of size P");
+      for (int r = 0; r < P; ++r)
+        for (int q = 0; q < W[j].cols(); ++q) blk.push_back(W[j](r, q));
+      for (int r = 0; r < P; ++r) blk.push_back(c[j](r));
+    }
+    return blk;
+  }
 };
 
 // Upload of a set's shared field / arm (gvi_factors_set_sdf2d / _sdf3d / _arm).
@@ -583,6 +616,23 @@ class MinimumAccGP : public LinearFactor {
     B = Psi;
     const MatrixXd Qn = Qtau - Psi * Prest * Qtau;
     Qt = (Qn + Qn.transpose()) * 0.5;
+  }
+  // Read-outs of DevicePsi::hinge_sdf2d_segment / hinge_sdf3d_segment: check point j is the first npos rows (the position) of
+  // the interpolated state at taus[j], W[j] = [A(tau_j) rows | B(tau_j) rows] (npos x 2 dim_state), c[j] = 0.
+  inline void segment_readout(const std::vector<double>& taus, int npos, std::vector<MatrixXd>& W, std::vector<VectorXd>& c) const {
+    const int n = _dim_state;
+    if (npos < 1 || npos > n) throw std::invalid_argument("MinimumAccGP::segment_readout: npos outside [1, dim_state]");
+    W.clear();
+    c.clear();
+    for (double tau : taus) {
+      MatrixXd A, B, Qt;
+      interpolation(tau, A, B, Qt);
+      MatrixXd Wj = MatrixXd::Zero(npos, 2 * n);
+      for (int r = 0; r < npos; ++r)
+        for (int q = 0; q < n; ++q) { Wj(r, q) = A(r, q); Wj(r, n + q) = B(r, q); }
+      W.push_back(Wj);
+      c.push_back(VectorXd::Zero(npos));
+    }
   }
   VectorXd get_mu() const override { return _target_mu; }
   MatrixXd get_precision() const override { return _invQ; }

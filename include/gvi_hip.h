@@ -63,10 +63,20 @@ enum { GVI_F64 = 0, GVI_F32 = 1 };
  *       (gvi_factors_set_sdf3d): CudaOperation_3dArm::cost_obstacle + ForwardKinematics
  *       (helpers/CudaOperation.h:325-399, 686-771); as there, n_balls = the factor dimension and the DH matrices
  *       are built from single-precision cosf / sinf
+ *   GVI_PSI_HINGE_SDF_2D_SEG / GVI_PSI_HINGE_SDF_3D_SEG                     d = n or 2n, P = 2 / P = 3 (no reference counterpart)
+ *       [sigma, epsilon, radius | W_0 (P x d, row-major) | c_0 (P) | ... | W_{J-1} | c_{J-1}]
+ *       psi(x) = sigma * sum_j max(0, epsilon + radius - sdf(W_j x + c_j))^2: J check points, each a linear read-out of the
+ *       factor's slice x (for d = 2n the pair (x_i, x_i+1)) -- e.g. the position rows of the Gauss-Markov interpolation
+ *       [A(tau) | B(tau)] at J times inside the segment, so that the optimiser sees an obstacle BETWEEN two support states
+ *       (DESIGN.md section 14).  The library neither knows nor requires that: any W_j, c_j is legal.  J is a property of the
+ *       set: J = (params_per_factor - 3) / (P (d + 1)); the division must be exact and 1 <= J <= 8 (GVI_SEG_MAX_J), else GVI_ERR_ARG.
+ *       Grid by gvi_factors_set_sdf2d (_2D_SEG) / gvi_factors_set_sdf3d (_3D_SEG); look-up and hinge as for HINGE_SDF_2D / _3D
  *   GVI_PSI_HOST_CALLBACK no parameters: psi is an opaque host function (the reference's
  *       std::function, ngd/NGDFactorizedBaseGH.h:30,46-48); use gvi_expand + gvi_moments_from_psi. */
 enum { GVI_PSI_RANGE_1D = 0, GVI_PSI_QUAD_PRIOR = 1, GVI_PSI_FIXED_PRIOR = 2, GVI_PSI_HOST_CALLBACK = 3,
-       GVI_PSI_HINGE_SDF_2D = 4, GVI_PSI_HINGE_SDF_2D_BODY = 5, GVI_PSI_HINGE_SDF_3D = 6, GVI_PSI_HINGE_SDF_3D_ARM = 7 };
+       GVI_PSI_HINGE_SDF_2D = 4, GVI_PSI_HINGE_SDF_2D_BODY = 5, GVI_PSI_HINGE_SDF_3D = 6, GVI_PSI_HINGE_SDF_3D_ARM = 7,
+       GVI_PSI_HINGE_SDF_2D_SEG = 8, GVI_PSI_HINGE_SDF_3D_SEG = 9 };
+enum { GVI_SEG_MAX_J = 8 };   /* check points of one HINGE_SDF_*_SEG factor */
 
 const char* gvi_version(void);
 /* Message of the last failing call on this context (never NULL). */
@@ -122,12 +132,12 @@ gvi_status gvi_factors_add_table(gvi_ctx* ctx, int K, int d, int p, const int32_
 /* Replace the set's quadrature table by a caller-supplied one (e.g. read from the reference's
  * cereal file quadrature/SparseGHQuadratureWeights_cereal.bin): Z [N][d], w [N], host. */
 gvi_status gvi_factors_set_table(gvi_ctx* ctx, int set_id, int64_t N, const double* Z, const double* w);
-/* Signed-distance grid of a GVI_PSI_HINGE_SDF_2D set: PlanarSDF(origin, cell_size, data)
+/* Signed-distance grid of a GVI_PSI_HINGE_SDF_2D / _2D_BODY / _2D_SEG set: PlanarSDF(origin, cell_size, data)
  * (helpers/CudaOperation.h:39-43); data is COLUMN-major rows x cols like Eigen's MatrixXd
  * (data[r + c * rows], :130), row = y cell, col = x cell; queries are clamped to the grid (:61-80). */
 gvi_status gvi_factors_set_sdf2d(gvi_ctx* ctx, int set_id, double origin_x, double origin_y, double cell_size,
                                  int rows, int cols, const double* data);
-/* 3-D field of a GVI_PSI_HINGE_SDF_3D set: SignedDistanceField(origin[3], cell_size, data) with
+/* 3-D field of a GVI_PSI_HINGE_SDF_3D / _3D_ARM / _3D_SEG set: SignedDistanceField(origin[3], cell_size, data) with
  * data[r + c * rows + z * rows * cols] (helpers/CudaOperation.h:148-158, 304-306): row = y, col = x, slice = z. */
 gvi_status gvi_factors_set_sdf3d(gvi_ctx* ctx, int set_id, const double* origin, double cell_size, int rows, int cols,
                                  int nz, const double* data);
@@ -404,7 +414,7 @@ gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_
  *      under GVI_RULE_PROX_JKO);  J(x) = sum over the sets, over k, of cost_k(x).
  *      The CLEARANCE of a hinge-on-SDF factor is min_b sdf(p_b) - r_b over the factor's check points b -- the points of its
  *      psi, in the same arithmetic: the one ball of HINGE_SDF_2D / _3D, the n_balls body points of _2D_BODY, the first
- *      min(d, nspheres) spheres with their own radii of _3D_ARM.  epsilon and slope play no part in it.  It is the continuous
+ *      min(d, nspheres) spheres with their own radii of _3D_ARM, the J read-outs W_j x + c_j of _2D_SEG / _3D_SEG.  epsilon and slope play no part in it.  It is the continuous
  *      quantity; the library returns no collided / not-collided indicator.
  *      S = 0 is a no-op; S < 0, a required NULL buffer, first < 0 or a set id outside the context's sets: GVI_ERR_ARG; before
  *      gvi_chain_set (gvi_ngd_*: before gvi_ngd_init): GVI_ERR_STATE, as is a hinge set whose grid (arm model) was never set; a
