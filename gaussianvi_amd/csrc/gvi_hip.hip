@@ -230,12 +230,6 @@ struct gvi_ctx {
   bool orbit_stack = true;            // two-set launch: block b takes item b of both sets (GVI_ORBIT_STACK=0: set 1 behind set 0)
   int orbit_copies = 8;               // private LDS copies of the accumulators (1, 2, 4, 8, 16; fewer when LDS is short)
   static constexpr int cost_chunk_mult = 8;   // cost pass of the F-factor kernel: chunks per factor relative to the full pass
-  static constexpr int scost_f = 2;           // factors per wave of the cost kernel (the four-factor form measured no better: removed)
-  // run_moments in planning mode: the launch that WOULD be issued is recorded instead (pair fusion of two sets)
-  // capture_any: kind 3 = "a lane-per-point launch of this set would go out with these arguments and this grid" (whichever
-  // register kernel): the three-set launch of the planning graph (moments_planar3_kernel)
-  struct Deferred { int kind = -1; MomArgs a; dim3 grid; int d = 0, m = 0; OrbitArgs oa; int smax = 0; bool all_pos = false; bool capture_any = false; };
-  Deferred* defer = nullptr;
   int update_rule = 0;                // 0 natural gradient (NGD-GH), 1 proximal / JKO (ProxGVI-GH)
   bool pair_fuse = true;              // GVI_NO_PAIR=1: one launch per set
   bool defer_gather = false;          // set around the trial-state refresh (a prep of that slot always follows)
@@ -511,24 +505,152 @@ FactorSet* get_set(gvi_ctx* c, int id) {
 
 static_assert(SEG_MAX_J == GVI_SEG_MAX_J, "the device's and the header's limit on check points per segment factor");
 
-// which (d, m) pairs have a register-kernel instantiation
-bool reg_supported(int kind, int d, int m) {
-  if (kind == KIND_RANGE_1D) return d == 1;
-  if (kind == KIND_HINGE_SDF_2D) return d == 2 || d == 4 || d == 6;
-  if (kind == KIND_HINGE_SDF_2D_BODY) return d == 3 || d == 6;
-  if (kind == KIND_HINGE_SDF_3D) return d == 3 || d == 6;
-  if (kind == KIND_HINGE_SDF_2D_SEG) return d == 4 || d == 8 || d == 12;
-  if (kind == KIND_HINGE_SDF_3D_SEG) return d == 6;   // d = 12: 256 VGPRs + 18 AGPR copies under launch_bounds(256) -> generic kernel
-  if (kind == KIND_QUAD_PRIOR) return (d == 2 && m == 1) || (d == 4 && m == 2) || (d == 6 && m == 3) ||
-                                      (d == 8 && m == 4) || (d == 12 && m == 6);
-  if (kind == KIND_FIXED_PRIOR) return d == m && (d == 1 || d == 2 || d == 3 || d == 4 || d == 6 || d == 8 || d == 12);
+// ---- the compiled instances of the factor kernels ----
+// Every kernel family has ONE list, with_<family>_instance: it hands f a tag that carries the template arguments of the
+// instance compiled for the shape and returns true, or returns false where there is none.  <family>_supported asks the list
+// with a no-op and the launch instantiates the kernel from the tag, so a new instance is registered by one line in its list.
+template <int D, typename Psi> struct RegInst {};
+template <int D, int M, bool PIPE> struct SregInst { static constexpr bool pipe = PIPE; };   // PIPE: the hand-pipelined body fits 256 registers
+template <int D, int M> struct ScostInst {};
+template <int D, int R> struct SplitInst {};
+template <int M, int SMAX, int WAVES, bool PAIR> struct OrbitInst { static constexpr int waves = WAVES; static constexpr bool pair = PAIR; };
+template <int KIND> struct OrbitPsiInst {};
+template <int M, int SMAX, int WAVES, int D0, int D1> struct FusedInst {};
+constexpr auto any_instance = [](auto) {};
+template <class F, class Inst> bool hit(F& f, Inst inst) { f(inst); return true; }
+
+// moments_reg_kernel<D, Psi, full>: lane-per-point, psi operands in LDS
+template <class F>
+bool with_reg_instance(int kind, int d, int m, F&& f) {
+  switch (kind) {
+    case KIND_RANGE_1D:
+      if (d == 1) return hit(f, RegInst<1, PsiRange1D>{});
+      break;
+    case KIND_HINGE_SDF_2D:
+      if (d == 2) return hit(f, RegInst<2, PsiHingeSdf2D<2>>{});
+      if (d == 4) return hit(f, RegInst<4, PsiHingeSdf2D<4>>{});
+      if (d == 6) return hit(f, RegInst<6, PsiHingeSdf2D<6>>{});
+      break;
+    case KIND_HINGE_SDF_2D_BODY:
+      if (d == 3) return hit(f, RegInst<3, PsiHingeSdf<3, KIND_HINGE_SDF_2D_BODY>>{});
+      if (d == 6) return hit(f, RegInst<6, PsiHingeSdf<6, KIND_HINGE_SDF_2D_BODY>>{});
+      break;
+    case KIND_HINGE_SDF_3D:
+      if (d == 3) return hit(f, RegInst<3, PsiHingeSdf<3, KIND_HINGE_SDF_3D>>{});
+      if (d == 6) return hit(f, RegInst<6, PsiHingeSdf<6, KIND_HINGE_SDF_3D>>{});
+      break;
+    case KIND_HINGE_SDF_2D_SEG:
+      if (d == 4) return hit(f, RegInst<4, PsiHingeSeg<4, 2>>{});
+      if (d == 8) return hit(f, RegInst<8, PsiHingeSeg<8, 2>>{});
+      if (d == 12) return hit(f, RegInst<12, PsiHingeSeg<12, 2>>{});
+      break;
+    case KIND_HINGE_SDF_3D_SEG:   // d = 12: 256 VGPRs + 18 AGPR copies under launch_bounds(256) -> generic kernel
+      if (d == 6) return hit(f, RegInst<6, PsiHingeSeg<6, 3>>{});
+      break;
+    case KIND_QUAD_PRIOR:
+      if (d != 2 * m) break;
+      if (d == 2) return hit(f, RegInst<2, PsiQuad<2, 1>>{});
+      if (d == 4) return hit(f, RegInst<4, PsiQuad<4, 2>>{});
+      if (d == 6) return hit(f, RegInst<6, PsiQuad<6, 3>>{});
+      if (d == 8) return hit(f, RegInst<8, PsiQuad<8, 4>>{});
+      if (d == 12) return hit(f, RegInst<12, PsiQuad<12, 6>>{});
+      break;
+    case KIND_FIXED_PRIOR:
+      if (d != m) break;
+      if (d == 1) return hit(f, RegInst<1, PsiQuad<1, 1>>{});
+      if (d == 2) return hit(f, RegInst<2, PsiQuad<2, 2>>{});
+      if (d == 3) return hit(f, RegInst<3, PsiQuad<3, 3>>{});
+      if (d == 4) return hit(f, RegInst<4, PsiQuad<4, 4>>{});
+      if (d == 6) return hit(f, RegInst<6, PsiQuad<6, 6>>{});
+      if (d == 8) return hit(f, RegInst<8, PsiQuad<8, 8>>{});
+      if (d == 12) return hit(f, RegInst<12, PsiQuad<12, 12>>{});
+      break;
+  }
   return false;
 }
 
-// split kernel (one block per factor and chunk): sum-of-squares kinds on a coded table
+// moments_sreg_kernel<D, M, full, pipelined>: lane-per-point, psi operands from SGPRs (variants 0 and 5)
+template <class F>
+bool with_sreg_instance(int kind, int d, int m, F&& f) {
+  if (kind == KIND_QUAD_PRIOR && d == 2 * m) {
+    if (d == 4) return hit(f, SregInst<4, 2, true>{});
+    if (d == 8) return hit(f, SregInst<8, 4, true>{});
+    if (d == 12) return hit(f, SregInst<12, 6, true>{});
+  }
+  if (kind == KIND_FIXED_PRIOR && d == m) {
+    if (d == 6) return hit(f, SregInst<6, 6, true>{});
+    if (d == 12) return hit(f, SregInst<12, 12, false>{});   // M = 12: the pipelined body does not fit 256 registers
+  }
+  return false;
+}
+
+// moments_scost_kernel<D, M, 2>: cost pass with two factors per wave (grid.x shrinks by 2); only the headline shapes
+template <class F>
+bool with_scost_instance(int kind, int d, int m, F&& f) {
+  if (kind == KIND_QUAD_PRIOR && d == 12 && m == 6) return hit(f, ScostInst<12, 6>{});
+  if (kind == KIND_FIXED_PRIOR && d == 6 && m == 6) return hit(f, ScostInst<6, 6>{});
+  return false;
+}
+
+// moments_split_kernel<D, R, full> (one block per factor and chunk), R = ceil(m / 4) row blocks: m = d and m = d / 2
+template <class F>
+bool with_split_instance(int d, int m, F&& f) {
+  if (d == 16 && m == 8) return hit(f, SplitInst<16, 2>{});
+  if (d == 16 && m == 16) return hit(f, SplitInst<16, 4>{});
+  if (d == 20 && m == 10) return hit(f, SplitInst<20, 3>{});
+  if (d == 20 && m == 20) return hit(f, SplitInst<20, 5>{});
+  if (d == 24 && m == 12) return hit(f, SplitInst<24, 3>{});
+  if (d == 24 && m == 24) return hit(f, SplitInst<24, 6>{});
+  return false;
+}
+
+// moments_orbit_kernel<M, SMAX, full, signed, WAVES>, and where PAIR moments_orbit_pair_kernel<M, SMAX, full, false, WAVES>:
+// smax is the largest support of the table's orbits (of both tables for the pair).  m = 2 is instantiated for supports <= 4
+// (every table of d <= 4, wider ones to degree 5), m = 14 (the d = 28 priors of the arm graph) likewise and on its own only.
+template <class F>
+bool with_orbit_instance(int m, int smax, F&& f) {
+  if (smax < 1 || smax > ORBIT_SMAX) return false;
+  if (m == 2 && smax <= 4) return hit(f, OrbitInst<2, 4, 4, true>{});
+  if (m == 14 && smax <= 4) return hit(f, OrbitInst<14, 4, 2, false>{});
+  if (m == 6) return smax <= 4 ? hit(f, OrbitInst<6, 4, 4, true>{}) : hit(f, OrbitInst<6, 6, 2, true>{});
+  if (m == 12) return smax <= 4 ? hit(f, OrbitInst<12, 4, 3, true>{}) : hit(f, OrbitInst<12, 6, 2, true>{});
+  return false;
+}
+
+// moments_orbit_psi_kernel<KIND, full>
+template <class F>
+bool with_orbit_psi_instance(int kind, F&& f) {
+  switch (kind) {
+    case KIND_RANGE_1D: return hit(f, OrbitPsiInst<KIND_RANGE_1D>{});
+    case KIND_HINGE_SDF_2D: return hit(f, OrbitPsiInst<KIND_HINGE_SDF_2D>{});
+    case KIND_HINGE_SDF_2D_BODY: return hit(f, OrbitPsiInst<KIND_HINGE_SDF_2D_BODY>{});
+    case KIND_HINGE_SDF_3D: return hit(f, OrbitPsiInst<KIND_HINGE_SDF_3D>{});
+    case KIND_HINGE_SDF_3D_ARM: return hit(f, OrbitPsiInst<KIND_HINGE_SDF_3D_ARM>{});
+  }
+  return false;
+}
+
+// factor_fused_kernel<M, SMAX, WAVES, D0, D1>: the chain patterns of BASELINE configs[1..3] (binary prior d = 2n + unary
+// factor d = n); smax over both tables
+template <class F>
+bool with_fused_instance(int m, int smax, int d0, int d1, F&& f) {
+  if (smax < 1 || smax > ORBIT_SMAX) return false;
+  if (m == 6 && d0 == 12 && d1 == 6) return smax <= 4 ? hit(f, FusedInst<6, 4, 4, 12, 6>{}) : hit(f, FusedInst<6, 6, 2, 12, 6>{});
+  if (m == 2 && d0 == 4 && d1 == 2 && smax <= 4) return hit(f, FusedInst<2, 4, 4, 4, 2>{});
+  return false;
+}
+
+bool reg_supported(int kind, int d, int m) { return with_reg_instance(kind, d, m, any_instance); }
+bool sreg_supported(const FactorSet& s) { return with_sreg_instance(s.kind, s.d, s.m, any_instance); }
+bool scost_supported(const FactorSet& s) { return with_scost_instance(s.kind, s.d, s.m, any_instance); }
+// sum-of-squares kinds on a coded table
 bool split_supported(const FactorSet& s) {
-  return (s.kind == KIND_QUAD_PRIOR || s.kind == KIND_FIXED_PRIOR) && s.table->coded &&
-         (s.d == 16 || s.d == 20 || s.d == 24) && (s.m == s.d || s.m == s.d / 2);
+  return (s.kind == KIND_QUAD_PRIOR || s.kind == KIND_FIXED_PRIOR) && s.table->coded && with_split_instance(s.d, s.m, any_instance);
+}
+bool orbit_pair_supported(int m, int smax) {
+  bool pair = false;
+  with_orbit_instance(m, smax, [&](auto inst) { pair = inst.pair; });
+  return pair;
 }
 
 template <int D, int R>
@@ -541,24 +663,15 @@ gvi_status launch_split(gvi_ctx* c, const MomArgs& a, dim3 grid, hipStream_t st)
   return GVI_OK;
 }
 
-void plan_chunks(gvi_ctx* c, FactorSet& s, bool reg) {
-  const int64_t Np = s.table->Np;
-  if (reg) {
-    const int64_t iters = Np / 256;                       // 256-point tiles (the tile kernel needs whole tiles)
-    int64_t nch = std::max<int64_t>(1, (c->target_waves + s.K - 1) / s.K);
-    nch = std::min<int64_t>(nch, std::max<int64_t>(1, iters));
-    const int64_t per = (iters + nch - 1) / nch;
-    s.chunk = per * 256;
-    s.nchunk = (int)((Np + s.chunk - 1) / s.chunk);
-  } else {
-    const int64_t blocks = (Np + 255) / 256;
-    int64_t nch = std::max<int64_t>(1, (1024 + s.K - 1) / s.K);
-    nch = std::min<int64_t>(nch, blocks);
-    const int64_t per = (blocks + nch - 1) / nch;
-    s.chunk = per * 256;
-    s.nchunk = (int)((Np + s.chunk - 1) / s.chunk);
-  }
+// about nch chunks of whole 256-point tiles (Np is a multiple of 256: upload_table)
+void chunk_tiles(FactorSet& s, int64_t nch) {
+  const int64_t Np = s.table->Np, iters = Np / 256;
+  nch = std::min<int64_t>(std::max<int64_t>(1, nch), std::max<int64_t>(1, iters));
+  s.chunk = (iters + nch - 1) / nch * 256;
+  s.nchunk = (int)((Np + s.chunk - 1) / s.chunk);
 }
+// lane-per-point kernels: target_waves waves over the set; generic kernel: ~1024 blocks
+void plan_chunks(gvi_ctx* c, FactorSet& s, bool reg) { chunk_tiles(s, ((reg ? c->target_waves : 1024) + s.K - 1) / s.K); }
 
 template <int D, typename Psi>
 void launch_reg(const MomArgs& a, dim3 grid, hipStream_t st) {
@@ -573,108 +686,16 @@ void launch_sreg(const MomArgs& a, dim3 grid, hipStream_t st, bool pipe) {
   else hipLaunchKernelGGL((moments_sreg_kernel<D, M, false>), grid, dim3(256), 0, st, a);
 }
 
-// cost pass with F factors per wave (grid.x shrinks by F); only the headline shapes
-bool scost_supported(const FactorSet& s) {
-  return (s.kind == KIND_QUAD_PRIOR && s.d == 12) || (s.kind == KIND_FIXED_PRIOR && s.d == 6);
-}
-template <int F>
-void launch_scost(const FactorSet& s, const MomArgs& a, int nchunk, hipStream_t st) {
-  const dim3 grid((s.K + 4 * F - 1) / (4 * F), nchunk);
-  if (s.kind == KIND_QUAD_PRIOR) hipLaunchKernelGGL((moments_scost_kernel<12, 6, F>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((moments_scost_kernel<6, 6, F>), grid, dim3(256), 0, st, a);
-}
-void dispatch_scost(gvi_ctx* c, const FactorSet& s, const MomArgs& a, int nchunk, hipStream_t st);
-
-bool sreg_supported(const FactorSet& s) {
-  if (s.kind == KIND_QUAD_PRIOR) return s.d == 4 || s.d == 8 || s.d == 12;
-  if (s.kind == KIND_FIXED_PRIOR) return s.d == 6 || s.d == 12;
-  return false;
-}
-
-// scalar-operand register kernel (variant 5)
-bool dispatch_sreg(const FactorSet& s, const MomArgs& a, dim3 grid, hipStream_t st, bool pipe) {
-  if (s.kind == KIND_QUAD_PRIOR) {
-    switch (s.d) {
-      case 4: launch_sreg<4, 2>(a, grid, st, pipe); return true;
-      case 8: launch_sreg<8, 4>(a, grid, st, pipe); return true;
-      case 12: launch_sreg<12, 6>(a, grid, st, pipe); return true;
-    }
-  }
-  if (s.kind == KIND_FIXED_PRIOR) {
-    switch (s.d) {
-      case 6: launch_sreg<6, 6>(a, grid, st, pipe); return true;
-      case 12: launch_sreg<12, 12>(a, grid, st, false); return true;   // M = 12: the pipelined body does not fit 256 registers
-    }
-  }
-  return false;
-}
-
-bool dispatch_reg(const FactorSet& s, const MomArgs& a, dim3 grid, hipStream_t st) {
-  const int d = s.d;
-  if (s.kind == KIND_RANGE_1D && d == 1) { launch_reg<1, PsiRange1D>(a, grid, st); return true; }
-  if (s.kind == KIND_HINGE_SDF_2D) {
-    switch (d) {
-      case 2: launch_reg<2, PsiHingeSdf2D<2>>(a, grid, st); return true;
-      case 4: launch_reg<4, PsiHingeSdf2D<4>>(a, grid, st); return true;
-      case 6: launch_reg<6, PsiHingeSdf2D<6>>(a, grid, st); return true;
-    }
-  }
-  if (s.kind == KIND_HINGE_SDF_2D_BODY) {
-    if (d == 3) { launch_reg<3, PsiHingeSdf<3, KIND_HINGE_SDF_2D_BODY>>(a, grid, st); return true; }
-    if (d == 6) { launch_reg<6, PsiHingeSdf<6, KIND_HINGE_SDF_2D_BODY>>(a, grid, st); return true; }
-  }
-  if (s.kind == KIND_HINGE_SDF_3D) {
-    if (d == 3) { launch_reg<3, PsiHingeSdf<3, KIND_HINGE_SDF_3D>>(a, grid, st); return true; }
-    if (d == 6) { launch_reg<6, PsiHingeSdf<6, KIND_HINGE_SDF_3D>>(a, grid, st); return true; }
-  }
-  if (s.kind == KIND_HINGE_SDF_2D_SEG) {
-    switch (d) {
-      case 4: launch_reg<4, PsiHingeSeg<4, 2>>(a, grid, st); return true;
-      case 8: launch_reg<8, PsiHingeSeg<8, 2>>(a, grid, st); return true;
-      case 12: launch_reg<12, PsiHingeSeg<12, 2>>(a, grid, st); return true;
-    }
-  }
-  if (s.kind == KIND_HINGE_SDF_3D_SEG) {
-    if (d == 6) { launch_reg<6, PsiHingeSeg<6, 3>>(a, grid, st); return true; }
-  }
-  if (s.kind == KIND_QUAD_PRIOR) {
-    switch (d) {
-      case 2: launch_reg<2, PsiQuad<2, 1>>(a, grid, st); return true;
-      case 4: launch_reg<4, PsiQuad<4, 2>>(a, grid, st); return true;
-      case 6: launch_reg<6, PsiQuad<6, 3>>(a, grid, st); return true;
-      case 8: launch_reg<8, PsiQuad<8, 4>>(a, grid, st); return true;
-      case 12: launch_reg<12, PsiQuad<12, 6>>(a, grid, st); return true;
-    }
-  }
-  if (s.kind == KIND_FIXED_PRIOR) {
-    switch (d) {
-      case 1: launch_reg<1, PsiQuad<1, 1>>(a, grid, st); return true;
-      case 2: launch_reg<2, PsiQuad<2, 2>>(a, grid, st); return true;
-      case 3: launch_reg<3, PsiQuad<3, 3>>(a, grid, st); return true;
-      case 4: launch_reg<4, PsiQuad<4, 4>>(a, grid, st); return true;
-      case 6: launch_reg<6, PsiQuad<6, 6>>(a, grid, st); return true;
-      case 8: launch_reg<8, PsiQuad<8, 8>>(a, grid, st); return true;
-      case 12: launch_reg<12, PsiQuad<12, 12>>(a, grid, st); return true;
-    }
-  }
-  return false;
-}
-
-void dispatch_scost(gvi_ctx* c, const FactorSet& s, const MomArgs& a, int nchunk, hipStream_t st) {
-  launch_scost<2>(s, a, nchunk, st);
-}
-
 // ---- sign-orbit kernel (kernels_orbit.hpp) ----
 bool orbit_supported(const gvi_ctx* c, const FactorSet& s) {
   if (!c->orbit || !(c->variant == 0 || c->variant == 6)) return false;
   if (s.kind != KIND_QUAD_PRIOR && s.kind != KIND_FIXED_PRIOR) return false;
-  if (!(s.m == 2 || s.m == 6 || s.m == 12 || (s.m == 14 && s.table->orb.smax <= 4)) || s.d > 32) return false;   // m = 14: the d = 28 priors of the arm graph
-  if (s.m == 2 && s.table->orb.smax > 4) return false;          // m = 2 is instantiated for supports <= 4: every table of d <= 4, wider ones to degree 5
   const OrbitHost& o = s.table->orb;
-  return o.ok && o.smax >= 1 && o.smax <= ORBIT_SMAX && !o.tile_s.empty();
+  return s.d <= 32 && o.ok && !o.tile_s.empty() && with_orbit_instance(s.m, o.smax, any_instance);
 }
 
-gvi_status orbit_args(gvi_ctx* c, FactorSet& s, int full, OrbitArgs* out) {
+// the table's sign-orbit form as kernel arguments, for the set's current s.nchunk
+gvi_status orbit_dev(gvi_ctx* c, FactorSet& s, OrbitDev* out) {
   Table& t = *s.table;
   auto it = t.orb_bounds.find(s.nchunk);
   if (it == t.orb_bounds.end()) {
@@ -684,39 +705,47 @@ gvi_status orbit_args(gvi_ctx* c, FactorSet& s, int full, OrbitArgs* out) {
     HIPCK(c, hipMemcpy(mem->p, b.data(), b.size() * 4, hipMemcpyHostToDevice));
     it = t.orb_bounds.emplace(s.nchunk, std::move(mem)).first;
   }
+  OrbitDev& ob = *out;
+  ob.cpk = (const uint64_t*)t.orb_cpk.p; ob.rpk = (const uint64_t*)t.orb_rpk.p; ob.mag = t.orb_mag.d(); ob.w = t.orb_w.d();
+  ob.bounds = it->second->i();
+  ob.norb_p = t.orb.norb_p; ob.w0 = t.orb.w0;
+  // the tile list as kernel arguments: class ends and, for up to four chunks, the chunk bounds
+  int32_t cum = 0;
+  for (int sz = 7; sz >= 0; --sz) {
+    if (sz >= 1 && sz <= t.orb.smax) cum += t.orb.cstride[sz] / 64;           // tiles of the class
+    ob.cend[sz] = sz > t.orb.smax ? 0 : cum;
+  }
+  for (int sz = 0; sz < 8; ++sz) {
+    const bool in = sz >= 1 && sz <= t.orb.smax;
+    ob.cbase[sz] = in ? t.orb.cbase[sz] : 0;
+    ob.cgrp[sz] = in ? t.orb.cgrp[sz] : 1;
+    ob.cstride[sz] = in ? t.orb.cstride[sz] : 0;
+  }
+  ob.nb = 0;
+  for (int i = 0; i < 5; ++i) ob.bnd[i] = 0;
+  if (s.nchunk <= 4) {
+    const std::vector<int32_t> b = orbit_chunk_bounds(t.orb, s.nchunk);
+    ob.nb = s.nchunk;
+    for (int i = 0; i <= s.nchunk; ++i) ob.bnd[i] = b[(size_t)i];
+  }
+  return GVI_OK;
+}
+
+// arguments of moments_orbit_kernel for a set that orbit_supported accepts
+gvi_status orbit_args(gvi_ctx* c, FactorSet& s, OrbitArgs* out) {
   OrbitArgs a;
   a.H = s.H.d(); a.u0 = s.u0.d(); a.sgn = s.sgn.d(); a.partial = s.partial.d();
   a.K = s.K; a.d = s.d; a.nchunk = s.nchunk;
   a.pred = c->cur_pred; a.pred_val = c->cur_pred_val;
-  // private accumulator copies: as many as the kernel's occupancy leaves LDS for (160 KB per CU, 64 KB per block), capped by orbit_copies
-  const int waves = ((s.m == 6 && t.orb.smax <= 4) || s.m == 2) ? 4 : ((s.m == 12 && t.orb.smax <= 4) ? 3 : 2);   // launch_orbit's occupancy
+  // private accumulator copies: as many as the occupancy of the set's own instance leaves LDS for (160 KB per CU, 64 KB per
+  // block), capped by orbit_copies
+  int waves = 0;
+  with_orbit_instance(s.m, s.table->orb.smax, [&](auto inst) { waves = inst.waves; });
+  if (!waves) return fail(c, GVI_ERR_STATE, "orbit_args: no sign-orbit instance for this set");
   const size_t lds_cap = std::min<size_t>(64 * 1024, 160 * 1024 / waves);
   a.copies = 1;
   while (a.copies * 2 <= c->orbit_copies && (size_t)4 * orbit_lds_doubles(s.d, s.m, a.copies * 2) * 8 <= lds_cap) a.copies *= 2;
-  a.ob.cpk = (const uint64_t*)t.orb_cpk.p; a.ob.rpk = (const uint64_t*)t.orb_rpk.p; a.ob.mag = t.orb_mag.d(); a.ob.w = t.orb_w.d();
-  a.ob.bounds = it->second->i();
-  a.ob.norb_p = t.orb.norb_p; a.ob.w0 = t.orb.w0;
-  {   // the tile list as kernel arguments (OrbitDev): class ends and, for up to four chunks, the chunk bounds
-    int32_t cum = 0;
-    for (int sz = 7; sz >= 0; --sz) {
-      if (sz >= 1 && sz <= t.orb.smax) cum += t.orb.cstride[sz] / 64;           // tiles of the class
-      a.ob.cend[sz] = sz > t.orb.smax ? 0 : cum;
-    }
-    for (int sz = 0; sz < 8; ++sz) {
-      const bool in = sz >= 1 && sz <= t.orb.smax;
-      a.ob.cbase[sz] = in ? t.orb.cbase[sz] : 0;
-      a.ob.cgrp[sz] = in ? t.orb.cgrp[sz] : 1;
-      a.ob.cstride[sz] = in ? t.orb.cstride[sz] : 0;
-    }
-    a.ob.nb = 0;
-    for (int i = 0; i < 5; ++i) a.ob.bnd[i] = 0;
-    if (s.nchunk <= 4) {
-      const std::vector<int32_t> b = orbit_chunk_bounds(t.orb, s.nchunk);
-      a.ob.nb = s.nchunk;
-      for (int i = 0; i <= s.nchunk; ++i) a.ob.bnd[i] = b[(size_t)i];
-    }
-  }
-  (void)full;
+  GVICK(orbit_dev(c, s, &a.ob));
   *out = a;
   return GVI_OK;
 }
@@ -727,17 +756,6 @@ void launch_orbit_t(const OrbitArgs& a, bool full, bool all_pos, dim3 grid, size
   else if (full) hipLaunchKernelGGL((moments_orbit_kernel<M, SMAX, true, true, WAVES>), grid, dim3(256), lds, st, a);
   else if (all_pos) hipLaunchKernelGGL((moments_orbit_kernel<M, SMAX, false, false, WAVES>), grid, dim3(256), lds, st, a);
   else hipLaunchKernelGGL((moments_orbit_kernel<M, SMAX, false, true, WAVES>), grid, dim3(256), lds, st, a);
-}
-
-void launch_orbit(const OrbitArgs& a, int m, int smax, bool full, bool all_pos, hipStream_t st) {
-  const dim3 grid((a.K + 3) / 4, a.nchunk);
-  const size_t lds = (size_t)4 * orbit_lds_doubles(a.d, m, a.copies) * 8;
-  if (m == 2) launch_orbit_t<2, 4, 4>(a, full, all_pos, grid, lds, st);
-  else if (m == 14) launch_orbit_t<14, 4, 2>(a, full, all_pos, grid, lds, st);
-  else if (m == 6 && smax <= 4) launch_orbit_t<6, 4, 4>(a, full, all_pos, grid, lds, st);
-  else if (m == 6) launch_orbit_t<6, 6, 2>(a, full, all_pos, grid, lds, st);
-  else if (smax <= 4) launch_orbit_t<12, 4, 3>(a, full, all_pos, grid, lds, st);
-  else launch_orbit_t<12, 6, 2>(a, full, all_pos, grid, lds, st);
 }
 
 // two sets with the same m and sgn = +1 in one launch.  e0 / e1 non-null: the launch itself carries the start / stop events
@@ -759,14 +777,13 @@ void launch_orbit_pair_t(const OrbitArgs& a0, const OrbitArgs& a1, bool full, si
                           a0, a1, nbx0, nb0, nx1);
 }
 
+// m and smax as orbit_pair_supported accepted them
 void launch_orbit_pair(const OrbitArgs& a0, const OrbitArgs& a1, int m, int smax, bool full, hipStream_t st, bool stack,
-                       hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+                       hipEvent_t e0, hipEvent_t e1) {
   const size_t lds = (size_t)4 * std::max(orbit_lds_doubles(a0.d, m, a0.copies), orbit_lds_doubles(a1.d, m, a1.copies)) * 8;
-  if (m == 2) launch_orbit_pair_t<2, 4, 4>(a0, a1, full, lds, st, e0, e1, stack);
-  else if (m == 6 && smax <= 4) launch_orbit_pair_t<6, 4, 4>(a0, a1, full, lds, st, e0, e1, stack);
-  else if (m == 6) launch_orbit_pair_t<6, 6, 2>(a0, a1, full, lds, st, e0, e1, stack);
-  else if (smax <= 4) launch_orbit_pair_t<12, 4, 3>(a0, a1, full, lds, st, e0, e1, stack);
-  else launch_orbit_pair_t<12, 6, 2>(a0, a1, full, lds, st, e0, e1, stack);
+  with_orbit_instance(m, smax, [&]<int M, int SMAX, int WAVES, bool PAIR>(OrbitInst<M, SMAX, WAVES, PAIR>) {
+    if constexpr (PAIR) launch_orbit_pair_t<M, SMAX, WAVES>(a0, a1, full, lds, st, e0, e1, stack);
+  });
 }
 
 // Launches of factor_fused_kernel in this process, per instantiation: [0] <6,4,4,12,6>, [1] <6,6,2,12,6>, [2] <2,4,4,4,2>.
@@ -851,12 +868,10 @@ gvi_status run_prep(gvi_ctx* c, FactorSet& s, const double* mu, const double* Si
 // pass than the generic kernel, which keeps 54 k points in flight.  It stays as the A/B leg and as the parity cross-check
 // (three independent kernels for these kinds); the arm graph's 0.27 ms launch was its d = 28 PRIOR set on the generic kernel,
 // which now takes the m = 14 instance of the sign-orbit kernel.
-bool orbit_psi_supported(const gvi_ctx* c, const FactorSet& s, bool reg) {
+bool orbit_psi_supported(const gvi_ctx* c, const FactorSet& s) {
   if (!c->orbit) return false;
-  (void)reg;
   if (!(c->variant == 0 && c->prefer_opsi)) return false;
-  if (!(s.kind == KIND_RANGE_1D || s.kind == KIND_HINGE_SDF_2D || s.kind == KIND_HINGE_SDF_2D_BODY || s.kind == KIND_HINGE_SDF_3D ||
-        s.kind == KIND_HINGE_SDF_3D_ARM)) return false;
+  if (!with_orbit_psi_instance(s.kind, any_instance)) return false;
   const OrbitHost& o = s.table->orb;
   if (!(o.ok && o.smax >= 1 && o.smax <= 4 && !o.tile_s.empty()) || s.d > 32) return false;
   if (s.kind == KIND_HINGE_SDF_3D_ARM && (s.arm_ndof < 1 || s.arm_ndof > orbit_psi_rows(KIND_HINGE_SDF_3D_ARM))) return false;
@@ -874,30 +889,29 @@ gvi_status launch_orbit_psi_t(gvi_ctx* c, const OrbitPsiArgs& a, bool full, dim3
   return GVI_OK;
 }
 
-gvi_status launch_orbit_psi(gvi_ctx* c, FactorSet& s, const double* mu, int full, hipStream_t st) {
-  OrbitArgs oa;
-  GVICK(orbit_args(c, s, full, &oa));                       // table pointers, class layout, chunk bounds
-  OrbitPsiArgs a;
-  a.f = s.dev(); a.mu = mu; a.partial = s.partial.d(); a.nchunk = s.nchunk;
-  a.pred = c->cur_pred; a.pred_val = c->cur_pred_val; a.ob = oa.ob;
-  const int NR = orbit_psi_rows(s.kind);
-  a.copies = 1;
-  while (a.copies * 2 <= c->orbit_copies && (size_t)4 * orbit_psi_lds_doubles(s.d, NR, a.copies * 2, true) * 8 <= 64 * 1024) a.copies *= 2;
-  const size_t lds = (size_t)4 * orbit_psi_lds_doubles(s.d, NR, a.copies, full != 0) * 8;
-  const dim3 grid((s.K + 3) / 4, s.nchunk);
-  switch (s.kind) {
-    case KIND_RANGE_1D: return launch_orbit_psi_t<KIND_RANGE_1D>(c, a, full != 0, grid, lds, st);
-    case KIND_HINGE_SDF_2D: return launch_orbit_psi_t<KIND_HINGE_SDF_2D>(c, a, full != 0, grid, lds, st);
-    case KIND_HINGE_SDF_2D_BODY: return launch_orbit_psi_t<KIND_HINGE_SDF_2D_BODY>(c, a, full != 0, grid, lds, st);
-    case KIND_HINGE_SDF_3D: return launch_orbit_psi_t<KIND_HINGE_SDF_3D>(c, a, full != 0, grid, lds, st);
-    default: return launch_orbit_psi_t<KIND_HINGE_SDF_3D_ARM>(c, a, full != 0, grid, lds, st);
-  }
-}
+// ---- the moments (full = 1) or cost (full = 0) pass of one set: plan, then launch ----
+// A plan is a value: the route, the chunking and the kernel arguments of the launch the set would issue on its own.  The
+// resident iteration plans every set once, then either fuses the launches of two or three plans or issues each one.
+enum class Route { Empty, Closed, Orbit, OrbitPsi, Split, Sreg, Scost, Reg, Generic };
+struct MomPlan {
+  Route route = Route::Empty;
+  int full = 0;
+  MomArgs a;                 // every route but the two sign-orbit ones
+  dim3 grid;                 // of the set's own launch
+  OrbitArgs oa;              // Orbit
+  int smax = 0;              // Orbit: the table's largest support (instance key beside m)
+  OrbitPsiArgs pa;           // OrbitPsi
+  size_t lds = 0;            // Orbit, OrbitPsi, Generic: dynamic LDS
+  bool pipe = false;         // Sreg: the hand-pipelined body
+};
+// lane-per-point register kernels: a block's four waves take four factors, grid ((K + 3) / 4, nchunk) but for Scost's own launch
+bool lane_per_point(const MomPlan& p) { return p.route == Route::Sreg || p.route == Route::Scost || p.route == Route::Reg; }
 
-// moments (full=1) or cost (full=0) pass for one set; prep must have run for (mu, Sigma).
-gvi_status run_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double* psi_ext, int full,
-                       hipStream_t st = nullptr) {
-  if (!st) st = c->stream;
+// Everything before the launch: state checks, route under `variant` and the options, chunking (s.nchunk / chunk / use_*),
+// the partial buffer, the kernel arguments.  prep must have run for (mu, Sigma) before the plan is launched.
+gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double* psi_ext, int full, MomPlan* out) {
+  MomPlan& p = *out;
+  p.route = Route::Empty; p.full = full;
   if (s.K == 0) { s.nchunk = 1; s.chunk = s.table->Np; s.use_reg = s.use_split = s.use_orbit = s.use_opsi = false; return GVI_OK; }   // empty shard
   if (s.kind == KIND_HINGE_SDF_3D_ARM && !psi_ext && !s.arm.p)
     return fail(c, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");
@@ -908,7 +922,7 @@ gvi_status run_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double*
     return fail(c, GVI_ERR_UNSUPPORTED, "register kernel not instantiated for this (kind, d)");
   const bool closed = s.closed_form && !psi_ext;
   const bool orbit = !closed && !psi_ext && orbit_supported(c, s);
-  const bool opsi = !closed && !orbit && !psi_ext && orbit_psi_supported(c, s, reg);
+  const bool opsi = !closed && !orbit && !psi_ext && orbit_psi_supported(c, s);
   const bool split = !closed && !orbit && !opsi && !reg && !psi_ext && c->variant != 1 && split_supported(s);
   if (closed) { reg = false; s.chunk = s.table->Np; s.nchunk = 1; }
   else if (orbit || opsi) {
@@ -928,21 +942,18 @@ gvi_status run_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double*
     s.chunk = (tiles + nch - 1) / nch * 64;
     s.nchunk = (int)((s.table->Np + s.chunk - 1) / s.chunk);
   } else plan_chunks(c, s, reg);
-  if (reg && !full && !closed && !orbit && (c->variant == 5 || c->variant == 0) && scost_supported(s) && !c->no_scost) {
-    // F factors per wave: keep the wave count up with more, shorter chunks
-    const int64_t iters = s.table->Np / 256;
-    int64_t nch = std::min<int64_t>(std::max<int64_t>(1, (int64_t)s.nchunk * c->cost_chunk_mult), std::max<int64_t>(1, iters));
-    const int64_t per = (iters + nch - 1) / nch;
-    s.chunk = per * 256;
-    s.nchunk = (int)((s.table->Np + s.chunk - 1) / s.chunk);
-  }
+  // auto (variants 0 and 5): psi operands from SGPRs where instantiated (fastest for both passes); otherwise the operand-
+  // resident kernel for the cost pass and the LDS-operand kernel for the full pass
+  const bool sgpr = reg && (c->variant == 5 || c->variant == 0);
+  const bool scost = sgpr && !full && scost_supported(s) && !c->no_scost;
+  if (scost) chunk_tiles(s, (int64_t)s.nchunk * c->cost_chunk_mult);   // two factors per wave: keep the wave count up with more, shorter chunks
   s.use_reg = reg;
   s.use_split = split;
   s.use_orbit = orbit;
   s.use_opsi = opsi;
   const size_t need = (size_t)s.K * s.nchunk * npairs(s.d) * 8;
   HIPCK(c, s.partial.ensure(need));
-  MomArgs a;
+  MomArgs& a = p.a;
   s.use_mirror = c->mirror;
   a.f = s.dev(); a.mu = mu; a.psi_ext = psi_ext; a.partial = s.partial.d();
   a.chunk = s.chunk; a.nchunk = s.nchunk; a.full = full; a.flush = c->split_flush;
@@ -952,73 +963,190 @@ gvi_status run_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double*
     const int64_t tiles = s.table->Nmp / 64;
     a.mchunk = (tiles + s.nchunk - 1) / s.nchunk * 64;
   }
-  const int which = full ? 0 : 1;
-  bool prof = !c->defer && c->profile && (c->profile_all || (full && &s == c->sets[0].get()));
-  if (prof && !c->profile_all && (c->profile_count++ % c->profile_every) != 0) prof = false;
-  if (prof) {
-    for (int e = 0; e < 2; ++e)
-      if (!s.ev[which][e]) HIPCK(c, hipEventCreate(&s.ev[which][e]));
-    HIPCK(c, hipEventRecord(s.ev[which][0], st));
-  }
+  p.grid = dim3((s.K + 3) / 4, s.nchunk);
   if (closed) {
-    hipLaunchKernelGGL(moments_closed_kernel, dim3(s.K), dim3(64), 0, st, a);
+    p.route = Route::Closed;
+    p.grid = dim3(s.K);
   } else if (orbit) {
-    OrbitArgs oa;
-    GVICK(orbit_args(c, s, full, &oa));
-    if (c->defer) {
-      c->defer->kind = 2; c->defer->oa = oa; c->defer->d = s.d; c->defer->m = s.m;
-      c->defer->smax = s.table->orb.smax; c->defer->all_pos = s.all_pos;
-      return GVI_OK;
-    }
-    launch_orbit(oa, s.m, s.table->orb.smax, full != 0, s.all_pos, st);
+    p.route = Route::Orbit;
+    GVICK(orbit_args(c, s, &p.oa));
+    p.smax = s.table->orb.smax;
+    p.lds = (size_t)4 * orbit_lds_doubles(s.d, s.m, p.oa.copies) * 8;
   } else if (opsi) {
-    GVICK(launch_orbit_psi(c, s, mu, full, st));
+    p.route = Route::OrbitPsi;
+    OrbitPsiArgs& pa = p.pa;
+    pa.f = a.f; pa.mu = mu; pa.partial = s.partial.d(); pa.nchunk = s.nchunk;
+    pa.pred = c->cur_pred; pa.pred_val = c->cur_pred_val;
+    GVICK(orbit_dev(c, s, &pa.ob));                         // table pointers, class layout, chunk bounds
+    const int NR = orbit_psi_rows(s.kind);
+    pa.copies = 1;
+    while (pa.copies * 2 <= c->orbit_copies && (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies * 2, true) * 8 <= 64 * 1024) pa.copies *= 2;
+    p.lds = (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies, full != 0) * 8;
   } else if (split) {
-    const dim3 grid(s.K, s.nchunk);
-    const int R = (s.m + 3) / 4;
-    if (s.d == 16 && R == 2) GVICK((launch_split<16, 2>(c, a, grid, st)));
-    else if (s.d == 16) GVICK((launch_split<16, 4>(c, a, grid, st)));
-    else if (s.d == 20 && R == 3) GVICK((launch_split<20, 3>(c, a, grid, st)));
-    else if (s.d == 20) GVICK((launch_split<20, 5>(c, a, grid, st)));
-    else if (R == 3) GVICK((launch_split<24, 3>(c, a, grid, st)));
-    else GVICK((launch_split<24, 6>(c, a, grid, st)));
+    p.route = Route::Split;
+    p.grid = dim3(s.K, s.nchunk);
+  } else if (scost) {
+    p.route = Route::Scost;
+    p.grid = dim3((s.K + 7) / 8, s.nchunk);
+  } else if (sgpr && sreg_supported(s)) {
+    p.route = Route::Sreg;
+    with_sreg_instance(s.kind, s.d, s.m, [&](auto inst) { p.pipe = inst.pipe && c->sreg_pipe && s.table->Zq.p; });
   } else if (reg) {
-    dim3 grid((s.K + 3) / 4, s.nchunk);
-    bool done = false;
-    if (c->defer && c->defer->capture_any) {
-      c->defer->kind = 3; c->defer->a = a; c->defer->grid = grid; c->defer->d = s.d; c->defer->m = s.m;
-      return GVI_OK;
-    }
-    // auto: psi operands from SGPRs where instantiated (fastest for both passes); otherwise the operand-
-    // resident kernel for the cost pass and the LDS-operand kernel for the full pass
-    if ((c->variant == 5 || c->variant == 0) && !full && scost_supported(s) && !c->no_scost) {
-      if (c->defer && c->scost_f == 2) {
-        c->defer->kind = 1; c->defer->a = a; c->defer->grid = dim3((s.K + 7) / 8, s.nchunk); c->defer->d = s.d; c->defer->m = s.m;
-        return GVI_OK;
-      }
-      dispatch_scost(c, s, a, s.nchunk, st);
-      done = true;
-    }
-    if (!done && (c->variant == 5 || c->variant == 0) && c->defer && full && sreg_supported(s)) {
-      c->defer->kind = 0; c->defer->a = a; c->defer->grid = grid; c->defer->d = s.d; c->defer->m = s.m;
-      return GVI_OK;
-    }
-    if (!done && (c->variant == 5 || c->variant == 0)) done = dispatch_sreg(s, a, grid, st, c->sreg_pipe && s.table->Zq.p);
-    if (!done && !dispatch_reg(s, a, grid, st)) return fail(c, GVI_ERR_UNSUPPORTED, "dispatch_reg");
+    p.route = Route::Reg;
   } else {
+    p.route = Route::Generic;
     if (s.d > 32) return fail(c, GVI_ERR_UNSUPPORTED, "generic kernel supports d <= 32");
     const int d = s.d, m = s.m;
-    const size_t lds = (size_t)(2 * GEN_BS * (d + 1) + GEN_BS + d * d + d + m * d + 2 * m) * 8;
-    if (lds > 160 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "generic kernel LDS budget");
-    GVICK(allow_lds(c, (const void*)moments_generic_kernel, 160 * 1024));
-    hipLaunchKernelGGL(moments_generic_kernel, dim3(s.K, s.nchunk), dim3(GEN_BS), lds, st, a);
-  }
-  HIPCK(c, hipGetLastError());
-  if (prof) {
-    HIPCK(c, hipEventRecord(s.ev[which][1], st));
-    s.ev_set[which] = true;
+    p.lds = (size_t)(2 * GEN_BS * (d + 1) + GEN_BS + d * d + d + m * d + 2 * m) * 8;
+    if (p.lds > 160 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "generic kernel LDS budget");
+    p.grid = dim3(s.K, s.nchunk);
   }
   return GVI_OK;
+}
+
+// the launch a plan describes, on its own
+gvi_status launch_plan(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t st) {
+  const MomArgs& a = p.a;
+  const bool full = p.full != 0;
+  bool hit = true;
+  gvi_status rc = GVI_OK;
+  switch (p.route) {
+    case Route::Empty:
+      return GVI_OK;
+    case Route::Closed:
+      hipLaunchKernelGGL(moments_closed_kernel, p.grid, dim3(64), 0, st, a);
+      break;
+    case Route::Orbit:
+      hit = with_orbit_instance(s.m, p.smax, [&]<int M, int SMAX, int WAVES, bool PAIR>(OrbitInst<M, SMAX, WAVES, PAIR>) {
+        launch_orbit_t<M, SMAX, WAVES>(p.oa, full, s.all_pos, p.grid, p.lds, st);
+      });
+      break;
+    case Route::OrbitPsi:
+      hit = with_orbit_psi_instance(s.kind, [&]<int KIND>(OrbitPsiInst<KIND>) { rc = launch_orbit_psi_t<KIND>(c, p.pa, full, p.grid, p.lds, st); });
+      break;
+    case Route::Split:
+      hit = with_split_instance(s.d, s.m, [&]<int D, int R>(SplitInst<D, R>) { rc = launch_split<D, R>(c, a, p.grid, st); });
+      break;
+    case Route::Sreg:
+      hit = with_sreg_instance(s.kind, s.d, s.m, [&]<int D, int M, bool PIPE>(SregInst<D, M, PIPE>) { launch_sreg<D, M>(a, p.grid, st, p.pipe); });
+      break;
+    case Route::Scost:
+      hit = with_scost_instance(s.kind, s.d, s.m, [&]<int D, int M>(ScostInst<D, M>) {
+        hipLaunchKernelGGL((moments_scost_kernel<D, M, 2>), p.grid, dim3(256), 0, st, a);
+      });
+      break;
+    case Route::Reg:
+      hit = with_reg_instance(s.kind, s.d, s.m, [&]<int D, typename Psi>(RegInst<D, Psi>) { launch_reg<D, Psi>(a, p.grid, st); });
+      break;
+    case Route::Generic:
+      GVICK(allow_lds(c, (const void*)moments_generic_kernel, 160 * 1024));
+      hipLaunchKernelGGL(moments_generic_kernel, p.grid, dim3(GEN_BS), p.lds, st, a);
+      break;
+  }
+  if (!hit) return fail(c, GVI_ERR_UNSUPPORTED, "planned route without a kernel instance");
+  GVICK(rc);
+  HIPCK(c, hipGetLastError());
+  return GVI_OK;
+}
+
+// ---- shared pieces of the resident factor stage (prep_all / epilogue_all / fused / block3 launches) ----
+// warm-started Jacobi of the symmetric-root products: the set's last eigenvectors go to the launch; a cold start every 32nd
+// prep bounds the drift
+gvi_status warm_start_of(gvi_ctx* ctx, FactorSet& s, FactorDev& f) {
+  if (!ctx->warm_start) return GVI_OK;
+  if (s.Vws.bytes == 0) { HIPCK(ctx, s.Vws.ensure((size_t)s.K * s.d * s.d * 8)); s.warm_count = 0; }
+  f.Vws = s.Vws.d();
+  f.warm = (s.warm_count % 32) != 0;
+  s.warm_count++;
+  return GVI_OK;
+}
+
+// The pending gather of NGD slot i goes into the launch that preps the slot (Args: PrepList / FusedArgs / Block3Args, whose
+// gather fields agree).  Returns the workgroups of `block` lanes the launch needs behind its own for the trial mean.
+template <class Args>
+unsigned take_gather(gvi_ctx* ctx, int i, Args& A, int block) {
+  NgdState& g = ctx->ngd;
+  NgdState::GatherPending& gp = g.gpend[i];
+  if (!gp.on) return 0;
+  const size_t T = ctx->T, nn = nn_(ctx);
+  A.gather = 1; A.n = ctx->n;
+  A.gmu = gp.dmu ? gp.mu_from : g.mu[i].d();
+  A.gdmu = gp.dmu; A.gstep = gp.step;
+  A.SigD = g.Sig[i].d(); A.SigU = g.Sig[i].d() + T * nn;
+  A.mu_out = g.mu[i].d(); A.nmu = (int64_t)T * ctx->n;
+  gp.on = false;
+  return A.gdmu ? (unsigned)((A.nmu + block - 1) / block) : 0u;
+}
+
+// The tail of a launch that ends the factor stage.  publish_slot >= 0: the launch also sums the costs of its `nitems`
+// factors and publishes the cost of NGD slot `publish_slot` under the next sequence number.
+gvi_status fill_epi_tail(gvi_ctx* ctx, int nitems, int publish_slot, EpiTail* out) {
+  EpiTail& tail = *out;
+  tail.on = 0; tail.acc = nullptr; tail.half_logdet = nullptr; tail.host_out = nullptr; tail.seq = 0.0; tail.counter = nullptr;
+  tail.pred = ctx->cur_pred; tail.pred_val = ctx->cur_pred_val;
+  tail.accept = nullptr; tail.cost_dev = nullptr; tail.slot_cur = tail.slot_trial = 0; tail.c0_use_imm = 1; tail.c0_imm = 0.0;
+  tail.safe = ctx->safe_publish ? 1 : 0;
+  if (publish_slot < 0) return GVI_OK;
+  const size_t need = (size_t)128 * (2 + (size_t)nitems / EPI_GROUP);
+  if (ctx->epi_counter.bytes < need) {
+    HIPCK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCK(ctx, ctx->epi_counter.ensure(need));
+    HIPCK(ctx, hipMemsetAsync(ctx->epi_counter.p, 0, need, ctx->stream));
+  }
+  ctx->seq += 1.0;
+  tail.on = 1; tail.acc = ctx->ngd.exch1.d(); tail.half_logdet = ctx->ngd.hld[publish_slot].d();
+  tail.host_out = pub_slot(ctx); tail.seq = ctx->seq; tail.counter = (unsigned*)ctx->epi_counter.p;
+  if (ctx->pipe_tail) {
+    tail.accept = ctx->pipe_dev.d() + ctx->pub_ring; tail.cost_dev = ctx->pipe_dev.d() + 2;   // accept word of THIS ring slot
+    tail.slot_cur = 1 - publish_slot; tail.slot_trial = publish_slot;
+    tail.c0_use_imm = ctx->pipe_c0_imm ? 1 : 0; tail.c0_imm = ctx->pipe_c0;
+  }
+  return GVI_OK;
+}
+
+// ---- profile bracket of a factor launch (gvi_profile_enable / gvi_profile_last) ----
+// The events live on the set the launch is booked on: s.ev[0 = moments | 1 = cost][start | stop].  Sampling: with
+// profile_all every eligible launch, else every profile_every-th eligible one (profile_count).  around: the pair is recorded
+// round the launch; else the launch carries e0 / e1 itself (hipExtLaunchKernelGGL).
+struct ProfBracket {
+  FactorSet* s = nullptr;      // null: this launch is not sampled
+  int which = 0;
+  bool around = true;
+  hipStream_t st = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+gvi_status prof_open(gvi_ctx* c, FactorSet& s, int which, bool eligible, bool around, hipStream_t st, ProfBracket* b) {
+  *b = ProfBracket();
+  if (!c->profile || !eligible) return GVI_OK;
+  if (!c->profile_all && (c->profile_count++ % c->profile_every) != 0) return GVI_OK;
+  for (int e = 0; e < 2; ++e)
+    if (!s.ev[which][e]) HIPCK(c, hipEventCreate(&s.ev[which][e]));
+  b->s = &s; b->which = which; b->around = around; b->st = st;
+  b->e0 = s.ev[which][0]; b->e1 = s.ev[which][1];
+  if (around) HIPCK(c, hipEventRecord(b->e0, st));
+  return GVI_OK;
+}
+gvi_status prof_close(gvi_ctx* c, const ProfBracket& b) {
+  if (!b.s) return GVI_OK;
+  if (b.around) HIPCK(c, hipEventRecord(b.e1, b.st));
+  b.s->ev_set[b.which] = true;
+  return GVI_OK;
+}
+
+// a plan's launch on its own, bracketed: every launch under profile_all, else the full pass of set 0
+gvi_status launch_single(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t st) {
+  if (p.route == Route::Empty) return GVI_OK;
+  ProfBracket b;
+  GVICK(prof_open(c, s, p.full ? 0 : 1, c->profile_all || (p.full && &s == c->sets[0].get()), true, st, &b));
+  GVICK(launch_plan(c, s, p, st));
+  return prof_close(c, b);
+}
+
+// moments (full=1) or cost (full=0) pass for one set; prep must have run for (mu, Sigma).
+gvi_status run_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double* psi_ext, int full) {
+  MomPlan p;
+  GVICK(plan_moments(c, s, mu, psi_ext, full, &p));
+  return launch_single(c, s, p, c->stream);
 }
 
 gvi_status run_epilogue(gvi_ctx* c, FactorSet& s, int full, double* Ephi, double* cost, double* Vdmu,
@@ -1851,12 +1979,7 @@ static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
     if (s->prep_slot == i) continue;
     s->prep_slot = i;
     L.f[L.nsets] = s->dev();
-    if (ctx->warm_start) {                 // warm-started Jacobi; a cold start every 32nd prep bounds the drift
-      if (s->Vws.bytes == 0) { HIPCK(ctx, s->Vws.ensure((size_t)s->K * s->d * s->d * 8)); s->warm_count = 0; }
-      L.f[L.nsets].Vws = s->Vws.d();
-      L.f[L.nsets].warm = (s->warm_count % 32) != 0;
-      s->warm_count++;
-    }
+    GVICK(warm_start_of(ctx, *s, L.f[L.nsets]));
     L.mu[L.nsets] = s->mu_k[i].d();
     L.Sigma[L.nsets] = s->Sigma_k[i].d();
     L.start[L.nsets] = (const int32_t*)s->dstart.p;
@@ -1867,17 +1990,7 @@ static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
     ++L.nsets;
   }
   if (L.nsets == 0) return GVI_OK;
-  int extra = 0;
-  if (g.gpend[i].on) {
-    const size_t T = ctx->T, nn = nn_(ctx);
-    L.gather = 1; L.n = ctx->n;
-    L.gmu = g.gpend[i].dmu ? g.gpend[i].mu_from : g.mu[i].d();
-    L.gdmu = g.gpend[i].dmu; L.gstep = g.gpend[i].step;
-    L.SigD = g.Sig[i].d(); L.SigU = g.Sig[i].d() + T * nn;
-    L.mu_out = g.mu[i].d(); L.nmu = (int64_t)T * ctx->n;
-    if (L.gdmu) extra = (int)((L.nmu + 63) / 64);
-    g.gpend[i].on = false;
-  }
+  const unsigned extra = take_gather(ctx, i, L, 64);
   const int dp = dmax + (dmax & 1);
   const size_t lds = (size_t)(4 * dmax * dmax + 2 * dp + 3 * dmax + (dp + 1) / 2 + 1 + dmax * dmax + dmax) * 8 + 16;
   const dim3 grid(L.koff[L.nsets] + extra);
@@ -1917,26 +2030,7 @@ static gvi_status ngd_epilogue_all(gvi_ctx* ctx, int full, int publish_slot = -1
   const size_t lds = (epilogue_lds_doubles(dmax) + 256) * 8;       // + the tail's 256-leaf tree
   if (L.koff[L.nsets] == 0) return GVI_OK;
   EpiTail tail;
-  tail.on = 0; tail.acc = nullptr; tail.half_logdet = nullptr; tail.host_out = nullptr; tail.seq = 0.0; tail.counter = nullptr;
-  tail.pred = ctx->cur_pred; tail.pred_val = ctx->cur_pred_val;
-  tail.accept = nullptr; tail.cost_dev = nullptr; tail.slot_cur = tail.slot_trial = 0; tail.c0_use_imm = 1; tail.c0_imm = 0.0;
-  tail.safe = ctx->safe_publish ? 1 : 0;
-  if (publish_slot >= 0) {
-    const size_t need = (size_t)128 * (2 + (size_t)L.koff[L.nsets] / EPI_GROUP);
-    if (ctx->epi_counter.bytes < need) {
-      HIPCK(ctx, hipStreamSynchronize(ctx->stream));
-      HIPCK(ctx, ctx->epi_counter.ensure(need));
-      HIPCK(ctx, hipMemsetAsync(ctx->epi_counter.p, 0, need, ctx->stream));
-    }
-    ctx->seq += 1.0;
-    tail.on = 1; tail.acc = ctx->ngd.exch1.d(); tail.half_logdet = ctx->ngd.hld[publish_slot].d();
-    tail.host_out = pub_slot(ctx); tail.seq = ctx->seq; tail.counter = (unsigned*)ctx->epi_counter.p;
-    if (ctx->pipe_tail) {
-      tail.accept = ctx->pipe_dev.d() + ctx->pub_ring; tail.cost_dev = ctx->pipe_dev.d() + 2;   // accept word of THIS ring slot
-      tail.slot_cur = 1 - publish_slot; tail.slot_trial = publish_slot;
-      tail.c0_use_imm = ctx->pipe_c0_imm ? 1 : 0; tail.c0_imm = ctx->pipe_c0;
-    }
-  }
+  GVICK(fill_epi_tail(ctx, L.koff[L.nsets], publish_slot, &tail));
   CostList cl{};
   cl.nsets = L.nsets;
   for (int si = 0; si < L.nsets; ++si) { cl.cost[si] = L.e[si].cost; cl.K[si] = L.e[si].f.K; }
@@ -1995,7 +2089,7 @@ static gvi_status ngd_refresh(gvi_ctx* ctx, int i) {
 // sum over sets of sum_k E[psi]/T_k at slot i -> exch1[0].  Everything stays on ONE stream: side streams
 // share the hardware queue on this part and every cross-stream dependency costs a 6-30 us barrier
 // packet (profiles/r01_d_*); the small sets ride along inside the fused prep / epilogue launches.
-static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full);
+static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full, const MomPlan* P = nullptr);
 
 // publish = true (single-process iteration): the same launch also writes {cost, half log-det, sequence} to the
 // host-mapped slot, so no separate publish_kernel follows
@@ -2288,117 +2382,91 @@ gvi_status gvi_ngd_factor_costs(gvi_ctx* ctx, int set_id, double* costs) {
   return sync(ctx);
 }
 
-// full moments pass of every set at NGD slot `slot` (per-factor Vdmu / Vddmu / E[psi] / cost)
-// All sets' moments (full = 1) or cost (full = 0) launches at slot.  The chain pattern -- set 0 binary priors (d = 2n,
-// m = n), set 1 unary factors (d = m = n), both on the SGPR-operand kernels -- goes out as ONE launch.
-static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full) {
+// the chain pattern of the two-set SGPR launches (moments_sreg_pair_kernel / moments_scost_pair_kernel <12, 6, 6, 6>): set 0
+// binary priors d = 12, set 1 unary factors d = 6
+static bool chain_pair_shape(const FactorSet& s0, const FactorSet& s1) {
+  return s0.kind == KIND_QUAD_PRIOR && s1.kind == KIND_FIXED_PRIOR && s0.d == 12 && s1.d == 6;
+}
+
+// the planning graph of the three-set launches (moments_planar3_kernel, factor_block3_kernel): d = 8 priors + d = 4
+// hinge-on-SDF obstacle factors + d = 4 anchors, registered in this order, none empty
+static bool planar_shape(const gvi_ctx* ctx) {
+  if (ctx->sets.size() != 3 || ctx->variant != 0 || ctx->prefer_opsi) return false;
+  const FactorSet &s0 = *ctx->sets[0], &s1 = *ctx->sets[1], &s2 = *ctx->sets[2];
+  return s0.kind == KIND_QUAD_PRIOR && s0.d == 8 && s0.m == 4 && s1.kind == KIND_HINGE_SDF_2D && s1.d == 4 &&
+         s2.kind == KIND_FIXED_PRIOR && s2.d == 4 && !s0.closed_form && !s2.closed_form && s0.K > 0 && s1.K > 0 && s2.K > 0;
+}
+
+// P: [MAX_SETS]
+static gvi_status plan_sets(gvi_ctx* ctx, int slot, int full, MomPlan* P) {
+  if ((int)ctx->sets.size() > MAX_SETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
+  for (size_t i = 0; i < ctx->sets.size(); ++i)
+    GVICK(plan_moments(ctx, *ctx->sets[i], ctx->sets[i]->mu_k[slot].d(), nullptr, full, &P[i]));
+  return GVI_OK;
+}
+
+// All sets' moments (full = 1) or cost (full = 0) launches at NGD slot `slot`: every set is planned once (P non-null: by the
+// caller already), then the plans decide.  Two sign-orbit sets of one instance with sgn = +1, the chain pattern on the
+// SGPR-operand kernels (Sreg / Sreg in the full pass, Scost / Scost in the cost pass) and the planning graph on three
+// lane-per-point kernels go out as ONE launch; every other combination as one launch per set.
+static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full, const MomPlan* P) {
   if (full) ++ctx->n_full_pass; else ++ctx->n_cost_pass;
-  if (ctx->pair_fuse && ctx->sets.size() == 2 && !ctx->profile_all) {
-    FactorSet& s0 = *ctx->sets[0];
-    FactorSet& s1 = *ctx->sets[1];
-    const bool shape = s0.kind == KIND_QUAD_PRIOR && s1.kind == KIND_FIXED_PRIOR && s0.d == 12 && s1.d == 6 &&
-                       !s0.closed_form && !s1.closed_form && s0.K > 0 && s1.K > 0;
-    const bool shape_orbit = orbit_supported(ctx, s0) && orbit_supported(ctx, s1) && s0.m == s1.m && s0.all_pos && s1.all_pos &&
-                             !s0.closed_form && !s1.closed_form && s0.K > 0 && s1.K > 0;
-    if (shape || shape_orbit) {
-      gvi_ctx::Deferred d0, d1;
-      ctx->defer = &d0;
-      gvi_status st = run_moments(ctx, s0, s0.mu_k[slot].d(), nullptr, full);
-      if (st == GVI_OK) { ctx->defer = &d1; st = run_moments(ctx, s1, s1.mu_k[slot].d(), nullptr, full); }
-      ctx->defer = nullptr;
-      GVICK(st);
-      const int want = full ? 0 : 1;
-      if (d0.kind == 2 && d1.kind == 2) {              // both sets on the sign-orbit kernel
-        const bool prof = ctx->profile && full && (ctx->profile_count++ % ctx->profile_every) == 0;
-        if (prof) {
-          for (int e = 0; e < 2; ++e)
-            if (!s0.ev[0][e]) HIPCK(ctx, hipEventCreate(&s0.ev[0][e]));
-        }
-        launch_orbit_pair(d0.oa, d1.oa, d0.m, std::max(d0.smax, d1.smax), full != 0, ctx->stream, ctx->orbit_stack,
-                          prof ? s0.ev[0][0] : nullptr, prof ? s0.ev[0][1] : nullptr);
-        HIPCK(ctx, hipGetLastError());
-        if (prof) s0.ev_set[0] = true;
-        s0.fused_pair = s1.fused_pair = true;
-        return GVI_OK;
-      }
-      if (d0.kind == 2 || d1.kind == 2) {              // only one of them: issue both on their own
-        s0.fused_pair = s1.fused_pair = false;
-        if (d0.kind >= 0) GVICK(run_moments(ctx, s0, s0.mu_k[slot].d(), nullptr, full));
-        if (d1.kind >= 0) GVICK(run_moments(ctx, s1, s1.mu_k[slot].d(), nullptr, full));
-        return GVI_OK;
-      }
-      if (d0.kind == want && d1.kind == want) {
-        const int nb0 = (int)(d0.grid.x * d0.grid.y), nb1 = (int)(d1.grid.x * d1.grid.y);
-        const bool prof = ctx->profile && full && (ctx->profile_count++ % ctx->profile_every) == 0;
-        if (prof) {
-          for (int e = 0; e < 2; ++e)
-            if (!s0.ev[0][e]) HIPCK(ctx, hipEventCreate(&s0.ev[0][e]));
-          HIPCK(ctx, hipEventRecord(s0.ev[0][0], ctx->stream));
-        }
-        if (full && ctx->sreg_pipe && s0.table->Zq.p && s1.table->Zq.p)    // every block: one prior item + strided unary items
-          hipLaunchKernelGGL((moments_sreg_pair_kernel<12, 6, 6, 6, true, true>), dim3(std::max(nb0, nb1)), dim3(256), 0, ctx->stream,
-                             d0.a, d1.a, (int)d0.grid.x, nb0, (int)d1.grid.x);
-        else if (full)
-          hipLaunchKernelGGL((moments_sreg_pair_kernel<12, 6, 6, 6, true>), dim3(nb0 + nb1), dim3(256), 0, ctx->stream, d0.a,
-                             d1.a, (int)d0.grid.x, nb0, (int)d1.grid.x);
-        else
-          hipLaunchKernelGGL((moments_scost_pair_kernel<12, 6, 6, 6, 2>), dim3(nb0 + nb1), dim3(256), 0, ctx->stream, d0.a, d1.a,
-                             (int)d0.grid.x, nb0, (int)d1.grid.x);
-        HIPCK(ctx, hipGetLastError());
-        if (prof) { HIPCK(ctx, hipEventRecord(s0.ev[0][1], ctx->stream)); s0.ev_set[0] = true; }
-        s0.fused_pair = s1.fused_pair = true;
-        return GVI_OK;
-      }
-      // a deferred launch that did not pair up: issue it on its own below (run_moments again, undeferred)
-      if (d0.kind < 0 && d1.kind < 0) { s0.fused_pair = s1.fused_pair = false; return GVI_OK; }   // both already launched
-      if (d0.kind >= 0 && d1.kind < 0) { s0.fused_pair = false; return run_moments(ctx, s0, s0.mu_k[slot].d(), nullptr, full); }
-      if (d1.kind >= 0 && d0.kind < 0) { s1.fused_pair = false; return run_moments(ctx, s1, s1.mu_k[slot].d(), nullptr, full); }
+  MomPlan own[MAX_SETS];
+  if (!P) { GVICK(plan_sets(ctx, slot, full, own)); P = own; }
+  const size_t ns = ctx->sets.size();
+  const bool fuse = ctx->pair_fuse && !ctx->profile_all;
+  if (fuse && ns == 2) {
+    FactorSet &s0 = *ctx->sets[0], &s1 = *ctx->sets[1];
+    const int smax = std::max(P[0].smax, P[1].smax);
+    ProfBracket b;
+    if (P[0].route == Route::Orbit && P[1].route == Route::Orbit && s0.m == s1.m && s0.all_pos && s1.all_pos &&
+        orbit_pair_supported(s0.m, smax)) {
+      GVICK(prof_open(ctx, s0, 0, full != 0, false, ctx->stream, &b));
+      launch_orbit_pair(P[0].oa, P[1].oa, s0.m, smax, full != 0, ctx->stream, ctx->orbit_stack, b.e0, b.e1);
+      HIPCK(ctx, hipGetLastError());
+      s0.fused_pair = s1.fused_pair = true;
+      return prof_close(ctx, b);
+    }
+    const Route want = full ? Route::Sreg : Route::Scost;
+    if (chain_pair_shape(s0, s1) && P[0].route == want && P[1].route == want) {
+      const MomArgs &a0 = P[0].a, &a1 = P[1].a;
+      const int nbx0 = (int)P[0].grid.x, nbx1 = (int)P[1].grid.x;
+      const int nb0 = nbx0 * (int)P[0].grid.y, nb1 = nbx1 * (int)P[1].grid.y;
+      GVICK(prof_open(ctx, s0, 0, full != 0, true, ctx->stream, &b));
+      if (full && P[0].pipe && P[1].pipe)                    // every block: one prior item + strided unary items
+        hipLaunchKernelGGL((moments_sreg_pair_kernel<12, 6, 6, 6, true, true>), dim3(std::max(nb0, nb1)), dim3(256), 0, ctx->stream,
+                           a0, a1, nbx0, nb0, nbx1);
+      else if (full)
+        hipLaunchKernelGGL((moments_sreg_pair_kernel<12, 6, 6, 6, true>), dim3(nb0 + nb1), dim3(256), 0, ctx->stream, a0, a1, nbx0, nb0, nbx1);
+      else
+        hipLaunchKernelGGL((moments_scost_pair_kernel<12, 6, 6, 6, 2>), dim3(nb0 + nb1), dim3(256), 0, ctx->stream, a0, a1, nbx0, nb0, nbx1);
+      HIPCK(ctx, hipGetLastError());
+      s0.fused_pair = s1.fused_pair = true;
+      return prof_close(ctx, b);
     }
   }
-  // the planning graph: d = 8 priors + d = 4 hinge-on-SDF obstacle factors + d = 4 anchors, all three on lane-per-point
-  // register kernels -> ONE launch (moments_planar3_kernel); any other shape: one launch per set
-  if (ctx->pair_fuse && ctx->sets.size() == 3 && !ctx->profile_all && ctx->variant == 0 && !ctx->prefer_opsi) {
-    FactorSet& s0 = *ctx->sets[0];
-    FactorSet& s1 = *ctx->sets[1];
-    FactorSet& s2 = *ctx->sets[2];
-    const bool shape = s0.kind == KIND_QUAD_PRIOR && s0.d == 8 && s0.m == 4 && s1.kind == KIND_HINGE_SDF_2D && s1.d == 4 &&
-                       s2.kind == KIND_FIXED_PRIOR && s2.d == 4 && !s0.closed_form && !s2.closed_form && s0.K > 0 && s1.K > 0 && s2.K > 0;
-    if (shape) {
-      gvi_ctx::Deferred dq[3];
-      FactorSet* ss[3] = {&s0, &s1, &s2};
-      gvi_status st = GVI_OK;
-      for (int q = 0; q < 3 && st == GVI_OK; ++q) {
-        dq[q].capture_any = true;
-        ctx->defer = &dq[q];
-        st = run_moments(ctx, *ss[q], ss[q]->mu_k[slot].d(), nullptr, full);
-      }
-      ctx->defer = nullptr;
-      GVICK(st);
-      if (dq[0].kind == 3 && dq[1].kind == 3 && dq[2].kind == 3) {
-        const int nb0 = (int)(dq[0].grid.x * dq[0].grid.y), nb1 = (int)(dq[1].grid.x * dq[1].grid.y), nb2 = (int)(dq[2].grid.x * dq[2].grid.y);
-        const bool prof = ctx->profile && full && (ctx->profile_count++ % ctx->profile_every) == 0;
-        if (prof) {                                          // the bracket is booked on the obstacle set (the dominant one)
-          for (int e = 0; e < 2; ++e)
-            if (!s1.ev[0][e]) HIPCK(ctx, hipEventCreate(&s1.ev[0][e]));
-          HIPCK(ctx, hipEventRecord(s1.ev[0][0], ctx->stream));
-        }
-        if (full)
-          hipLaunchKernelGGL((moments_planar3_kernel<true>), dim3(nb0 + nb1 + nb2), dim3(256), 0, ctx->stream, dq[0].a, dq[1].a, dq[2].a,
-                             (int)dq[0].grid.x, nb0, (int)dq[1].grid.x, nb1, (int)dq[2].grid.x, (ctx->sreg_pipe && s0.table->Zq.p) ? 1 : 0);
-        else
-          hipLaunchKernelGGL((moments_planar3_kernel<false>), dim3(nb0 + nb1 + nb2), dim3(256), 0, ctx->stream, dq[0].a, dq[1].a, dq[2].a,
-                             (int)dq[0].grid.x, nb0, (int)dq[1].grid.x, nb1, (int)dq[2].grid.x, 0);
-        HIPCK(ctx, hipGetLastError());
-        if (prof) { HIPCK(ctx, hipEventRecord(s1.ev[0][1], ctx->stream)); s1.ev_set[0] = true; }
-        for (auto* q : ss) q->fused_pair = false;
-        return GVI_OK;
-      }
-      for (int q = 0; q < 3; ++q)                            // some set took another route: whatever was captured goes out on its own
-        if (dq[q].kind >= 0) { ss[q]->fused_pair = false; GVICK(run_moments(ctx, *ss[q], ss[q]->mu_k[slot].d(), nullptr, full)); }
-      return GVI_OK;
+  if (fuse && planar_shape(ctx) && lane_per_point(P[0]) && lane_per_point(P[1]) && lane_per_point(P[2])) {
+    int nbx[3], nb[3];
+    for (int q = 0; q < 3; ++q) {
+      ctx->sets[q]->fused_pair = false;
+      nbx[q] = (ctx->sets[q]->K + 3) / 4;
+      nb[q] = nbx[q] * P[q].a.nchunk;
     }
+    ProfBracket b;                                           // the bracket is booked on the obstacle set (the dominant one)
+    GVICK(prof_open(ctx, *ctx->sets[1], 0, full != 0, true, ctx->stream, &b));
+    if (full)
+      hipLaunchKernelGGL((moments_planar3_kernel<true>), dim3(nb[0] + nb[1] + nb[2]), dim3(256), 0, ctx->stream, P[0].a, P[1].a, P[2].a,
+                         nbx[0], nb[0], nbx[1], nb[1], nbx[2], P[0].pipe ? 1 : 0);
+    else
+      hipLaunchKernelGGL((moments_planar3_kernel<false>), dim3(nb[0] + nb[1] + nb[2]), dim3(256), 0, ctx->stream, P[0].a, P[1].a, P[2].a,
+                         nbx[0], nb[0], nbx[1], nb[1], nbx[2], 0);
+    HIPCK(ctx, hipGetLastError());
+    return prof_close(ctx, b);
   }
-  for (auto& s : ctx->sets) { s->fused_pair = false; GVICK(run_moments(ctx, *s, s->mu_k[slot].d(), nullptr, full)); }
+  for (size_t i = 0; i < ns; ++i) {
+    ctx->sets[i]->fused_pair = false;
+    GVICK(launch_single(ctx, *ctx->sets[i], P[i], ctx->stream));
+  }
   return GVI_OK;
 }
 
@@ -2412,31 +2480,35 @@ static int fused_nblk(const gvi_ctx* ctx) {
   return per <= FUSED_MAX_ITEMS ? nblk : 0;
 }
 
+// key of the fused instance (with_fused_instance): m and the second dimension of a one-set problem as the chain pattern has them
+struct FusedKey { int m, smax, d0, d1; };
+static FusedKey fused_key(const gvi_ctx* ctx) {
+  FusedKey k{ctx->sets[0]->m, 0, ctx->sets[0]->d, ctx->sets.size() > 1 ? ctx->sets[1]->d : ctx->sets[0]->d / 2};
+  for (auto& sp : ctx->sets) k.smax = std::max(k.smax, sp->table->orb.smax);
+  return k;
+}
+
 static bool fused_ok(const gvi_ctx* ctx, int slot) {
   if (!ctx->fused || !ctx->pair_fuse || ctx->profile_all || ctx->sets.empty() || ctx->sets.size() > 2) return false;
   if (ctx->update_rule != GVI_RULE_NGD) return false;     // the JKO map reads the sets' Sigma^-1 after the pass
-  const int m = ctx->sets[0]->m;
+  const FusedKey k = fused_key(ctx);
   for (auto& sp : ctx->sets) {
     const FactorSet& s = *sp;
-    if (!orbit_supported(ctx, s) || !s.all_pos || s.closed_form || s.K <= 0 || s.m != m) return false;
+    if (!orbit_supported(ctx, s) || !s.all_pos || s.closed_form || s.K <= 0 || s.m != k.m) return false;
     if (s.prep_slot == slot) return false;          // products already resident: the plain route skips the prep
-    if (s.table->orb.tile_s.empty()) return false;
   }
-  // instantiated shapes: the chain patterns of BASELINE configs[1..3] (binary prior d = 2n + unary factor d = n), Cholesky route
-  const int d0 = ctx->sets[0]->d, d1 = ctx->sets.size() > 1 ? ctx->sets[1]->d : d0 / 2;
-  if (!((m == 6 && d0 == 12 && d1 == 6) || (m == 2 && d0 == 4 && d1 == 2))) return false;
+  if (!with_fused_instance(k.m, k.smax, k.d0, k.d1, any_instance)) return false;
   for (auto& sp : ctx->sets)
-    if (!sp->dev().chol) return false;
+    if (!sp->dev().chol) return false;              // the instances are compiled for the Cholesky route
   return fused_nblk(ctx) > 0;
 }
 
 static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot) {
-  NgdState& g = ctx->ngd;
   FusedArgs A{};
   A.nsets = (int)ctx->sets.size();
   A.koff[0] = 0;
-  int smax = 0, dmax = 0, copies = 1;
-  const int m = ctx->sets[0]->m;
+  int dmax = 0, copies = 1;
+  const FusedKey key = fused_key(ctx);
   A.nblk = fused_nblk(ctx);
   for (int si = 0; si < A.nsets; ++si) {
     FactorSet& s = *ctx->sets[si];
@@ -2445,13 +2517,8 @@ static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot) {
     s.nchunk = 4; s.chunk = s.table->Np;
     s.use_reg = s.use_split = false; s.use_orbit = true; s.fused_pair = true;
     F.f = s.dev();
-    if (ctx->warm_start) {                 // (symmetric-root sets only; the Cholesky route ignores it)
-      if (s.Vws.bytes == 0) { HIPCK(ctx, s.Vws.ensure((size_t)s.K * s.d * s.d * 8)); s.warm_count = 0; }
-      F.f.Vws = s.Vws.d();
-      F.f.warm = (s.warm_count % 32) != 0;
-      s.warm_count++;
-    }
-    GVICK(orbit_args(ctx, s, 1, &F.oa));
+    GVICK(warm_start_of(ctx, s, F.f));     // (symmetric-root sets only; the Cholesky route ignores it)
+    GVICK(orbit_args(ctx, s, &F.oa));
     F.oa.partial = nullptr;
     F.mu = s.mu_k[slot].d(); F.Sigma = s.Sigma_k[slot].d();
     F.start = s.chain_structured ? nullptr : (const int32_t*)s.dstart.p;      // null: start[k] == k, one dependent load less
@@ -2459,161 +2526,75 @@ static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot) {
     F.Ephi = s.Ephi.d(); F.cost = s.cost.d(); F.Vdmu = s.Vdmu.d(); F.Vddmu = s.Vddmu.d();
     A.koff[si + 1] = A.koff[si] + s.K;
     A.cl.cost[si] = s.cost.d(); A.cl.K[si] = s.K;
-    smax = std::max(smax, s.table->orb.smax);
     dmax = std::max(dmax, s.d);
     copies = std::max(copies, F.oa.copies);
   }
   // (the walk regions are sized for the widest set with the most accumulator copies: an upper bound for every set)
   const int items = 1 + (A.nsets > 1 ? (ctx->sets[1]->K + A.nblk - 1) / A.nblk : 0);      // most items of a block
-  const size_t lds = fused_lds_doubles(dmax, m, copies, items) * 8;
+  const size_t lds = fused_lds_doubles(dmax, key.m, copies, items) * 8;
   if (lds > 160 * 1024) return fail(ctx, GVI_ERR_UNSUPPORTED, "fused pass: LDS budget");
   A.cl.nsets = A.nsets;
   if (A.nsets == 1) A.koff[2] = A.koff[1];
-  unsigned extra = 0;
-  if (g.gpend[slot].on) {
-    const size_t T = ctx->T, nn = nn_(ctx);
-    A.gather = 1; A.n = ctx->n;
-    A.gmu = g.gpend[slot].dmu ? g.gpend[slot].mu_from : g.mu[slot].d();
-    A.gdmu = g.gpend[slot].dmu; A.gstep = g.gpend[slot].step;
-    A.SigD = g.Sig[slot].d(); A.SigU = g.Sig[slot].d() + T * nn;
-    A.mu_out = g.mu[slot].d(); A.nmu = (int64_t)T * ctx->n;
-    if (A.gdmu) extra = (unsigned)((A.nmu + 255) / 256);
-    g.gpend[slot].on = false;
-  }
-  EpiTail& tail = A.tail;
-  tail.on = 0; tail.pred = ctx->cur_pred; tail.pred_val = ctx->cur_pred_val; tail.c0_use_imm = 1;
-  tail.safe = ctx->safe_publish ? 1 : 0;
-  if (publish_slot >= 0) {
-    const size_t need = (size_t)128 * (2 + (size_t)A.koff[A.nsets] / EPI_GROUP);
-    if (ctx->epi_counter.bytes < need) {
-      HIPCK(ctx, hipStreamSynchronize(ctx->stream));
-      HIPCK(ctx, ctx->epi_counter.ensure(need));
-      HIPCK(ctx, hipMemsetAsync(ctx->epi_counter.p, 0, need, ctx->stream));
-    }
-    ctx->seq += 1.0;
-    tail.on = 1; tail.acc = g.exch1.d(); tail.half_logdet = g.hld[publish_slot].d();
-    tail.host_out = pub_slot(ctx); tail.seq = ctx->seq; tail.counter = (unsigned*)ctx->epi_counter.p;
-    if (ctx->pipe_tail) {
-      tail.accept = ctx->pipe_dev.d() + ctx->pub_ring; tail.cost_dev = ctx->pipe_dev.d() + 2;
-      tail.slot_cur = 1 - publish_slot; tail.slot_trial = publish_slot;
-      tail.c0_use_imm = ctx->pipe_c0_imm ? 1 : 0; tail.c0_imm = ctx->pipe_c0;
-    }
-  }
+  const unsigned extra = take_gather(ctx, slot, A, 256);
+  GVICK(fill_epi_tail(ctx, A.koff[A.nsets], publish_slot, &A.tail));
   ++ctx->n_full_pass;
-  FactorSet& s0 = *ctx->sets[0];
-  const bool prof = ctx->profile && (ctx->profile_count++ % ctx->profile_every) == 0;
-  if (prof)
-    for (int e = 0; e < 2; ++e)
-      if (!s0.ev[0][e]) HIPCK(ctx, hipEventCreate(&s0.ev[0][e]));
-  hipEvent_t e0 = prof ? s0.ev[0][0] : nullptr, e1 = prof ? s0.ev[0][1] : nullptr;
+  ProfBracket b;
+  GVICK(prof_open(ctx, *ctx->sets[0], 0, true, false, ctx->stream, &b));
   const unsigned grid = (unsigned)A.nblk + extra;
-  const int d0 = ctx->sets[0]->d, d1 = A.nsets > 1 ? ctx->sets[1]->d : d0 / 2;
-  if (m == 6 && smax <= 4 && d0 == 12 && d1 == 6) GVICK((launch_fused_t<6, 4, 4, 12, 6>(ctx, A, grid, lds, dmax, copies, items, e0, e1)));
-  else if (m == 6 && d0 == 12 && d1 == 6) GVICK((launch_fused_t<6, 6, 2, 12, 6>(ctx, A, grid, lds, dmax, copies, items, e0, e1)));
-  else if (m == 2 && d0 == 4 && d1 == 2) GVICK((launch_fused_t<2, 4, 4, 4, 2>(ctx, A, grid, lds, dmax, copies, items, e0, e1)));
-  else return fail(ctx, GVI_ERR_UNSUPPORTED, "fused pass: shape not instantiated");
+  gvi_status rc = GVI_OK;
+  if (!with_fused_instance(key.m, key.smax, key.d0, key.d1, [&]<int M, int SMAX, int WAVES, int D0, int D1>(FusedInst<M, SMAX, WAVES, D0, D1>) {
+        rc = launch_fused_t<M, SMAX, WAVES, D0, D1>(ctx, A, grid, lds, dmax, copies, items, b.e0, b.e1);
+      }))
+    return fail(ctx, GVI_ERR_UNSUPPORTED, "fused pass: shape not instantiated");
+  GVICK(rc);
   HIPCK(ctx, hipGetLastError());
-  if (prof) s0.ev_set[0] = true;
-  return GVI_OK;
+  return prof_close(ctx, b);
 }
 
 // ---- the planning graph's full pass as ONE launch (kernels_block.hpp) ----
-// The shape of moments_planar3_kernel (priors d = 8 / hinge on the SDF d = 4 / anchors d = 4, all on their lane-per-point
-// kernels), at most four chunks per factor (a workgroup's four waves take them), products
-// of this state not resident yet.  *done = false: not this shape -- the caller takes the three launches.
-static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, bool* done) {
-  *done = false;
-  if (!ctx->fused || !ctx->pair_fuse || ctx->profile_all || ctx->sets.size() != 3 || ctx->variant != 0 || ctx->prefer_opsi) return GVI_OK;
+// The shape of moments_planar3_kernel (planar_shape, all three on their lane-per-point kernels), at most four chunks per
+// factor (a workgroup's four waves take them), products of this state not resident yet.  *done = false: not this shape -- the
+// caller takes the three launches, with the plans made here where *planned.
+static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, MomPlan* P, bool* planned, bool* done) {
+  *done = *planned = false;
+  if (!ctx->fused || !ctx->pair_fuse || ctx->profile_all || !planar_shape(ctx)) return GVI_OK;
   if (ctx->update_rule != GVI_RULE_NGD) return GVI_OK;     // the JKO map reads the sets' Sigma^-1 after the pass
   FactorSet* ss[3] = {ctx->sets[0].get(), ctx->sets[1].get(), ctx->sets[2].get()};
-  FactorSet &s0 = *ss[0], &s1 = *ss[1], &s2 = *ss[2];
-  const bool shape = s0.kind == KIND_QUAD_PRIOR && s0.d == 8 && s0.m == 4 && s1.kind == KIND_HINGE_SDF_2D && s1.d == 4 &&
-                     s2.kind == KIND_FIXED_PRIOR && s2.d == 4 && !s0.closed_form && !s2.closed_form && s0.K > 0 && s1.K > 0 && s2.K > 0;
-  if (!shape) return GVI_OK;
   for (auto* q : ss)
     if (q->prep_slot == slot) return GVI_OK;                 // products already resident: the plain route skips the prep
-  if (!s0.dev().chol || s1.dev().chol || !s2.dev().chol) return GVI_OK;     // the products the kernel is compiled for (kernels_block.hpp)
-  NgdState& g = ctx->ngd;
+  if (!ss[0]->dev().chol || ss[1]->dev().chol || !ss[2]->dev().chol) return GVI_OK;     // the products the kernel is compiled for (kernels_block.hpp)
   // the sets' moments launches exactly as they would go out on their own (chunking, table pointers, partial buffers)
-  gvi_ctx::Deferred dq[3];
-  gvi_status st = GVI_OK;
-  for (int q = 0; q < 3 && st == GVI_OK; ++q) {
-    dq[q].capture_any = true;
-    ctx->defer = &dq[q];
-    st = run_moments(ctx, *ss[q], ss[q]->mu_k[slot].d(), nullptr, 1);
-  }
-  ctx->defer = nullptr;
-  GVICK(st);
-  bool ok = true;
-  for (int q = 0; q < 3; ++q) ok = ok && dq[q].kind == 3 && dq[q].grid.y <= 4 && (int)dq[q].grid.y == dq[q].a.nchunk;
-  if (!ok) {                                   // some set took another route: whatever was captured is re-planned by the caller
-    for (int q = 0; q < 3; ++q)
-      if (dq[q].kind < 0) return fail(ctx, GVI_ERR_STATE, "planning-graph pass: a set launched while its siblings were captured");
-    return GVI_OK;
-  }
+  GVICK(plan_sets(ctx, slot, 1, P));
+  *planned = true;
+  for (int q = 0; q < 3; ++q)
+    if (!lane_per_point(P[q]) || P[q].a.nchunk > 4) return GVI_OK;
   ++ctx->n_full_pass;
   Block3Args A{};
-  A.nitems = s0.K + s1.K + s2.K;
-  A.pipe = (ctx->sreg_pipe && s0.table->Zq.p) ? 1 : 0;
+  A.nitems = ss[0]->K + ss[1]->K + ss[2]->K;
+  A.pipe = P[0].pipe ? 1 : 0;
+  unsigned nblk = 0;
   for (int q = 0; q < 3; ++q) {
     FactorSet& s = *ss[q];
     BlockSet& B = A.s[q];
-    B.a = dq[q].a;
-    if (ctx->warm_start) {                 // warm-started Jacobi of the symmetric-root sets, as ngd_prep_all
-      if (s.Vws.bytes == 0) { HIPCK(ctx, s.Vws.ensure((size_t)s.K * s.d * s.d * 8)); s.warm_count = 0; }
-      B.a.f.Vws = s.Vws.d();
-      B.a.f.warm = (s.warm_count % 32) != 0;
-      s.warm_count++;
-    }
+    B.a = P[q].a;
+    GVICK(warm_start_of(ctx, s, B.a.f));       // warm-started Jacobi of the symmetric-root sets, as ngd_prep_all
     B.start = (const int32_t*)s.dstart.p;
     B.mu_k = s.mu_k[slot].d(); B.Sigma_k = s.Sigma_k[slot].d();
     B.Ephi = s.Ephi.d(); B.cost = s.cost.d(); B.Vdmu = s.Vdmu.d(); B.Vddmu = s.Vddmu.d();
+    A.cl.cost[q] = s.cost.d(); A.cl.K[q] = s.K;
+    nblk += (unsigned)block3_blocks(s.K, B.a.nchunk);
     s.prep_slot = slot;                        // the products go to memory as prep_all_kernel leaves them
     s.fused_pair = false;
   }
-  unsigned extra = 0;
-  if (g.gpend[slot].on) {
-    const size_t T = ctx->T, nn = nn_(ctx);
-    A.gather = 1; A.n = ctx->n;
-    A.gmu = g.gpend[slot].dmu ? g.gpend[slot].mu_from : g.mu[slot].d();
-    A.gdmu = g.gpend[slot].dmu; A.gstep = g.gpend[slot].step;
-    A.SigD = g.Sig[slot].d(); A.SigU = g.Sig[slot].d() + T * nn;
-    A.mu_out = g.mu[slot].d(); A.nmu = (int64_t)T * ctx->n;
-    if (A.gdmu) extra = (unsigned)((A.nmu + 255) / 256);
-    g.gpend[slot].on = false;
-  }
-  EpiTail& tail = A.tail;
-  tail.on = 0; tail.pred = ctx->cur_pred; tail.pred_val = ctx->cur_pred_val; tail.c0_use_imm = 1;
-  tail.safe = ctx->safe_publish ? 1 : 0;
-  if (publish_slot >= 0) {
-    const size_t need = (size_t)128 * (2 + (size_t)A.nitems / EPI_GROUP);
-    if (ctx->epi_counter.bytes < need) {
-      HIPCK(ctx, hipStreamSynchronize(ctx->stream));
-      HIPCK(ctx, ctx->epi_counter.ensure(need));
-      HIPCK(ctx, hipMemsetAsync(ctx->epi_counter.p, 0, need, ctx->stream));
-    }
-    ctx->seq += 1.0;
-    tail.on = 1; tail.acc = g.exch1.d(); tail.half_logdet = g.hld[publish_slot].d();
-    tail.host_out = pub_slot(ctx); tail.seq = ctx->seq; tail.counter = (unsigned*)ctx->epi_counter.p;
-    if (ctx->pipe_tail) {
-      tail.accept = ctx->pipe_dev.d() + ctx->pub_ring; tail.cost_dev = ctx->pipe_dev.d() + 2;
-      tail.slot_cur = 1 - publish_slot; tail.slot_trial = publish_slot;
-      tail.c0_use_imm = ctx->pipe_c0_imm ? 1 : 0; tail.c0_imm = ctx->pipe_c0;
-    }
-  }
   A.cl.nsets = 3;
-  for (int q = 0; q < 3; ++q) { A.cl.cost[q] = ss[q]->cost.d(); A.cl.K[q] = ss[q]->K; }
-  const bool prof = ctx->profile && (ctx->profile_count++ % ctx->profile_every) == 0;
-  if (prof) {                                  // the bracket is booked on the obstacle set (the dominant one)
-    for (int e = 0; e < 2; ++e)
-      if (!s1.ev[0][e]) HIPCK(ctx, hipEventCreate(&s1.ev[0][e]));
-    HIPCK(ctx, hipEventRecord(s1.ev[0][0], ctx->stream));
-  }
-  const unsigned nblk = (unsigned)(block3_blocks(s0.K, A.s[0].a.nchunk) + block3_blocks(s1.K, A.s[1].a.nchunk) + block3_blocks(s2.K, A.s[2].a.nchunk));
+  const unsigned extra = take_gather(ctx, slot, A, 256);
+  GVICK(fill_epi_tail(ctx, A.nitems, publish_slot, &A.tail));
+  ProfBracket b;                               // the bracket is booked on the obstacle set (the dominant one)
+  GVICK(prof_open(ctx, *ss[1], 0, true, true, ctx->stream, &b));
   hipLaunchKernelGGL(factor_block3_kernel, dim3(nblk + extra), dim3(256), 4 * block3_lds_doubles() * 8, ctx->stream, A);
   ++block3_launches();
   HIPCK(ctx, hipGetLastError());
-  if (prof) { HIPCK(ctx, hipEventRecord(s1.ev[0][1], ctx->stream)); s1.ev_set[0] = true; }
+  GVICK(prof_close(ctx, b));
   *done = true;
   return GVI_OK;
 }
@@ -2624,13 +2605,12 @@ static gvi_status ngd_moments_full(gvi_ctx* ctx, int slot, int publish_slot = -1
     if (s->kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_UNSUPPORTED, "resident NGD needs device psi kinds");
   StageScope scope(ctx, STAGE_FACTORS);
   if (fused_ok(ctx, slot)) return ngd_fused_full(ctx, slot, publish_slot);
-  {
-    bool done = false;
-    GVICK(ngd_block3_full(ctx, slot, publish_slot, &done));
-    if (done) return GVI_OK;
-  }
+  MomPlan plans[MAX_SETS];
+  bool planned = false, done = false;
+  GVICK(ngd_block3_full(ctx, slot, publish_slot, plans, &planned, &done));
+  if (done) return GVI_OK;
   GVICK(ngd_prep_all(ctx, slot));
-  GVICK(ngd_moments_launch(ctx, slot, 1));
+  GVICK(ngd_moments_launch(ctx, slot, 1, planned ? plans : nullptr));
   return ngd_epilogue_all(ctx, 1, publish_slot);
 }
 
