@@ -1462,6 +1462,7 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   std::unique_ptr<FactorSet> s(new FactorSet);
   s->jtol = ctx->jacobi_tol;
   s->use_chol = ctx->chol_sqrt;
+  s->unit_temperature = ctx->update_rule == GVI_RULE_PROX_JKO;    // the rule belongs to the context: a set takes it when it is added
   s->K = K; s->d = d; s->p = p; s->m = m; s->kind = psi_kind; s->seg_J = seg_J;
   if (K > 0) s->start.assign(start, start + K);
   // quadrature table: shared between sets with the same (d, p)

@@ -249,8 +249,12 @@ gvi_status gvi_ngd_counters(gvi_ctx* ctx, int64_t* full_passes, int64_t* cost_pa
  *      moments as the natural-gradient path; per factor b = Lam E[(x-mu)psi], S = Lam E[(x-mu)(x-mu)^T psi] Lam - Lam E[psi],
  *      Sig_half = (I - h S) Sigma (I - h S)^T, Sigma_new = Sig_half/2 + h I + sqrtm(Sig_half (Sig_half + 4hI))/2,
  *      Vdmu = -b, Vddmu = (Sigma_new^-1 - Lam)/h; the joint dmu / dprecision are their plain scattered sums (no solve).
- *      The reference's prox classes never divide by the temperature: selecting the rule switches every set to unit
- *      temperature.  Single process only.
+ *      The reference's prox classes never divide by the temperature: under GVI_RULE_PROX_JKO every set is at unit
+ *      temperature.  The rule is a property of the CONTEXT, not of the sets that exist when it is selected: it survives
+ *      gvi_chain_set, and a set added afterwards (gvi_factors_add / gvi_factors_add_table) takes it when it is added, so the
+ *      order of gvi_ngd_set_update_rule, gvi_chain_set and gvi_factors_add does not matter.  The sets keep their own
+ *      temperatures (gvi_factors_set_temperature) and divide by them again after a switch back to GVI_RULE_NGD.
+ *      Single process only.
  * gvi_ngd_set_update_rule: GVI_RULE_NGD (default) or GVI_RULE_PROX_JKO; state set by gvi_ngd_init is kept.
  * gvi_prox_gradients(h): increments at the current proposal for step h (read back with gvi_ngd_get_gradients:
  *      dmu = gq, dprecision = (VD, VU)).   gvi_prox_trial(step): cost at mu + step dmu, Lam + step dprecision.
