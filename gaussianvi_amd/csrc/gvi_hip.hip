@@ -97,7 +97,7 @@ struct FactorSet {
   int arm_ndof = 0;
   int seg_J = 0;                      // HINGE_SDF_*_SEG: check points per factor
   bool fused_pair = false;            // last resident launch went out fused with the other set
-  bool closed_form = false;           // NGDFactorizedLinear route (no sigma points)
+  bool closed_form = false;           // no sigma points: NGDFactorizedLinear route (sum-of-squares kinds), box_moments.hpp (HINGE_BOX, its default)
   bool chain_structured = false;      // start[k] == k (factor k on state k / states k, k + 1): assemble-on-load needs no CSR
   bool all_pos = false;               // every residual row has sgn = +1 (positive-definite weight)
   double jtol = 1e-34;                // ctx->jacobi_tol
@@ -519,6 +519,12 @@ template <int M, int SMAX, int WAVES, int D0, int D1> struct FusedInst {};
 constexpr auto any_instance = [](auto) {};
 template <class F, class Inst> bool hit(F& f, Inst inst) { f(inst); return true; }
 
+// the hinge-on-SDF kinds: psi reads a signed-distance grid (gvi_factors_set_sdf2d / _sdf3d)
+bool sdf_kind(int kind) {
+  return kind == KIND_HINGE_SDF_2D || kind == KIND_HINGE_SDF_2D_BODY || kind == KIND_HINGE_SDF_3D || kind == KIND_HINGE_SDF_3D_ARM ||
+         kind == KIND_HINGE_SDF_2D_SEG || kind == KIND_HINGE_SDF_3D_SEG;
+}
+
 // moments_reg_kernel<D, Psi, full>: lane-per-point, psi operands in LDS
 template <class F>
 bool with_reg_instance(int kind, int d, int m, F&& f) {
@@ -546,6 +552,12 @@ bool with_reg_instance(int kind, int d, int m, F&& f) {
       break;
     case KIND_HINGE_SDF_3D_SEG:   // d = 12: 256 VGPRs + 18 AGPR copies under launch_bounds(256) -> generic kernel
       if (d == 6) return hit(f, RegInst<6, PsiHingeSeg<6, 3>>{});
+      break;
+    case KIND_HINGE_BOX:          // above d = 8 the accumulators leave no room: generic kernel, or the closed form
+      if (d == 2) return hit(f, RegInst<2, PsiBoxHinge<2>>{});
+      if (d == 4) return hit(f, RegInst<4, PsiBoxHinge<4>>{});
+      if (d == 6) return hit(f, RegInst<6, PsiBoxHinge<6>>{});
+      if (d == 8) return hit(f, RegInst<8, PsiBoxHinge<8>>{});
       break;
     case KIND_QUAD_PRIOR:
       if (d != 2 * m) break;
@@ -901,7 +913,7 @@ struct MomPlan {
   OrbitArgs oa;              // Orbit
   int smax = 0;              // Orbit: the table's largest support (instance key beside m)
   OrbitPsiArgs pa;           // OrbitPsi
-  size_t lds = 0;            // Orbit, OrbitPsi, Generic: dynamic LDS
+  size_t lds = 0;            // Orbit, OrbitPsi, Generic, Closed (HINGE_BOX): dynamic LDS
   bool pipe = false;         // Sreg: the hand-pipelined body
 };
 // lane-per-point register kernels: a block's four waves take four factors, grid ((K + 3) / 4, nchunk) but for Scost's own launch
@@ -915,7 +927,7 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
   if (s.K == 0) { s.nchunk = 1; s.chunk = s.table->Np; s.use_reg = s.use_split = s.use_orbit = s.use_opsi = false; return GVI_OK; }   // empty shard
   if (s.kind == KIND_HINGE_SDF_3D_ARM && !psi_ext && !s.arm.p)
     return fail(c, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");
-  if (s.kind >= KIND_HINGE_SDF_2D && s.kind <= KIND_HINGE_SDF_3D_SEG && !psi_ext && s.sdf_rows == 0)
+  if (sdf_kind(s.kind) && !psi_ext && s.sdf_rows == 0)
     return fail(c, GVI_ERR_STATE, "HINGE_SDF set without a grid: call gvi_factors_set_sdf2d / gvi_factors_set_sdf3d");
   bool reg = reg_supported(s.kind, s.d, s.m) && !psi_ext && c->variant != 1;
   if (c->variant == 2 && !reg && !psi_ext)
@@ -967,6 +979,10 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
   if (closed) {
     p.route = Route::Closed;
     p.grid = dim3(s.K);
+    if (s.kind == KIND_HINGE_BOX) {
+      p.lds = box_closed_lds_doubles(s.d) * 8;
+      if (p.lds > 64 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_BOX kernel LDS budget (d <= 89)");
+    }
   } else if (orbit) {
     p.route = Route::Orbit;
     GVICK(orbit_args(c, s, &p.oa));
@@ -1014,7 +1030,8 @@ gvi_status launch_plan(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t s
     case Route::Empty:
       return GVI_OK;
     case Route::Closed:
-      hipLaunchKernelGGL(moments_closed_kernel, p.grid, dim3(64), 0, st, a);
+      if (s.kind == KIND_HINGE_BOX) hipLaunchKernelGGL(moments_box_closed_kernel, p.grid, dim3(64), p.lds, st, a);
+      else hipLaunchKernelGGL(moments_closed_kernel, p.grid, dim3(64), 0, st, a);
       break;
     case Route::Orbit:
       hit = with_orbit_instance(s.m, p.smax, [&]<int M, int SMAX, int WAVES, bool PAIR>(OrbitInst<M, SMAX, WAVES, PAIR>) {
@@ -1453,10 +1470,26 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
       need = params_per_factor;
       break;
     }
+    case GVI_PSI_HINGE_BOX:
+      if (params_per_factor != 4 * (int64_t)d) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX needs params_per_factor = 4 d: [sigma | eps | lo | hi]");
+      need = params_per_factor;
+      break;
     default: return fail(ctx, GVI_ERR_ARG, "unknown psi kind");
   }
   if (need > 0 && (!psi_params || params_per_factor < need))
     return fail(ctx, GVI_ERR_ARG, "psi_params missing or params_per_factor too small for this kind");
+  if (psi_kind == GVI_PSI_HINGE_BOX) {
+    for (int64_t k = 0; k < K; ++k) {
+      const double* P = psi_params + k * params_per_factor;
+      for (int i = 0; i < d; ++i) {
+        const double sg = P[i], ep = P[d + i], lo = P[2 * d + i], hi = P[3 * d + i];
+        if (!std::isfinite(sg) || sg < 0.0) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX: sigma must be finite and >= 0");
+        if (!std::isfinite(ep)) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX: eps must be finite");
+        if (std::isnan(lo) || std::isnan(hi)) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX: NaN limit");
+        if (!(lo < hi)) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX: lo must be below hi (lo = -inf / hi = +inf switch a side off)");
+      }
+    }
+  }
   HIPCK(ctx, hipSetDevice(ctx->device));
 
   std::unique_ptr<FactorSet> s(new FactorSet);
@@ -1464,6 +1497,7 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   s->use_chol = ctx->chol_sqrt;
   s->unit_temperature = ctx->update_rule == GVI_RULE_PROX_JKO;    // the rule belongs to the context: a set takes it when it is added
   s->K = K; s->d = d; s->p = p; s->m = m; s->kind = psi_kind; s->seg_J = seg_J;
+  s->closed_form = psi_kind == GVI_PSI_HINGE_BOX;      // exact and cheaper than any rule on the kink; gvi_factors_set_closed_form(.., 0) for the quadrature
   if (K > 0) s->start.assign(start, start + K);
   // quadrature table: shared between sets with the same (d, p)
   if (tabZ) {
@@ -1521,8 +1555,8 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   GVICK(up(s->b, b.data(), b.size() * 8));
   GVICK(up(s->sgn, sg.data(), sg.size() * 8));
   s->all_pos = std::all_of(sg.begin(), sg.end(), [](double v) { return v == 1.0; });
-  const bool raw_kind = psi_kind == GVI_PSI_RANGE_1D || (psi_kind >= GVI_PSI_HINGE_SDF_2D && psi_kind <= GVI_PSI_HINGE_SDF_3D_SEG);
-  if (raw_kind) {                       // raw_stride = the kind's own block (for the _SEG kinds: 3 + J P (d + 1))
+  const bool raw_kind = psi_kind == GVI_PSI_RANGE_1D || sdf_kind(psi_kind) || psi_kind == GVI_PSI_HINGE_BOX;
+  if (raw_kind) {                       // raw_stride = the kind's own block (_SEG kinds: 3 + J P (d + 1), HINGE_BOX: 4 d)
     const int np = (int)need;
     std::vector<double> raw((size_t)K * np);
     for (int k = 0; k < K; ++k) memcpy(&raw[(size_t)k * np], psi_params + (size_t)k * params_per_factor, (size_t)np * 8);
@@ -1668,8 +1702,8 @@ gvi_status gvi_factors_set_arm(gvi_ctx* ctx, int set_id, int ndof, const double*
 gvi_status gvi_factors_set_closed_form(gvi_ctx* ctx, int set_id, int on) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  if (on && s->kind != KIND_QUAD_PRIOR && s->kind != KIND_FIXED_PRIOR)
-    return fail(ctx, GVI_ERR_ARG, "closed form exists for QUAD_PRIOR / FIXED_PRIOR sets only");
+  if (on && s->kind != KIND_QUAD_PRIOR && s->kind != KIND_FIXED_PRIOR && s->kind != KIND_HINGE_BOX)
+    return fail(ctx, GVI_ERR_ARG, "closed form exists for QUAD_PRIOR / FIXED_PRIOR / HINGE_BOX sets only");
   GVICK(sync(ctx));
   s->closed_form = on != 0;
   ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;

@@ -13,6 +13,7 @@
 //                      reg / wide / tile policy-templated register kernels (other psi kinds; A/B variants)
 //                      generic           any d <= 32, any psi kind, host psi
 //                      closed            quadrature-free moments of a quadratic psi (NGDFactorizedLinear)
+//                      box_closed        quadrature-free moments of the separable squared hinge of HINGE_BOX
 //   cost_tail_kernel per-factor cost + ordered sum + publish for a cost pass, one launch
 //   jko_*            factor-level proximal (JKO) map around the prep kernel's Jacobi
 //   epilogue_kernel  ordered sum of the chunk partials, back-transform to x-space, Vdmu_k / Vddmu_k
@@ -32,13 +33,14 @@
 
 #include <utility>
 
+#include "box_moments.hpp"
 #include "device_common.hpp"
 
 namespace gvi {
 
 enum { KIND_RANGE_1D = 0, KIND_QUAD_PRIOR = 1, KIND_FIXED_PRIOR = 2, KIND_HOST_CALLBACK = 3, KIND_HINGE_SDF_2D = 4,
        KIND_HINGE_SDF_2D_BODY = 5, KIND_HINGE_SDF_3D = 6, KIND_HINGE_SDF_3D_ARM = 7, KIND_HINGE_SDF_2D_SEG = 8,
-       KIND_HINGE_SDF_3D_SEG = 9 };
+       KIND_HINGE_SDF_3D_SEG = 9, KIND_HINGE_BOX = 10 };
 
 constexpr int SEG_MAX_J = 8;   // check points of one HINGE_SDF_*_SEG factor
 
@@ -67,7 +69,7 @@ struct FactorDev {
   const double* A;          // [K][m][d]   sum-of-squares kinds
   const double* b;          // [K][m]
   const double* sgn;        // [K][m]
-  const double* raw;        // [K][raw_stride] raw parameter block (RANGE_1D)
+  const double* raw;        // [K][raw_stride] raw parameter block (RANGE_1D, HINGE_SDF_*, HINGE_BOX)
   int raw_stride;
   const double* temperature;  // [K]
   // per-pass products of prep_kernel
@@ -948,7 +950,7 @@ __device__ inline double psi_hinge_sdf3d_seg(const FactorDev& f, const double* p
   return cost;
 }
 
-// psi and / or clearance of factor k of a hinge-on-SDF set at the state slice x [d].  psi is the kind's
+// psi and / or clearance of factor k of a hinge-on-SDF or HINGE_BOX set at the state slice x [d].  psi is the kind's
 // psi_* function; the clearance walks the same *_points with a min-visitor.  eps and slope play no part in the clearance.
 __device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, const double* x, bool want_psi, bool want_clr,
                                                     double& psi, double& clr) {
@@ -973,7 +975,10 @@ __device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, c
   } else if (f.kind == KIND_HINGE_SDF_3D_SEG) {
     if (want_psi) psi = psi_hinge_sdf3d_seg(f, p, x, f.d);
     if (want_clr) hinge_sdf3d_seg_points(f, p, x, f.d, keep);
-  } else {                      // not a hinge-on-SDF kind: the host refuses such a set before any launch
+  } else if (f.kind == KIND_HINGE_BOX) {      // limits on the slice itself (box_moments.hpp): the clearance is the margin
+    if (want_psi) psi = psi_hinge_box(p, x, f.d);
+    if (want_clr) c = box_margin(p, x, f.d);
+  } else {                      // no clearance for this kind: the host refuses such a set before any launch
     if (want_psi) psi = __builtin_nan("");
     c = __builtin_nan("");
   }
@@ -1037,6 +1042,64 @@ __global__ __launch_bounds__(64) void moments_closed_kernel(MomArgs a) {
       const int col = row + rem;
       for (int r = 0; r < m; ++r) v = fma(sg[r] * H[row * m + r], H[col * m + r], v);
       v = 2.0 * v + (row == col ? m0 : 0.0);
+    }
+    out[j] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// moments_box_closed_kernel: quadrature-free moments of the HINGE_BOX psi (box_moments.hpp).  psi is a
+// sum over coordinates of functions of ONE coordinate x_i = mu_i + s_i z (s_i = row i of S, sd_i = |s_i|), so with the 1-D
+// expectations (e0, e1, e2)_i of box_coordinate and Stein's lemma
+//   E[psi] = sum_i e0_i,   E[z psi] = sum_i s_i e1_i,   E[z z^T psi] = E[psi] I + sum_i s_i s_i^T e2_i
+// for any root S S^T = Sigma, S row-major as prep writes it (x = mu + S z: Ss[i * d + c] is entry c of ROW i).  Only the
+// symmetric root ever reaches this kernel (FactorSet::dev sets chol for the sum-of-squares kinds alone), for which rows and
+// columns coincide: the row convention is NOT exercised by any test, and a later switch of this kind to the Cholesky prep
+// (S = L, lower triangular) must test it before relying on it.  One wave per factor like moments_closed_kernel and the same packed one-chunk layout, so the
+// epilogue is shared.  Lane i takes coordinate i (erfc and exp once per finite side), S and (e1, e2) go through LDS
+// (d d + 2 d doubles of dynamic LDS), then lane j forms output j as a d-long sum in ascending i: deterministic.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ inline size_t box_closed_lds_doubles(int d) { return (size_t)d * d + 2 * (size_t)d; }
+
+__global__ __launch_bounds__(64) void moments_box_closed_kernel(MomArgs a) {
+  if (pred_skip(a.pred, a.pred_val)) return;
+  extern __shared__ double bsm[];
+  const FactorDev& f = a.f;
+  const int d = f.d, k = blockIdx.x, lane = threadIdx.x;
+  double* Ss = bsm;                   // [d][d]
+  double* e1s = Ss + d * d;           // [d]
+  double* e2s = e1s + d;              // [d]
+  const double* S = f.S + (size_t)k * d * d;
+  const double* p = f.raw + (size_t)k * f.raw_stride;
+  const double* mu = a.mu + (size_t)k * d;
+  for (int e = lane; e < d * d; e += 64) Ss[e] = S[e];
+  wave_lds_sync();
+  double e0 = 0.0;
+  for (int i = lane; i < d; i += 64) {
+    double q = 0.0;
+    for (int c = 0; c < d; ++c) q = fma(Ss[i * d + c], Ss[i * d + c], q);
+    const BoxSide s = box_coordinate(p, d, i, mu[i], sqrt(q));
+    e0 += s.e0;
+    e1s[i] = s.e1;
+    e2s[i] = s.e2;
+  }
+  const double m0 = wave_sum(e0);
+  wave_lds_sync();
+  const int npo = a.full ? npairs(d) : 1;
+  double* out = a.partial + (size_t)k * a.nchunk * npo;
+  if (lane == 0) out[0] = m0;
+  if (!a.full) return;
+  for (int j = 1 + lane; j < npo; j += 64) {
+    double v = 0.0;
+    if (j <= d) {
+      const int c = j - 1;
+      for (int i = 0; i < d; ++i) v = fma(Ss[i * d + c], e1s[i], v);
+    } else {
+      int rem = j - 1 - d, row = 0;
+      while (rem >= d - row) { rem -= d - row; ++row; }
+      const int col = row + rem;
+      for (int i = 0; i < d; ++i) v = fma(Ss[i * d + row] * Ss[i * d + col], e2s[i], v);
+      if (row == col) v += m0;
     }
     out[j] = v;
   }
@@ -1110,6 +1173,7 @@ __global__ __launch_bounds__(GEN_BS) void moments_generic_kernel(MomArgs a) {
       else if (f.kind == KIND_HINGE_SDF_3D_ARM) psi = psi_hinge_sdf3d_arm(f, f.raw + (size_t)k * f.raw_stride, xr, d);
       else if (f.kind == KIND_HINGE_SDF_2D_SEG) psi = psi_hinge_sdf2d_seg(f, f.raw + (size_t)k * f.raw_stride, xr, d);
       else if (f.kind == KIND_HINGE_SDF_3D_SEG) psi = psi_hinge_sdf3d_seg(f, f.raw + (size_t)k * f.raw_stride, xr, d);
+      else if (f.kind == KIND_HINGE_BOX) psi = psi_hinge_box(f.raw + (size_t)k * f.raw_stride, xr, d);
       else {
         for (int r = 0; r < m; ++r) {
           double u = bsh[r];
@@ -1280,6 +1344,43 @@ struct PsiHingeSeg {
       }
       const double sd = P == 2 ? sdf2d_lookup(a.f, q[0], q[1]) : sdf3d_lookup(a.f, q[0], q[1], q[P - 1]);
       cost += hinge_sq(sd, thr, 1.0, sigma);
+    }
+    return cost;
+  }
+};
+
+// Limits on the slice itself (HINGE_BOX, box_moments.hpp).  hs: S [D][D] | mu [D] | sigma [D] | upper threshold hi - eps [D] |
+// lower threshold lo + eps [D], an infinite threshold for a side that is off.  eval forms x_i = mu_i + s_i z only for a
+// coordinate with a finite side (a wave-uniform test on LDS values): a set that limits the velocities of a state pays for
+// those rows of S only.
+template <int D>
+struct PsiBoxHinge {
+  static constexpr int LDS = D * D + 4 * D;
+  static constexpr bool GUARD = false;
+  __device__ static void load(const MomArgs& a, int k, double* hs, int lane) {
+    const double* p = a.f.raw + (size_t)k * a.f.raw_stride;
+    for (int e = lane; e < D * D; e += 64) hs[e] = a.f.S[(size_t)k * D * D + e];
+    if (lane < D) {
+      hs[D * D + lane] = a.mu[(size_t)k * D + lane];
+      hs[D * D + D + lane] = p[lane];
+      hs[D * D + 2 * D + lane] = p[3 * D + lane] - p[D + lane];
+      hs[D * D + 3 * D + lane] = p[2 * D + lane] + p[D + lane];
+    }
+  }
+  __device__ static double eval(const double (&z)[D], const double* hs, const MomArgs&) {
+    double cost = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const double up = hs[D * D + 2 * D + i], dn = hs[D * D + 3 * D + i];
+      if (up < INFINITY || dn > -INFINITY) {
+        double x = hs[D * D + i];
+#pragma unroll
+        for (int c = 0; c < D; ++c) x = fma(hs[i * D + c], z[c], x);
+        const double eu = x - up, ed = dn - x;           // -inf on a side that is off
+        const double sg = hs[D * D + D + i];
+        if (eu > 0.0) cost += sg * eu * eu;
+        if (ed > 0.0) cost += sg * ed * ed;
+      }
     }
     return cost;
   }

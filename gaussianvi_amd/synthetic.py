@@ -8,6 +8,7 @@ the C-ABI works on.  psi parameter blocks use the C-ABI layouts of include/gvi_h
   FIXED_PRIOR [mu0 (d) | Kinv (d x d)]                         d = n    (gp/fixed_prior.h)
   RANGE_1D    [y, mu_p, f*b, sig_r_sq, sig_p_sq]               d = 1    (src/1d_example.cpp:25-35)
   HINGE_SDF_2D_SEG / _3D_SEG  [sigma, eps, r | W_0 (P x d) | c_0 (P) | ... ]   d = n or 2n   (segment_params)
+  HINGE_BOX   [sigma (d) | eps (d) | lo (d) | hi (d)]          d = n or 2n   (box_params)
 """
 from __future__ import annotations
 
@@ -16,6 +17,7 @@ import numpy as np
 PSI_RANGE_1D, PSI_QUAD_PRIOR, PSI_FIXED_PRIOR, PSI_HOST_CALLBACK, PSI_HINGE_SDF_2D = 0, 1, 2, 3, 4
 PSI_HINGE_SDF_2D_BODY, PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM = 5, 6, 7
 PSI_HINGE_SDF_2D_SEG, PSI_HINGE_SDF_3D_SEG = 8, 9
+PSI_HINGE_BOX = 10
 
 CONFIGS = {
     # name: (cfg#, T, n, p, prior kind)
@@ -119,6 +121,28 @@ def _segment_spec(obstacle, kind, T, n, nd, dt, taus, npos, p=None):
     return dict(kind=kind, d=2 * n, p=obstacle["p"] if p is None else p, start=np.arange(T - 1, dtype=np.int32),
                 params=segment_params(P[:T - 1, 0], P[:T - 1, 1], P[:T - 1, 2], W, c), temperature=np.ones(T - 1),
                 seg_W=W, seg_c=c, sdf_origin=obstacle["sdf_origin"], sdf_cell=obstacle["sdf_cell"], sdf_field=obstacle["sdf_field"])
+
+
+def box_params(sigma, eps, lo, hi):
+    """Parameter blocks [K][4 d] of a HINGE_BOX set: [sigma (d) | eps (d) | lo (d) | hi (d)].  Each argument is a scalar, [d]
+    (shared by the set) or [K][d]; lo = -inf / hi = +inf switches a side off."""
+    parts = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (sigma, eps, lo, hi)]
+    d = max(v.shape[-1] for v in parts)
+    K = max([v.shape[0] for v in parts if v.ndim == 2] + [1])
+    return np.ascontiguousarray(np.concatenate([np.broadcast_to(v, (K, d)) for v in parts], axis=1))
+
+
+def add_box_set(chain, lo, hi, sigma=10.0, eps=0.05, p=3, pair=False, temperature=1.0):
+    """A copy of `chain` (the arrays are shared) with a HINGE_BOX set appended behind its sets: one factor per state (d = n) or,
+    pair = True, per pair of neighbouring states (d = 2n), limits lo / hi [d] with -inf / +inf for the coordinates and sides
+    without one.  Velocity limits on make_planar_chain: lo = [-inf, -inf, -v, -v], hi = [inf, inf, v, v]; joint-angle and
+    joint-rate limits on make_obstacle_chain("arm7"): lo = [q_min (7) | -w (7)], hi = [q_max (7) | w (7)]."""
+    T, n = chain["T"], chain["n"]
+    K, d = (T - 1, 2 * n) if pair else (T, n)
+    lo, hi = np.broadcast_to(np.asarray(lo, dtype=np.float64), (d,)), np.broadcast_to(np.asarray(hi, dtype=np.float64), (d,))
+    spec = dict(kind=PSI_HINGE_BOX, d=d, p=p, start=np.arange(K, dtype=np.int32), params=np.tile(box_params(sigma, eps, lo, hi), (K, 1)),
+                temperature=np.full(K, float(temperature)))
+    return dict(chain, specs=list(chain["specs"]) + [spec])
 
 
 def _ltv_system(rng, nd):

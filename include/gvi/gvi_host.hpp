@@ -349,6 +349,24 @@ struct DevicePsi {
     p.sdf3d = std::move(sdf);
     return p;
   }
+  // Limits on the factor's slice itself (GVI_PSI_HINGE_BOX; no reference counterpart): a squared hinge per coordinate and
+  // side, sigma_i [max(0, x_i - (hi_i - eps_i))^2 + max(0, (lo_i + eps_i) - x_i)^2].  lo_i = -infinity / hi_i = +infinity
+  // switches a side off: joint limits, or limits on the velocities of a state only.  Needs no field.  Evaluated in closed form
+  // on the device (no sigma points); sample_clearance of such a set returns min_i min(hi_i - x_i, x_i - lo_i).
+  static DevicePsi hinge_box(const VectorXd& sigma, const VectorXd& eps, const VectorXd& lo, const VectorXd& hi) {
+    const int d = (int)sigma.size();
+    if (d < 1 || eps.size() != d || lo.size() != d || hi.size() != d)
+      throw std::invalid_argument("limit factor: sigma, eps, lo and hi must have the factor's dimension");
+    DevicePsi p{GVI_PSI_HINGE_BOX, {}};
+    for (const VectorXd* v : {&sigma, &eps, &lo, &hi})
+      for (int i = 0; i < d; ++i) p.params.push_back((*v)(i));
+    for (int i = 0; i < d; ++i) {
+      if (!std::isfinite(sigma(i)) || sigma(i) < 0.0) throw std::invalid_argument("limit factor: sigma must be finite and >= 0");
+      if (!std::isfinite(eps(i))) throw std::invalid_argument("limit factor: eps must be finite");
+      if (!(lo(i) < hi(i))) throw std::invalid_argument("limit factor: lo must be below hi (NaN, lo = +inf and hi = -inf are refused)");
+    }
+    return p;
+  }
   // a set is homogeneous in its block size too: segment factors with different J stay apart
   bool same_group(const DevicePsi& o) const {
     const bool seg = kind == GVI_PSI_HINGE_SDF_2D_SEG || kind == GVI_PSI_HINGE_SDF_3D_SEG;
@@ -1624,7 +1642,7 @@ class GVIGH {
     return M;
   }
   // Minimum over the factors of set `factor_set` (the sets are formed in the order their first factor was given: factors
-  // of the same dimension, degree and psi group share one; hinge-on-SDF kinds only) of sdf(p_b) - r_b at sample j of stream `seed`: negative where the sampled trajectory touches an obstacle.
+  // of the same dimension, degree and psi group share one; hinge-on-SDF kinds and limit factors only) of sdf(p_b) - r_b (limit factors: of the margin to the limits) at sample j of stream `seed`: negative where the sampled trajectory touches an obstacle.
   VectorXd sample_clearance(int n_samples, uint64_t seed, int factor_set) {
     if (n_samples < 0) throw GviError(GVI_ERR_ARG, "n_samples < 0");
     if (factor_set < 0 || factor_set >= (int)_sets.size()) throw GviError(GVI_ERR_ARG, "sample_clearance: no such factor set");

@@ -71,11 +71,21 @@ enum { GVI_F64 = 0, GVI_F32 = 1 };
  *       (DESIGN.md section 14).  The library neither knows nor requires that: any W_j, c_j is legal.  J is a property of the
  *       set: J = (params_per_factor - 3) / (P (d + 1)); the division must be exact and 1 <= J <= 8 (GVI_SEG_MAX_J), else GVI_ERR_ARG.
  *       Grid by gvi_factors_set_sdf2d (_2D_SEG) / gvi_factors_set_sdf3d (_3D_SEG); look-up and hinge as for HINGE_SDF_2D / _3D
+ *   GVI_PSI_HINGE_BOX                                                      any d >= 1 (no reference counterpart)
+ *       [sigma (d) | eps (d) | lo (d) | hi (d)], params_per_factor = 4 d exactly
+ *       psi(x) = sum_i sigma_i [max(0, x_i - (hi_i - eps_i))^2 + max(0, (lo_i + eps_i) - x_i)^2]: joint, velocity or workspace
+ *       limits on the factor's slice, a squared hinge per coordinate and side that starts eps inside the limit.
+ *       lo_i = -inf or hi_i = +inf switches that side off, both: coordinate i is unconstrained (limits on the velocities of a
+ *       state only).  GVI_ERR_ARG: a NaN, sigma_i < 0 or not finite, eps_i not finite, lo_i >= hi_i, lo_i = +inf, hi_i = -inf.
+ *       Needs no grid and no arm model (those setters refuse it).  psi is separable, so its Gaussian moments are exact closed
+ *       forms in Phi and phi of the 1-D marginals, and the set is created in CLOSED FORM (no sigma points; DESIGN.md section
+ *       15); gvi_factors_set_closed_form(set, 0) selects the Gauss-Hermite quadrature of the same psi, (set, 1) returns.
+ *       margin(x) = min_i min(hi_i - x_i, x_i - lo_i) is what the clearance calls return for such a set
  *   GVI_PSI_HOST_CALLBACK no parameters: psi is an opaque host function (the reference's
  *       std::function, ngd/NGDFactorizedBaseGH.h:30,46-48); use gvi_expand + gvi_moments_from_psi. */
 enum { GVI_PSI_RANGE_1D = 0, GVI_PSI_QUAD_PRIOR = 1, GVI_PSI_FIXED_PRIOR = 2, GVI_PSI_HOST_CALLBACK = 3,
        GVI_PSI_HINGE_SDF_2D = 4, GVI_PSI_HINGE_SDF_2D_BODY = 5, GVI_PSI_HINGE_SDF_3D = 6, GVI_PSI_HINGE_SDF_3D_ARM = 7,
-       GVI_PSI_HINGE_SDF_2D_SEG = 8, GVI_PSI_HINGE_SDF_3D_SEG = 9 };
+       GVI_PSI_HINGE_SDF_2D_SEG = 8, GVI_PSI_HINGE_SDF_3D_SEG = 9, GVI_PSI_HINGE_BOX = 10 };
 enum { GVI_SEG_MAX_J = 8 };   /* check points of one HINGE_SDF_*_SEG factor */
 
 const char* gvi_version(void);
@@ -152,7 +162,9 @@ gvi_status gvi_factors_set_arm(gvi_ctx* ctx, int set_id, int ndof, const double*
  * fact_cost_value (ngd/NGDFactorizedLinear.h:93-129) instead of quadrature -- the factors the reference's
  * classify_factors sends to its linear branch (gvibase/GVI-GH-Cuda-impl.h:31-38).  No sigma points are
  * evaluated; the Gaussian 4th-moment contraction (its O(d^4) loop, :108-118) is done in the whitened
- * space where it collapses to (u0^2 + |h|^2) I + 2 h h^T per residual row.  on = 0 returns to quadrature. */
+ * space where it collapses to (u0^2 + |h|^2) I + 2 h h^T per residual row.  on = 0 returns to quadrature.
+ * A GVI_PSI_HINGE_BOX set has a closed form of its own and starts with it on (see the kind).  on = 1 for any other kind:
+ * GVI_ERR_ARG. */
 gvi_status gvi_factors_set_closed_form(gvi_ctx* ctx, int set_id, int on);
 /* factor_switch_to_high_temperature (gvibase/GVIFactorizedBase.h:212-214), batched. */
 gvi_status gvi_factors_set_temperature(gvi_ctx* ctx, int set_id, const double* temperature);
@@ -418,7 +430,8 @@ gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_
  *      under GVI_RULE_PROX_JKO);  J(x) = sum over the sets, over k, of cost_k(x).
  *      The CLEARANCE of a hinge-on-SDF factor is min_b sdf(p_b) - r_b over the factor's check points b -- the points of its
  *      psi, in the same arithmetic: the one ball of HINGE_SDF_2D / _3D, the n_balls body points of _2D_BODY, the first
- *      min(d, nspheres) spheres with their own radii of _3D_ARM, the J read-outs W_j x + c_j of _2D_SEG / _3D_SEG.  epsilon and slope play no part in it.  It is the continuous
+ *      min(d, nspheres) spheres with their own radii of _3D_ARM, the J read-outs W_j x + c_j of _2D_SEG / _3D_SEG.  epsilon and slope play no part in it.
+ *      For a HINGE_BOX set the clearance is margin(x) = min_i min(hi_i - x_i, x_i - lo_i), +inf when no limit is finite.  It is the continuous
  *      quantity; the library returns no collided / not-collided indicator.
  *      S = 0 is a no-op; S < 0, a required NULL buffer, first < 0 or a set id outside the context's sets: GVI_ERR_ARG; before
  *      gvi_chain_set (gvi_ngd_*: before gvi_ngd_init): GVI_ERR_STATE, as is a hinge set whose grid (arm model) was never set; a
@@ -434,7 +447,7 @@ gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_
  *      64, ... 1).  The order depends on the sets only. ---- */
 /* cost [S][K] of one set at X [S][T][n]; host buffers, a pure operator. */
 gvi_status gvi_sample_factor_costs(gvi_ctx* ctx, int set_id, int S, const double* X, double* cost);
-/* clr [S][K]: hinge-on-SDF sets only, every other kind: GVI_ERR_UNSUPPORTED.  The _dev twin takes device buffers and is
+/* clr [S][K]: hinge-on-SDF and HINGE_BOX sets only, every other kind: GVI_ERR_UNSUPPORTED.  The _dev twin takes device buffers and is
  * asynchronous on the context stream. */
 gvi_status gvi_sample_clearance(gvi_ctx* ctx, int set_id, int S, const double* X, double* clr);
 gvi_status gvi_sample_clearance_dev(gvi_ctx* ctx, int set_id, int S, const double* X_dev, double* clr_dev);
