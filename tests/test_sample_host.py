@@ -1,12 +1,18 @@
 """CPU checks of the samplers' boundary: the Python restatement of the generator (include/gvi_hip.h, "samples of q")
-reproduces the Random123 Philox4x32-10 known answers, and GVIGH::sample / GVIGH::log_density compile against the shim."""
+reproduces the Random123 Philox4x32-10 known answers, GVIGH::sample / GVIGH::log_density compile against the shim, and the
+float64 restatement of the sweep (tests/sample_ref.py) is proven at every shape tests/test_sample_sweep_gpu.py compares the device
+with: against the dense inverse up to T n = 600, through F^T Lambda F = I on random vectors above, with the conditioning of
+every dense matrix formed."""
 import math
 import os
 import subprocess
 
 import numpy as np
+import pytest
 
+import sample_ref as sr
 from gaussianvi_amd import build
+from test_solve_host import SHAPES, cr_factor, dense, random_chain
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M32 = 0xFFFFFFFF
@@ -49,6 +55,63 @@ def test_restated_generator_is_split_invariant_and_standard():
     assert np.array_equal(z[10:20], randn(7, 13, 10))           # number i depends on (seed, i) only
     assert not np.array_equal(z[:100], randn(8, 3, 100))
     assert abs(z.mean()) < 6 / math.sqrt(len(z)) and abs(z.var() - 1.0) < 6 * math.sqrt(2.0 / len(z))
+
+
+# ---- the per-entry reference of the sweep (tests/sample_ref.py) at every shape tests/test_sample_sweep_gpu.py uses ----
+_SHAPES = sorted(set(sr.gpu_shapes()) | set(SHAPES))
+SMALL = [s for s in _SHAPES if s[0] * s[1] <= sr.SMALL_TN]
+LARGE = [s for s in _SHAPES if s[0] * s[1] > sr.SMALL_TN]
+DENSE_LOGDET_TN = 1600
+REF_TOL = 1e-13                      # three orders inside the 1e-10 of the GPU tests
+COND_MAX = 1e2
+
+
+def _cond(A):
+    w = np.linalg.eigvalsh(A)
+    assert w[0] > 0
+    return w[-1] / w[0]
+
+
+@pytest.mark.parametrize("T,n", SMALL)
+def test_reference_sweep_gives_the_dense_covariance(T, n):
+    D, U, _ = random_chain(T, n, 100 + T * n)
+    A = dense(D, U)
+    assert _cond(A) <= COND_MAX
+    N = T * n
+    F = sr.cr_sample(D, U, np.eye(N).reshape(N, T, n)).reshape(N, N).T       # column j = the draw from eps = e_j
+    Sig = np.linalg.inv(A)
+    err = np.abs(F @ F.T - Sig).max() / np.abs(Sig).max()
+    assert err <= REF_TOL, err
+    sgn, ld = np.linalg.slogdet(A)
+    assert sgn > 0 and abs(sr.half_logdet(D, U) - 0.5 * ld) <= REF_TOL * max(1.0, abs(0.5 * ld))
+
+
+@pytest.mark.parametrize("T,n", LARGE)
+def test_reference_sweep_keeps_the_quadratic_form(T, n):
+    """F^T Lambda F = I on random vectors: y^T Lambda y = |eps|^2 and y_i^T Lambda y_j = eps_i . eps_j, no dense matrix."""
+    D, U, _ = random_chain(T, n, 100 + T * n)
+    fac = cr_factor(D, U)
+    eps = np.random.default_rng(T + n).standard_normal((3, T, n))
+    Y = sr.cr_sample(D, U, eps, fac).reshape(3, -1)
+    G = Y @ sr.block_matvec(D, U, Y.reshape(3, T, n)).reshape(3, -1).T
+    E = eps.reshape(3, -1) @ eps.reshape(3, -1).T
+    err = np.abs(G - E).max() / np.abs(E).max()
+    assert err <= REF_TOL, err
+    if T * n <= DENSE_LOGDET_TN:
+        A = dense(D, U)
+        assert _cond(A) <= COND_MAX
+        sgn, ld = np.linalg.slogdet(A)
+        assert sgn > 0 and abs(sr.half_logdet(D, U, fac) - 0.5 * ld) <= REF_TOL * abs(0.5 * ld)
+
+
+def test_restated_sweep_plan():
+    """The plan's own arithmetic at its edges (the GPU cases assert the rows they were written for against it)."""
+    assert sr.sweep_plan(1, 1, 1) == (True, 1) and sr.sweep_plan(512, 7, 4) == (True, 1) and sr.sweep_plan(513, 7, 4) == (True, 2)
+    assert sr.sweep_plan(4096, 7, 4) == (True, 8) and sr.sweep_plan(10 ** 6, 7, 4) == (True, 8)
+    assert sr.sweep_plan(10 ** 6, 640, 16) == (True, 1) and sr.sweep_plan(3, 641, 16) == (False, 1)
+    assert sr.sweep_plan(10 ** 6, 641, 16) == (False, 8)
+    for T, n, S, lds, tile, last in sr.LDS_TILES + sr.LDS_CAPPED + sr.BOUNDARY + sr.BUFFER_TILES + sr.GENERATED + sr.NOT_PD:
+        assert sr.sweep_plan(S, T, n) == (lds, tile) and sr.last_tile(S, tile) == last, (T, n, S)
 
 
 def test_sample_callsite_compiles_against_the_shim(tmp_path):
