@@ -7,7 +7,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +16,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "host_linalg.hpp"
@@ -138,16 +138,14 @@ struct FactorSet {
   }
 };
 
-struct NgdState {
-  bool ready = false;
+// The host's bookkeeping of the resident iteration: what is where, what is valid, what is parked.  One plain value, so that
+// the pipelined run (gvi_ngd_run) takes it back after a rejected first trial by assignment: a field added here is rolled back
+// with the rest.  (The sets' prep_slot / warm_count are the other part of that snapshot.)
+struct NgdBook {
   int cur = 0;
-  DevMem mu[2], Lam[2], Sig[2], hld[2];   // Lam = [D | U], Sig = [SigD | SigU]
-  DevMem exch0[2], exch1;                 // gradient buffers [g | VD | VU] (double-buffered for speculation), [cost partial sum]
-  DevMem dmu2[2];
   int gcur = 0;                           // gradient buffer holding the gradients of `grad_slot`
   bool grad_valid = false;
   int grad_slot = -1;
-  DevMem dmu, dLam, total;
   bool cost_valid[2] = {false, false};
   double cost[2] = {0, 0};
   bool have_trial = false;
@@ -155,6 +153,25 @@ struct NgdState {
   // gather of slot i deferred into the next prep launch of that slot (ngd_prep_all) -- see PrepList
   struct GatherPending { bool on = false; const double* mu_from = nullptr; const double* dmu = nullptr; double step = 0.0; };
   GatherPending gpend[2];
+  // solve_deferred[gb]: the solve of gradient buffer gb is not launched yet -- it goes out fused with the next trial
+  // factorisation (the dual launch of ngd_trial_state: same three launches, no second stream), or with its first other reader
+  bool solve_deferred[2] = {false, false};
+  bool asm_pending[2] = {false, false};   // gradient buffer gb is NOT assembled yet (assemble-on-load, see gvi_ctx::asm_on_load)
+  bool last_first_accepted = true;        // adaptive fusing (gvi_ctx::fuse_trial = 2)
+  int64_t n_full_pass = 0, n_cost_pass = 0;   // psi passes launched over all sets (gvi_ngd_counters)
+  long profile_count = 0;                 // eligible launches seen by the profile sampling (gvi_ctx::profile_every)
+};
+static_assert(std::is_trivially_copyable<NgdBook>::value, "the pipelined run snapshots the bookkeeping by assignment");
+
+// Outside NgdBook, deliberately never rolled back: the device buffers (the predicated launches of a rejected iteration wrote
+// nothing), and in gvi_ctx the publish sequence `seq` and the chain hand-over `chain_seq` (their numbers were handed to
+// launches that stay queued, so they only ever grow) and the options (only gvi_ctx_create and the setters write them).
+struct NgdState : NgdBook {
+  bool ready = false;
+  DevMem mu[2], Lam[2], Sig[2], hld[2];   // Lam = [D | U], Sig = [SigD | SigU]
+  DevMem exch0[2], exch1;                 // gradient buffers [g | VD | VU] (double-buffered for speculation), [cost partial sum]
+  DevMem dmu2[2];
+  DevMem dmu, dLam, total;
 };
 
 // State of the posterior queries (posterior_host.inc)
@@ -195,13 +212,10 @@ struct gvi_ctx {
   // 0 never, 1 always (first trial), 2 adaptive (default): fused while first trials keep being accepted, the m0-only
   // cost pass after a rejection (a rejected fused trial wastes the moment accumulation)
   int fuse_trial = 2;
-  bool last_first_accepted = true;
-  int64_t n_full_pass = 0, n_cost_pass = 0;   // psi passes launched over all sets (gvi_ngd_counters)
   bool speculate = true;              // gvi_ngd_step: queue the next gradients behind the first trial
   bool profile = false;
   bool profile_all = false;           // events around every moments / cost launch (else: set 0, full pass only)
   int profile_every = 1;              // on = 3: bracket only every 8th dominant launch (an event pair costs ~14 us of queue gaps)
-  long profile_count = 0;
   int target_waves = 2048;
   bool mirror = true;                 // GVI_MIRROR=0: never pair z with -z (A/B; results agree to rounding)
   int split_flush = SPLIT_FLUSH;      // GVI_SPLIT_FLUSH=0: plain recursive sums in the split kernel (A/B of the (24,7) rounding)
@@ -232,23 +246,14 @@ struct gvi_ctx {
   static constexpr int cost_chunk_mult = 8;   // cost pass of the F-factor kernel: chunks per factor relative to the full pass
   int update_rule = 0;                // 0 natural gradient (NGD-GH), 1 proximal / JKO (ProxGVI-GH)
   bool pair_fuse = true;              // GVI_NO_PAIR=1: one launch per set
-  bool defer_gather = false;          // set around the trial-state refresh (a prep of that slot always follows)
   bool fuse_gather = true;            // GVI_NO_FUSE_GATHER=1: stand-alone gather launch before the trial's prep
-  hipEvent_t fork = nullptr;
-  // side-stream solve: the chain solve of the gradients runs beside the trial factorisation (independent given Vddmu)
-  bool side_solve = true;             // GVI_SIDE_SOLVE=0 keeps everything on one stream
-  hipStream_t side = nullptr;
-  hipEvent_t ev_grad = nullptr, ev_solve[2] = {nullptr, nullptr};
-  bool solve_pending[2] = {false, false};
-  // dual_chain (GVI_DUAL_CHAIN=0 restores the side stream): the gradient solve is not launched at once but parked, and goes
-  // out fused with the next trial factorisation (same three launches, no fork / join events)
-  bool dual_chain = true;
-  bool solve_deferred[2] = {false, false};
+  // the chain solve of the gradients goes out beside the next trial factorisation (independent given Vddmu), as one dual
+  // launch (dual_solve, NgdBook::solve_deferred); GVI_SIDE_SOLVE=0, or a one-state chain: the solve is launched at once
+  bool side_solve = true;
   // assemble-on-load (GVI_ASM_ON_LOAD=0 / option "assemble_on_load": the stand-alone assemble launch): on chain-structured
   // graphs the ordered assemble of (g, V_D, V_U) is not launched behind the factor pass but done by the first pass of the
-  // chain operations that consume it (kernels_chain.hpp, AsmList); asm_pending[gb]: gradient buffer gb is NOT assembled yet
+  // chain operations that consume it (kernels_chain.hpp, AsmList; NgdBook::asm_pending)
   bool asm_on_load = true;
-  bool asm_pending[2] = {false, false};
   DevMem Wbuf2, Ibuf2;                // second BCR workspace (the two chains are in flight together)
   // merged top + backward launch of the chain (chain_launch.hpp::ChainSync): a ring of word pairs, one pair per launch
   DevMem chain_sync;
@@ -257,10 +262,6 @@ struct gvi_ctx {
   bool chain_merge_fault = false;     // option chain_merge = 2: the hand-over word is stored wrong (test of the bounded wait)
   DevMem tail_counter;                // arrival counter of cost_tail_kernel (last block reduces)
   DevMem epi_counter;                 // two-level arrival counters of epilogue_all_kernel's tail
-  // trial precision formed inside the first pass of the next factorisation (see ChainArgs::mix*)
-  struct Mix { const double* VD = nullptr; const double* VU = nullptr; double* outD = nullptr; double* outU = nullptr; double step = 0.0; } mix;
-  hipStream_t chain_stream = nullptr; // stream of the chain launches being queued (null: ctx->stream)
-  int chain_ws = 0;
   // ---- sharded factors (one process per GPU): the exchange steps run inside the library, on the context stream ----
   struct Dist {
     int rank = 0, world = 1;
@@ -277,20 +278,23 @@ struct gvi_ctx {
     bool rec_fresh = false;           // the last assemble wrote this rank's exchange records itself (no pack launch)
     bool ranges_valid = false;
   } dist;
-  // pipelined iterations (gvi_ngd_run): predicate of the launches being queued, device-side accept decision of the tails,
-  // ring of two host slots (a speculatively queued iteration publishes into the other one)
-  const double* cur_pred = nullptr;
-  double cur_pred_val = 0.0;
+  // pipelined iterations (gvi_ngd_run): what holds for EVERY launch queued while an iteration is being queued ahead -- its
+  // predicate, the device-side accept decision of the tails, the ring of two host slots (a speculatively queued iteration
+  // publishes into the other one).  The default value is the plain iteration; only PipeWindowScope sets another.
+  struct PipeWindow {
+    const double* pred = nullptr;     // predicate of the launches being queued
+    double pred_val = 0.0;
+    bool tail = false;                // tails take the accept decision on the device
+    bool c0_imm = true;               // current cost as an immediate (known to the host) or from pipe_dev
+    double c0 = 0.0;
+    int pub_ring = 0;                 // host slot the next publish goes to
+  } pipe;
   DevMem pipe_dev;                    // doubles: [0..1] accept words (ring), [2..3] cost of the state in NGD slot 0 / 1
   // Option "pipeline" (GVI_PIPELINE=0 switches it off): gvi_ngd_run queues iteration i + 1 (predicated) before it has read
   // the cost of iteration i.  Round 2 measured no gain (129.7 vs 130.5 us per C3 iteration: the early publish of the trial
   // cost already gave the host its head start); with the round-3 kernels the iteration is short enough for the host's
   // hand-over to show again: 109.3 -> 107.4 us at C3, 45.8 -> 44.3 us at C2.  On by default since then.
   bool pipeline = true;
-  bool pipe_tail = false;             // tails take the accept decision on the device
-  bool pipe_c0_imm = true;            // current cost as an immediate (known to the host) or from pipe_dev
-  double pipe_c0 = 0.0;
-  int pub_ring = 0;                   // host slot the next publish goes to
   double* host_slot = nullptr;        // host-mapped {cost value, sequence}: one 16-byte device store (publish_to_host)
   // kernels whose dynamic-LDS limit was raised on THIS context's device (the attribute is per device, and a
   // process may hold contexts on several devices)
@@ -376,13 +380,10 @@ gvi_status sync(gvi_ctx* c) {
   // polled for a while before the blocking wait: a blocked hipStreamSynchronize wakes up 50-70 us after the stream has drained
   // (bench.py, closing synchronisation of a 2 ms timed region), a poll within a few
   const auto t0 = std::chrono::steady_clock::now();
-  for (hipStream_t st : {c->stream, c->side}) {
-    if (!st) continue;
-    hipError_t e = hipStreamQuery(st);
-    while (e == hipErrorNotReady && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2)) e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) HIPCK(c, e);
-    HIPCK(c, hipStreamSynchronize(st));
-  }
+  hipError_t e = hipStreamQuery(c->stream);
+  while (e == hipErrorNotReady && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2)) e = hipStreamQuery(c->stream);
+  if (e != hipSuccess && e != hipErrorNotReady) HIPCK(c, e);
+  HIPCK(c, hipStreamSynchronize(c->stream));
   return GVI_OK;
 }
 
@@ -495,7 +496,7 @@ gvi_status upload_table(gvi_ctx* c, Table& t, int d, int p, int64_t N, const dou
 
 // device address of the current publish slot (four doubles per ring entry); bit 0 tags the checked form (publish_to_host)
 double* pub_slot(const gvi_ctx* c) {
-  return (double*)((unsigned long long)(c->host_slot_dev + 4 * c->pub_ring) | (c->safe_publish ? 1ull : 0ull));
+  return (double*)((unsigned long long)(c->host_slot_dev + 4 * c->pipe.pub_ring) | (c->safe_publish ? 1ull : 0ull));
 }
 
 FactorSet* get_set(gvi_ctx* c, int id) {
@@ -748,7 +749,7 @@ gvi_status orbit_args(gvi_ctx* c, FactorSet& s, OrbitArgs* out) {
   OrbitArgs a;
   a.H = s.H.d(); a.u0 = s.u0.d(); a.sgn = s.sgn.d(); a.partial = s.partial.d();
   a.K = s.K; a.d = s.d; a.nchunk = s.nchunk;
-  a.pred = c->cur_pred; a.pred_val = c->cur_pred_val;
+  a.pred = c->pipe.pred; a.pred_val = c->pipe.pred_val;
   // private accumulator copies: as many as the occupancy of the set's own instance leaves LDS for (160 KB per CU, 64 KB per
   // block), capped by orbit_copies
   int waves = 0;
@@ -856,6 +857,17 @@ gvi_status launch_fused_t(gvi_ctx* c, const FusedArgs& A, unsigned grid, size_t 
   return GVI_OK;
 }
 
+// prep_kernel for the f.K factors of f at (mu, Sigma) device pointers: the instance of the dimension and its LDS
+gvi_status launch_prep(gvi_ctx* c, const FactorDev& f, const double* mu, const double* Sigma, hipStream_t st) {
+  const int d = f.d, dp = d + (d & 1);
+  const size_t lds = (size_t)(4 * d * d + 2 * dp + 3 * d) * 8 + (size_t)dp * 4 + 16;
+  if (d <= 8) hipLaunchKernelGGL(prep_kernel<1>, dim3(f.K), dim3(64), lds, st, f, mu, Sigma);
+  else if (d <= 16) hipLaunchKernelGGL(prep_kernel<4>, dim3(f.K), dim3(64), lds, st, f, mu, Sigma);
+  else if (d <= 32) hipLaunchKernelGGL(prep_kernel<16>, dim3(f.K), dim3(64), lds, st, f, mu, Sigma);
+  else return fail(c, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
+  return GVI_OK;
+}
+
 // prep (sqrt / inverse / psi operands) for one set at (mu, Sigma) device pointers
 gvi_status run_prep(gvi_ctx* c, FactorSet& s, const double* mu, const double* Sigma, int slot = -1,
                     hipStream_t st = nullptr) {
@@ -863,12 +875,7 @@ gvi_status run_prep(gvi_ctx* c, FactorSet& s, const double* mu, const double* Si
   if (slot >= 0 && s.prep_slot == slot) return GVI_OK;     // products of this slot are still resident
   s.prep_slot = slot;
   if (s.K == 0) return GVI_OK;
-  const int d = s.d, dp = d + (d & 1);
-  const size_t lds = (size_t)(4 * d * d + 2 * dp + 3 * d) * 8 + (size_t)dp * 4 + 16;
-  if (d <= 8) hipLaunchKernelGGL(prep_kernel<1>, dim3(s.K), dim3(64), lds, st, s.dev(), mu, Sigma);
-  else if (d <= 16) hipLaunchKernelGGL(prep_kernel<4>, dim3(s.K), dim3(64), lds, st, s.dev(), mu, Sigma);
-  else if (d <= 32) hipLaunchKernelGGL(prep_kernel<16>, dim3(s.K), dim3(64), lds, st, s.dev(), mu, Sigma);
-  else return fail(c, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
+  GVICK(launch_prep(c, s.dev(), mu, Sigma, st));
   HIPCK(c, hipGetLastError());
   return GVI_OK;
 }
@@ -970,7 +977,7 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
   a.f = s.dev(); a.mu = mu; a.psi_ext = psi_ext; a.partial = s.partial.d();
   a.chunk = s.chunk; a.nchunk = s.nchunk; a.full = full; a.flush = c->split_flush;
   a.mchunk = 0;
-  a.pred = c->cur_pred; a.pred_val = c->cur_pred_val;
+  a.pred = c->pipe.pred; a.pred_val = c->pipe.pred_val;
   if (s.table->Nmp > 0) {                                   // same number of chunks over the mirror-half table
     const int64_t tiles = s.table->Nmp / 64;
     a.mchunk = (tiles + s.nchunk - 1) / s.nchunk * 64;
@@ -992,7 +999,7 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
     p.route = Route::OrbitPsi;
     OrbitPsiArgs& pa = p.pa;
     pa.f = a.f; pa.mu = mu; pa.partial = s.partial.d(); pa.nchunk = s.nchunk;
-    pa.pred = c->cur_pred; pa.pred_val = c->cur_pred_val;
+    pa.pred = c->pipe.pred; pa.pred_val = c->pipe.pred_val;
     GVICK(orbit_dev(c, s, &pa.ob));                         // table pointers, class layout, chunk bounds
     const int NR = orbit_psi_rows(s.kind);
     pa.copies = 1;
@@ -1100,7 +1107,7 @@ unsigned take_gather(gvi_ctx* ctx, int i, Args& A, int block) {
 gvi_status fill_epi_tail(gvi_ctx* ctx, int nitems, int publish_slot, EpiTail* out) {
   EpiTail& tail = *out;
   tail.on = 0; tail.acc = nullptr; tail.half_logdet = nullptr; tail.host_out = nullptr; tail.seq = 0.0; tail.counter = nullptr;
-  tail.pred = ctx->cur_pred; tail.pred_val = ctx->cur_pred_val;
+  tail.pred = ctx->pipe.pred; tail.pred_val = ctx->pipe.pred_val;
   tail.accept = nullptr; tail.cost_dev = nullptr; tail.slot_cur = tail.slot_trial = 0; tail.c0_use_imm = 1; tail.c0_imm = 0.0;
   tail.safe = ctx->safe_publish ? 1 : 0;
   if (publish_slot < 0) return GVI_OK;
@@ -1113,10 +1120,10 @@ gvi_status fill_epi_tail(gvi_ctx* ctx, int nitems, int publish_slot, EpiTail* ou
   ctx->seq += 1.0;
   tail.on = 1; tail.acc = ctx->ngd.exch1.d(); tail.half_logdet = ctx->ngd.hld[publish_slot].d();
   tail.host_out = pub_slot(ctx); tail.seq = ctx->seq; tail.counter = (unsigned*)ctx->epi_counter.p;
-  if (ctx->pipe_tail) {
-    tail.accept = ctx->pipe_dev.d() + ctx->pub_ring; tail.cost_dev = ctx->pipe_dev.d() + 2;   // accept word of THIS ring slot
+  if (ctx->pipe.tail) {
+    tail.accept = ctx->pipe_dev.d() + ctx->pipe.pub_ring; tail.cost_dev = ctx->pipe_dev.d() + 2;   // accept word of THIS ring slot
     tail.slot_cur = 1 - publish_slot; tail.slot_trial = publish_slot;
-    tail.c0_use_imm = ctx->pipe_c0_imm ? 1 : 0; tail.c0_imm = ctx->pipe_c0;
+    tail.c0_use_imm = ctx->pipe.c0_imm ? 1 : 0; tail.c0_imm = ctx->pipe.c0;
   }
   return GVI_OK;
 }
@@ -1135,7 +1142,7 @@ struct ProfBracket {
 gvi_status prof_open(gvi_ctx* c, FactorSet& s, int which, bool eligible, bool around, hipStream_t st, ProfBracket* b) {
   *b = ProfBracket();
   if (!c->profile || !eligible) return GVI_OK;
-  if (!c->profile_all && (c->profile_count++ % c->profile_every) != 0) return GVI_OK;
+  if (!c->profile_all && (c->ngd.profile_count++ % c->profile_every) != 0) return GVI_OK;
   for (int e = 0; e < 2; ++e)
     if (!s.ev[which][e]) HIPCK(c, hipEventCreate(&s.ev[which][e]));
   b->s = &s; b->which = which; b->around = around; b->st = st;
@@ -1192,13 +1199,14 @@ gvi_status ensure_set_buffers(gvi_ctx* c, FactorSet& s) {
   return GVI_OK;
 }
 
-// workspace of one chain operation (kernels_chain.hpp); two operations are in flight together in the dual launches
+// workspace of one chain operation (kernels_chain.hpp); two operations are in flight together in the dual launches, so
+// there are two: `which` = 0 (the factorisations, every stand-alone operation) or 1 (the parked gradient solve)
 struct ChainWs { double* ws; int* wsi; };
-gvi_status ensure_chain_ws(gvi_ctx* c, ChainWs& w) {
+gvi_status ensure_chain_ws(gvi_ctx* c, int which, ChainWs& w) {
   const int NP = chain_padded(c->n);
   if (!NP) return fail(c, GVI_ERR_UNSUPPORTED, "state_dim > 16");
-  DevMem& Wb = c->chain_ws ? c->Wbuf2 : c->Wbuf;
-  DevMem& Ib = c->chain_ws ? c->Ibuf2 : c->Ibuf;
+  DevMem& Wb = which ? c->Wbuf2 : c->Wbuf;
+  DevMem& Ib = which ? c->Ibuf2 : c->Ibuf;
   HIPCK(c, Wb.ensure(chain_ws_doubles(c->T, NP) * 8));
   HIPCK(c, Ib.ensure(chain_lp_entries(c->T) * sizeof(int)));
   w.ws = Wb.d();
@@ -1206,31 +1214,33 @@ gvi_status ensure_chain_ws(gvi_ctx* c, ChainWs& w) {
   return GVI_OK;
 }
 
+// trial precision formed inside the first pass of a factorisation (see ChainArgs::mix*): out = chain + step (V - chain).
+// V and out are [D | U] in one buffer each: the kernels derive the U parts.
+struct TrialMix { const double* V; double* out; double step; };
+
 ChainArgs make_chain_args(gvi_ctx* c, const ChainWs& w, const double* D, const double* U, const double* rhs, double scale, bool need_back,
-                          double* SigD, double* SigU, double* x, double* hld, bool with_mix) {
+                          double* SigD, double* SigU, double* x, double* hld, const TrialMix* mix = nullptr) {
   ChainArgs a{};
   a.T = c->T; a.n = c->n; a.need_back = need_back ? 1 : 0;
   a.D = D; a.U = U; a.rhs = rhs; a.rhs_scale = scale;
   a.ws = w.ws; a.wsi = w.wsi;
   a.SigD = SigD; a.SigU = SigU; a.x = x; a.hld = hld;
-  a.pred = c->cur_pred; a.pred_val = c->cur_pred_val;
-  // the mixed-in matrix and its output are [D | U] in one buffer each (ngd_trial_state): the kernels derive the U parts
-  a.mixV = with_mix ? c->mix.VD : nullptr;
-  a.mixOut = with_mix ? c->mix.outD : nullptr; a.mix_step = with_mix ? c->mix.step : 0.0;
-  assert(!(with_mix && c->mix.VD) || (c->mix.VU == c->mix.VD + (size_t)c->T * nn_(c) && c->mix.outU == c->mix.outD + (size_t)c->T * nn_(c)));
+  a.pred = c->pipe.pred; a.pred_val = c->pipe.pred_val;
+  a.mixV = mix ? mix->V : nullptr;
+  a.mixOut = mix ? mix->out : nullptr; a.mix_step = mix ? mix->step : 0.0;
   return a;
 }
 
 gvi_status run_chain(gvi_ctx* c, const ChainArgs& a0, const ChainArgs& a1, bool on0, bool on1, const AsmList* AL = nullptr) {
-  hipStream_t st = c->chain_stream ? c->chain_stream : c->stream;
+  hipStream_t st = c->stream;
   StageScope scope(c, STAGE_CHAIN);
   ChainSync sy;
   if (c->chain_merge) {
     constexpr unsigned RING = 64;
     if (!c->chain_sync.p) {
       HIPCK(c, c->chain_sync.ensure(RING * 2 * sizeof(unsigned)));
-      // (once per context) on the launch stream, then waited for: the chain kernels run on non-blocking streams (c->stream,
-      // or c->side for a side-stream solve), which a clear on the null stream would not be ordered before
+      // (once per context) on the launch stream, then waited for: the chain kernels run on a non-blocking stream, which a
+      // clear on the null stream would not be ordered before
       HIPCK(c, hipMemsetAsync(c->chain_sync.p, 0, RING * 2 * sizeof(unsigned), st));
       HIPCK(c, hipStreamSynchronize(st));
     }
@@ -1245,18 +1255,18 @@ gvi_status run_chain(gvi_ctx* c, const ChainArgs& a0, const ChainArgs& a1, bool 
   return GVI_OK;
 }
 
-// log-det (+ optionally marginals) of the chain (D, U) device arrays; carries the fused trial precision (ctx->mix) if set
+// log-det (+ optionally marginals) of the chain (D, U) device arrays
 gvi_status run_bt_factor(gvi_ctx* c, const double* D, const double* U, double* SigD, double* SigU, double* hld) {
   ChainWs w;
-  GVICK(ensure_chain_ws(c, w));
-  const ChainArgs a0 = make_chain_args(c, w, D, U, nullptr, 1.0, SigD != nullptr, SigD, SigU, nullptr, hld, true);
+  GVICK(ensure_chain_ws(c, 0, w));
+  const ChainArgs a0 = make_chain_args(c, w, D, U, nullptr, 1.0, SigD != nullptr, SigD, SigU, nullptr, hld);
   return run_chain(c, a0, a0, true, false);
 }
 
-gvi_status run_bt_solve(gvi_ctx* c, const double* D, const double* U, const double* rhs, double scale, double* x) {
+gvi_status run_bt_solve(gvi_ctx* c, const double* D, const double* U, const double* rhs, double scale, double* x, int ws = 0) {
   ChainWs w;
-  GVICK(ensure_chain_ws(c, w));
-  const ChainArgs a1 = make_chain_args(c, w, D, U, rhs, scale, false, nullptr, nullptr, x, nullptr, false);
+  GVICK(ensure_chain_ws(c, ws, w));
+  const ChainArgs a1 = make_chain_args(c, w, D, U, rhs, scale, false, nullptr, nullptr, x, nullptr);
   return run_chain(c, a1, a1, false, true);
 }
 
@@ -1329,10 +1339,9 @@ gvi_status gvi_ctx_create(int device, int dtype, gvi_ctx** out) {
   if (const char* w = getenv("GVI_FUSE_TRIAL")) c->fuse_trial = std::min(2, std::max(0, atoi(w)));
   if (const char* w = getenv("GVI_SPIN_MS")) c->spin_ms = std::max(0, atoi(w));
   if (const char* w = getenv("GVI_SAFE_PUBLISH")) c->safe_publish = atoi(w) != 0;
-  if (hipEventCreateWithFlags(&c->fork, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void**)&c->host_slot, 128, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+  if (hipHostMalloc((void**)&c->host_slot, 128, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
       hipHostGetDevicePointer((void**)&c->host_slot_dev, c->host_slot, 0) != hipSuccess)
-    return fail(nullptr, GVI_ERR_HIP, "event / host-mapped slot allocation failed");
+    return fail(nullptr, GVI_ERR_HIP, "host-mapped slot allocation failed");
   for (int q = 0; q < 16; ++q) c->host_slot[q] = 0.0;
   *out = c.release();
   return GVI_OK;
@@ -1344,13 +1353,8 @@ gvi_status gvi_ctx_destroy(gvi_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   ctx->sets.clear();
   if (ctx->dist.comm && ctx->dist.ncclCommDestroy) (void)ctx->dist.ncclCommDestroy(ctx->dist.comm);
-  if (ctx->fork) (void)hipEventDestroy(ctx->fork);
   for (auto& r : ctx->stage_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
   for (auto& e : ctx->stage_pool) (void)hipEventDestroy(e);
-  if (ctx->side) (void)hipStreamSynchronize(ctx->side);
-  if (ctx->ev_grad) (void)hipEventDestroy(ctx->ev_grad);
-  for (auto& e : ctx->ev_solve) if (e) (void)hipEventDestroy(e);
-  if (ctx->side) (void)hipStreamDestroy(ctx->side);
   if (ctx->dbg_mask) {                                          // the device-wide log pointer must not outlive its buffer
     double* lg = nullptr;
     (void)hipMemcpyToSymbol(HIP_SYMBOL(gvi_dbg_log), &lg, sizeof(double*));
@@ -1980,29 +1984,23 @@ static SetList make_set_list(gvi_ctx* ctx, int slot) {
   return L;
 }
 
-// prep of every set whose per-pass products are not those of NGD slot i -- one launch
-static gvi_status ngd_refresh_gather(gvi_ctx* ctx, int i, const double* mu_from, const double* dmu, double step);
+static gvi_status ngd_gather_now(gvi_ctx* ctx, int i, const double* mu_from, const double* dmu, double step);
 
 // stand-alone gather of a slot whose gather was left to the next prep (consumers other than prep call this)
 static gvi_status ngd_flush_gather(gvi_ctx* ctx, int i) {
-  NgdState::GatherPending& gp = ctx->ngd.gpend[i];
-  if (!gp.on) return GVI_OK;
-  const NgdState::GatherPending p = gp;
-  gp.on = false;
-  const bool keep = ctx->fuse_gather;
-  ctx->fuse_gather = false;
-  const gvi_status st = ngd_refresh_gather(ctx, i, p.mu_from, p.dmu, p.step);
-  ctx->fuse_gather = keep;
-  return st;
+  const NgdState::GatherPending p = ctx->ngd.gpend[i];
+  if (!p.on) return GVI_OK;
+  return ngd_gather_now(ctx, i, p.mu_from, p.dmu, p.step);
 }
 
+// prep of every set whose per-pass products are not those of NGD slot i -- one launch
 static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
   NgdState& g = ctx->ngd;
   PrepList L;
   L.nsets = 0;
   L.koff[0] = 0;
   L.gather = 0;
-  L.pred = ctx->cur_pred; L.pred_val = ctx->cur_pred_val;
+  L.pred = ctx->pipe.pred; L.pred_val = ctx->pipe.pred_val;
   int dmax = 0;
   bool all = true;
   for (auto& s : ctx->sets) {
@@ -2085,14 +2083,10 @@ static gvi_status ngd_refresh_factor(gvi_ctx* ctx, int i) {
   return run_bt_factor(ctx, D, U, sD, sU, g.hld[i].d());
 }
 
+// gather every set's (mu_k, Sigma_k) into slot i, launched now (one launch).
 // mu_from / dmu / step: form mu[i] = mu_from + step dmu inside the gather launch (trial state); null: mu[i] is current
-static gvi_status ngd_refresh_gather(gvi_ctx* ctx, int i, const double* mu_from, const double* dmu, double step) {
+static gvi_status ngd_gather_now(gvi_ctx* ctx, int i, const double* mu_from, const double* dmu, double step) {
   NgdState& g = ctx->ngd;
-  if (ctx->fuse_gather && ctx->defer_gather && !ctx->sets.empty()) {   // trial state: the prep launch that follows gathers
-    for (auto& s : ctx->sets) if (s->prep_slot == i) s->prep_slot = -1;
-    g.gpend[i].on = true; g.gpend[i].mu_from = mu_from; g.gpend[i].dmu = dmu; g.gpend[i].step = step;
-    return GVI_OK;
-  }
   g.gpend[i].on = false;
   const size_t T = ctx->T, nn = nn_(ctx);
   const int64_t nmu = (int64_t)T * ctx->n;
@@ -2116,9 +2110,18 @@ static gvi_status ngd_refresh_gather(gvi_ctx* ctx, int i, const double* mu_from,
   return GVI_OK;
 }
 
+// the same gather left to the prep launch of slot i that follows (trial state: a cost or full pass of the slot always does;
+// any other reader flushes it, ngd_flush_gather); option fuse_gather = 0: launched now
+static gvi_status ngd_gather_with_prep(gvi_ctx* ctx, int i, const double* mu_from, const double* dmu, double step) {
+  if (!ctx->fuse_gather || ctx->sets.empty()) return ngd_gather_now(ctx, i, mu_from, dmu, step);
+  for (auto& s : ctx->sets) if (s->prep_slot == i) s->prep_slot = -1;
+  ctx->ngd.gpend[i] = {true, mu_from, dmu, step};
+  return GVI_OK;
+}
+
 static gvi_status ngd_refresh(gvi_ctx* ctx, int i) {
   GVICK(ngd_refresh_factor(ctx, i));
-  return ngd_refresh_gather(ctx, i, nullptr, nullptr, 0.0);
+  return ngd_gather_now(ctx, i, nullptr, nullptr, 0.0);
 }
 
 // sum over sets of sum_k E[psi]/T_k at slot i -> exch1[0].  Everything stays on ONE stream: side streams
@@ -2178,7 +2181,7 @@ static inline void cpu_relax() {
 static gvi_status ngd_cost_wait(gvi_ctx* ctx, int i, double* out, double seq_expected = -1.0, int ring = -1) {
   NgdState& g = ctx->ngd;
   const double want = seq_expected >= 0.0 ? seq_expected : ctx->seq;
-  const int rg = ring >= 0 ? ring : ctx->pub_ring;
+  const int rg = ring >= 0 ? ring : ctx->pipe.pub_ring;
   // Spin on the host-mapped sequence word: a blocking stream sync costs tens of us of wake-up latency and would
   // also wait for the speculative work queued behind the publish.  The spin is bounded by WALL TIME (2 ms -- an
   // iteration is < 1 ms); past that the wait sleeps between polls (below).
@@ -2359,9 +2362,9 @@ gvi_status gvi_ngd_init(gvi_ctx* ctx, const double* mu, const double* D, const d
     HIPCK(ctx, g.dmu2[i].ensure(T * n * 8));
   }
   g.gcur = 0; g.grad_valid = false; g.grad_slot = -1;
-  ctx->solve_deferred[0] = ctx->solve_deferred[1] = false;
-  ctx->asm_pending[0] = ctx->asm_pending[1] = false;
-  ctx->last_first_accepted = true;                 // adaptive fusing starts afresh: the pass order of a run must not depend on the previous problem
+  ctx->ngd.solve_deferred[0] = ctx->ngd.solve_deferred[1] = false;
+  ctx->ngd.asm_pending[0] = ctx->ngd.asm_pending[1] = false;
+  ctx->ngd.last_first_accepted = true;             // adaptive fusing starts afresh: the pass order of a run must not depend on the previous problem
   HIPCK(ctx, g.exch1.ensure(8));
   HIPCK(ctx, g.dmu.ensure(T * n * 8));
   HIPCK(ctx, g.dLam.ensure(bt * 8));
@@ -2445,7 +2448,7 @@ static gvi_status plan_sets(gvi_ctx* ctx, int slot, int full, MomPlan* P) {
 // SGPR-operand kernels (Sreg / Sreg in the full pass, Scost / Scost in the cost pass) and the planning graph on three
 // lane-per-point kernels go out as ONE launch; every other combination as one launch per set.
 static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full, const MomPlan* P) {
-  if (full) ++ctx->n_full_pass; else ++ctx->n_cost_pass;
+  if (full) ++ctx->ngd.n_full_pass; else ++ctx->ngd.n_cost_pass;
   MomPlan own[MAX_SETS];
   if (!P) { GVICK(plan_sets(ctx, slot, full, own)); P = own; }
   const size_t ns = ctx->sets.size();
@@ -2572,7 +2575,7 @@ static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot) {
   if (A.nsets == 1) A.koff[2] = A.koff[1];
   const unsigned extra = take_gather(ctx, slot, A, 256);
   GVICK(fill_epi_tail(ctx, A.koff[A.nsets], publish_slot, &A.tail));
-  ++ctx->n_full_pass;
+  ++ctx->ngd.n_full_pass;
   ProfBracket b;
   GVICK(prof_open(ctx, *ctx->sets[0], 0, true, false, ctx->stream, &b));
   const unsigned grid = (unsigned)A.nblk + extra;
@@ -2603,7 +2606,7 @@ static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, MomP
   *planned = true;
   for (int q = 0; q < 3; ++q)
     if (!lane_per_point(P[q]) || P[q].a.nchunk > 4) return GVI_OK;
-  ++ctx->n_full_pass;
+  ++ctx->ngd.n_full_pass;
   Block3Args A{};
   A.nitems = ss[0]->K + ss[1]->K + ss[2]->K;
   A.pipe = P[0].pipe ? 1 : 0;
@@ -2649,11 +2652,15 @@ static gvi_status ngd_moments_full(gvi_ctx* ctx, int slot, int publish_slot = -1
   return ngd_epilogue_all(ctx, 1, publish_slot);
 }
 
+// the gradient solve is parked and goes out beside the next trial factorisation, as the dual launch (ngd_trial_state);
+// else (option side_solve = 0, a one-state chain) it is launched at once
+static bool dual_solve(const gvi_ctx* ctx) { return ctx->side_solve && chain_supported(ctx->n) && ctx->T > 1; }
+
 // assemble-on-load applies: every set chain-structured, the solve of this buffer will go out through the dual launch (or
 // the flushing solve), nobody needs [g | V_D | V_U] in memory before that
 static bool asm_on_load_ok(const gvi_ctx* ctx) {
   if (!ctx->asm_on_load || dist_on(ctx) || ctx->update_rule != GVI_RULE_NGD || ctx->sets.empty()) return false;
-  if (!(ctx->dual_chain && ctx->side_solve && chain_supported(ctx->n) && ctx->T > 1)) return false;
+  if (!dual_solve(ctx)) return false;
   for (auto& s : ctx->sets)
     if (!s->chain_structured && !(s->d == ctx->n && s->K <= ASM_SPARSE_MAX)) return false;    // (sparse unary sets: AsmSet::sp)
   return true;
@@ -2680,18 +2687,18 @@ static gvi_status ngd_scatter_now(gvi_ctx* ctx, int slot, int gb);
 // chain operations that consume the buffer (assemble-on-load)
 static gvi_status ngd_scatter(gvi_ctx* ctx, int slot, int gb) {
   if ((int)ctx->sets.size() <= MAX_SETS && asm_on_load_ok(ctx)) {
-    ctx->asm_pending[gb] = true;
-    ctx->asm_pending[1 - gb] = false;               // its source (the sets' Vdmu / Vddmu) has just been overwritten
+    ctx->ngd.asm_pending[gb] = true;
+    ctx->ngd.asm_pending[1 - gb] = false;               // its source (the sets' Vdmu / Vddmu) has just been overwritten
     return GVI_OK;
   }
-  ctx->asm_pending[gb] = false;
+  ctx->ngd.asm_pending[gb] = false;
   return ngd_scatter_now(ctx, slot, gb);
 }
 
 // stand-alone assemble of a buffer whose assemble was left pending (consumers other than the chain launches)
 static gvi_status ngd_flush_assemble(gvi_ctx* ctx, int gb) {
-  if (!ctx->asm_pending[gb]) return GVI_OK;
-  ctx->asm_pending[gb] = false;
+  if (!ctx->ngd.asm_pending[gb]) return GVI_OK;
+  ctx->ngd.asm_pending[gb] = false;
   return ngd_scatter_now(ctx, ctx->ngd.cur, gb);
 }
 
@@ -2710,14 +2717,14 @@ static gvi_status ngd_scatter_now(gvi_ctx* ctx, int slot, int gb) {
     rec = ctx->dist.send.d(); rlo = ctx->dist.lo[ctx->dist.rank]; rlen = ctx->dist.hi[ctx->dist.rank] - rlo + 1;
   }
   hipLaunchKernelGGL(bt_scatter_all_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                     make_set_list(ctx, slot), ctx->T, ctx->n, eg, eD, eU, ctx->cur_pred, ctx->cur_pred_val, rec, rlo, rlen);
+                     make_set_list(ctx, slot), ctx->T, ctx->n, eg, eD, eU, ctx->pipe.pred, ctx->pipe.pred_val, rec, rlo, rlen);
   HIPCK(ctx, hipGetLastError());
   if (rec) ctx->dist.rec_fresh = true;
   return GVI_OK;
 }
 
 static gvi_status ngd_grad_local(gvi_ctx* ctx, int slot, int gb) {
-  ctx->solve_deferred[gb] = false;                      // a parked solve of this buffer's previous contents is moot
+  ctx->ngd.solve_deferred[gb] = false;                      // a parked solve of this buffer's previous contents is moot
   GVICK(ngd_moments_full(ctx, slot));
   return ngd_scatter(ctx, slot, gb);
 }
@@ -2729,61 +2736,30 @@ static gvi_status ngd_grad_finish(gvi_ctx* ctx, int gb) {
   double* eg = g.exch0[gb].d();
   double* eD = eg + T * n;
   double* eU = eD + T * nn;
-  if (ctx->dual_chain && ctx->side_solve && chain_supported(ctx->n) && ctx->T > 1) {
-    ctx->solve_deferred[gb] = true;                     // goes out with the next trial factorisation (ngd_trial_state)
+  if (dual_solve(ctx)) {
+    g.solve_deferred[gb] = true;                        // goes out with the next trial factorisation (ngd_trial_state)
     return GVI_OK;
   }
   GVICK(ngd_flush_assemble(ctx, gb));
-  if (ctx->side_solve && chain_supported(ctx->n)) {
-    // the solve only feeds mu_trial; the trial precision and its factorisation need Vddmu alone, so the solve goes
-    // to the side stream and ngd_join_solve() waits for it right before the first reader of dmu
-    if (!ctx->side) {
-      HIPCK(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-      HIPCK(ctx, hipEventCreateWithFlags(&ctx->ev_grad, hipEventDisableTiming));
-      for (auto& e : ctx->ev_solve) HIPCK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    HIPCK(ctx, hipEventRecord(ctx->ev_grad, ctx->stream));
-    HIPCK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_grad, 0));
-    ctx->chain_stream = ctx->side; ctx->chain_ws = 1;
-    const gvi_status st = run_bt_solve(ctx, eD, eU, eg, -1.0, g.dmu2[gb].d());
-    ctx->chain_stream = nullptr; ctx->chain_ws = 0;
-    GVICK(st);
-    HIPCK(ctx, hipEventRecord(ctx->ev_solve[gb], ctx->side));
-    ctx->solve_pending[gb] = true;
-    return GVI_OK;
-  }
   return run_bt_solve(ctx, eD, eU, eg, -1.0, g.dmu2[gb].d());
 }
 
-// main stream waits for a side-stream solve of gradient buffer gb (no-op when none is pending)
+// a reader of dmu / [g | V_D | V_U] of gradient buffer gb other than the next trial: a parked solve that nobody fused with a
+// factorisation runs now, in stream order, on the second workspace; a pending assemble goes with it, or alone
 static gvi_status ngd_join_solve(gvi_ctx* ctx, int gb) {
-  if (ctx->solve_deferred[gb]) {                        // nobody fused it with a factorisation: run it now, in stream order
-    ctx->solve_deferred[gb] = false;
-    NgdState& g = ctx->ngd;
-    const size_t T = ctx->T, n = ctx->n, nn = n * n;
-    double* eg = g.exch0[gb].d();
-    ctx->chain_ws = 1;
-    gvi_status st;
-    if (ctx->asm_pending[gb]) {
-      ctx->asm_pending[gb] = false;
-      ChainWs w;
-      st = ensure_chain_ws(ctx, w);
-      if (st == GVI_OK) {
-        ChainArgs a1 = make_chain_args(ctx, w, eg + T * n, eg + T * n + T * nn, eg, -1.0, false, nullptr, nullptr, g.dmu2[gb].d(), nullptr, false);
-        a1.asm_on = 1; a1.asmG = eg; a1.asmD = eg + T * n; a1.asmU = eg + T * n + T * nn;
-        const AsmList AL = make_asm_list(ctx);
-        st = run_chain(ctx, a1, a1, false, true, &AL);
-      }
-    } else st = run_bt_solve(ctx, eg + T * n, eg + T * n + T * nn, eg, -1.0, g.dmu2[gb].d());
-    ctx->chain_ws = 0;
-    return st;
-  }
-  GVICK(ngd_flush_assemble(ctx, gb));
-  if (ctx->solve_pending[gb]) {
-    HIPCK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_solve[gb], 0));
-    ctx->solve_pending[gb] = false;
-  }
-  return GVI_OK;
+  NgdState& g = ctx->ngd;
+  if (!g.solve_deferred[gb]) return ngd_flush_assemble(ctx, gb);
+  g.solve_deferred[gb] = false;
+  const size_t T = ctx->T, n = ctx->n, nn = n * n;
+  double* eg = g.exch0[gb].d();
+  if (!g.asm_pending[gb]) return run_bt_solve(ctx, eg + T * n, eg + T * n + T * nn, eg, -1.0, g.dmu2[gb].d(), 1);
+  g.asm_pending[gb] = false;
+  ChainWs w;
+  GVICK(ensure_chain_ws(ctx, 1, w));
+  ChainArgs a1 = make_chain_args(ctx, w, eg + T * n, eg + T * n + T * nn, eg, -1.0, false, nullptr, nullptr, g.dmu2[gb].d(), nullptr);
+  a1.asm_on = 1; a1.asmG = eg; a1.asmD = eg + T * n; a1.asmU = eg + T * n + T * nn;
+  const AsmList AL = make_asm_list(ctx);
+  return run_chain(ctx, a1, a1, false, true, &AL);
 }
 
 gvi_status gvi_ngd_gradients_local(gvi_ctx* ctx) {
@@ -2816,62 +2792,32 @@ static gvi_status ngd_trial_state(gvi_ctx* ctx, double step) {
   const int c = g.cur, t = 1 - c;
   g.cost_valid[t] = false;
   g.spec_ready = false;
-  if (ctx->solve_deferred[g.gcur]) {
-    // Lam_trial formed and factorised (log-det + marginals) and the parked gradient solve, side by side in three launches
+  if (g.solve_deferred[g.gcur]) {
+    // Lam_trial formed and factorised (log-det + marginals) and the parked gradient solve, side by side in three launches.
+    // Lam_trial = Lam + step (V - Lam) is formed by the first pass of the factorisation while it loads the chain (and written
+    // to Lam[t] there): "Lam[c] mixed with V" is factorised, no trial_kernel goes first.
     const size_t T = ctx->T, Tnn = T * nn_(ctx);
     double* eg = g.exch0[g.gcur].d();
     const double* V = eg + Tn;
-    ctx->mix.VD = V; ctx->mix.VU = V + Tnn; ctx->mix.outD = g.Lam[t].d(); ctx->mix.outU = g.Lam[t].d() + Tnn; ctx->mix.step = step;
+    const TrialMix mix{V, g.Lam[t].d(), step};
     ChainWs w0, w1;
-    ctx->chain_ws = 0;
-    gvi_status fs = ensure_chain_ws(ctx, w0);
-    ctx->chain_ws = 1;
-    if (fs == GVI_OK) fs = ensure_chain_ws(ctx, w1);
-    ctx->chain_ws = 0;
-    if (fs == GVI_OK) {
-      double* sD = g.Sig[t].d();
-      ChainArgs a0 = make_chain_args(ctx, w0, g.Lam[c].d(), g.Lam[c].d() + Tnn, nullptr, 1.0, true, sD, sD + Tnn, nullptr, g.hld[t].d(), true);
-      ChainArgs a1 = make_chain_args(ctx, w1, V, V + Tnn, eg, -1.0, false, nullptr, nullptr, g.dmu2[g.gcur].d(), nullptr, false);
-      if (ctx->asm_pending[g.gcur]) {
-        // the assemble of this gradient buffer was left to these launches: both operations form V from the per-factor
-        // results while they load, the solve leaves [g | V_D | V_U] in the buffer (later trials of this iteration read it)
-        ctx->asm_pending[g.gcur] = false;
-        a0.asm_on = a1.asm_on = 1;
-        a1.asmG = eg; a1.asmD = eg + Tn; a1.asmU = eg + Tn + Tnn;
-        const AsmList AL = make_asm_list(ctx);
-        fs = run_chain(ctx, a0, a1, true, true, &AL);
-      } else fs = run_chain(ctx, a0, a1, true, true);
-    }
-    ctx->mix = gvi_ctx::Mix();
-    GVICK(fs);
-    ctx->solve_deferred[g.gcur] = false;
-    ctx->defer_gather = true;               // mu_trial and the gather ride in the prep launch of the cost pass
-    const gvi_status gs = ngd_refresh_gather(ctx, t, g.mu[c].d(), g.dmu2[g.gcur].d(), step);
-    ctx->defer_gather = false;
-    GVICK(gs);
-  } else if (ctx->solve_pending[g.gcur]) {
-    // precision part first (needs no dmu), factorise, then join the side-stream solve and form mu_trial
-    if (chain_supported(ctx->n) && ctx->T > 1) {
-      // Lam_trial = Lam + step (V - Lam) is formed by the first BCR pass while it loads the chain (and written to
-      // Lam[t] there): factorise "Lam[c] mixed with V" instead of launching trial_kernel first
-      const size_t Tnn = (size_t)ctx->T * nn_(ctx);
-      const double* V = g.exch0[g.gcur].d() + Tn;
-      ctx->mix.VD = V; ctx->mix.VU = V + Tnn; ctx->mix.outD = g.Lam[t].d(); ctx->mix.outU = g.Lam[t].d() + Tnn; ctx->mix.step = step;
-      double* sD = g.Sig[t].d();
-      const gvi_status fs = run_bt_factor(ctx, g.Lam[c].d(), g.Lam[c].d() + Tnn, sD, sD + Tnn, g.hld[t].d());
-      ctx->mix = gvi_ctx::Mix();
-      GVICK(fs);
-    } else {
-      hipLaunchKernelGGL(trial_kernel, dim3((unsigned)((bt + 255) / 256)), dim3(256), 0, ctx->stream, (int64_t)0, (int64_t)bt,
-                         step, g.mu[c].d(), g.dmu2[g.gcur].d(), g.Lam[c].d(), g.exch0[g.gcur].d() + Tn, g.mu[t].d(), g.Lam[t].d());
-      HIPCK(ctx, hipGetLastError());
-      GVICK(ngd_refresh_factor(ctx, t));
-    }
-    GVICK(ngd_join_solve(ctx, g.gcur));
-    ctx->defer_gather = true;               // mu_trial and the gather ride in the prep launch of the cost pass
-    const gvi_status gs = ngd_refresh_gather(ctx, t, g.mu[c].d(), g.dmu2[g.gcur].d(), step);
-    ctx->defer_gather = false;
-    GVICK(gs);
+    GVICK(ensure_chain_ws(ctx, 0, w0));
+    GVICK(ensure_chain_ws(ctx, 1, w1));
+    double* sD = g.Sig[t].d();
+    ChainArgs a0 = make_chain_args(ctx, w0, g.Lam[c].d(), g.Lam[c].d() + Tnn, nullptr, 1.0, true, sD, sD + Tnn, nullptr, g.hld[t].d(), &mix);
+    ChainArgs a1 = make_chain_args(ctx, w1, V, V + Tnn, eg, -1.0, false, nullptr, nullptr, g.dmu2[g.gcur].d(), nullptr);
+    if (g.asm_pending[g.gcur]) {
+      // the assemble of this gradient buffer was left to these launches: both operations form V from the per-factor
+      // results while they load, the solve leaves [g | V_D | V_U] in the buffer (later trials of this iteration read it)
+      g.asm_pending[g.gcur] = false;
+      a0.asm_on = a1.asm_on = 1;
+      a1.asmG = eg; a1.asmD = eg + Tn; a1.asmU = eg + Tn + Tnn;
+      const AsmList AL = make_asm_list(ctx);
+      GVICK(run_chain(ctx, a0, a1, true, true, &AL));
+    } else GVICK(run_chain(ctx, a0, a1, true, true));
+    g.solve_deferred[g.gcur] = false;
+    // mu_trial and the gather ride in the prep launch of the cost pass
+    GVICK(ngd_gather_with_prep(ctx, t, g.mu[c].d(), g.dmu2[g.gcur].d(), step));
   } else {
     hipLaunchKernelGGL(trial_kernel, dim3((unsigned)((Tn + bt + 255) / 256)), dim3(256), 0, ctx->stream, (int64_t)Tn,
                        (int64_t)bt, step, g.mu[c].d(), g.dmu2[g.gcur].d(), g.Lam[c].d(), g.exch0[g.gcur].d() + Tn,
@@ -2935,12 +2881,15 @@ gvi_status gvi_ngd_spec_gradients_finish(gvi_ctx* ctx) {
   return GVI_OK;
 }
 
+// after an accept: the gradients queued at the trial state (the other buffer) are those of the current state
+static void take_spec_gradients(NgdState& g) { g.gcur = 1 - g.gcur; g.grad_valid = true; g.grad_slot = g.cur; }
+
 gvi_status gvi_ngd_accept_spec(gvi_ctx* ctx) {
   GVICK(ngd_check(ctx));
   if (!ctx->ngd.spec_ready) return fail(ctx, GVI_ERR_STATE, "no speculative gradients at the trial state");
   GVICK(gvi_ngd_accept(ctx));
-  NgdState& g = ctx->ngd;
-  g.gcur = 1 - g.gcur; g.grad_valid = true; g.grad_slot = g.cur; g.spec_ready = false;
+  take_spec_gradients(ctx->ngd);
+  ctx->ngd.spec_ready = false;
   return GVI_OK;
 }
 
@@ -2961,7 +2910,7 @@ static gvi_status ngd_iteration_entry(gvi_ctx* ctx, double* c0) {
   NgdState& g = ctx->ngd;
   const bool have_grad = g.grad_valid && g.grad_slot == g.cur;
   if (!g.cost_valid[g.cur] && !have_grad && ctx->fuse_trial != 0 && !dist_on(ctx) && !ctx->sets.empty()) {
-    ctx->solve_deferred[g.gcur] = false;
+    ctx->ngd.solve_deferred[g.gcur] = false;
     GVICK(ngd_moments_full(ctx, g.cur, g.cur));          // epilogue + ordered cost sum + publish in one launch
     GVICK(ngd_scatter(ctx, g.cur, g.gcur));
     GVICK(ngd_grad_finish(ctx, g.gcur));
@@ -2985,7 +2934,7 @@ static gvi_status ngd_linesearch(gvi_ctx* ctx, double c0, double step, int cnt, 
     const int t = 1 - g.cur;
     const bool spec = cnt == 0 && ctx->speculate;
     GVICK(ngd_trial_state(ctx, step));
-    const bool fuse = spec && (ctx->fuse_trial == 1 || (ctx->fuse_trial == 2 && ctx->last_first_accepted));
+    const bool fuse = spec && (ctx->fuse_trial == 1 || (ctx->fuse_trial == 2 && ctx->ngd.last_first_accepted));
     if (fuse) {
       // Fused form: ONE full moments pass at the trial point serves both the trial cost (its m0 column)
       // and -- if the trial is accepted -- the next iteration's gradients.  Same numbers, one psi pass
@@ -3031,10 +2980,10 @@ static gvi_status ngd_linesearch(gvi_ctx* ctx, double c0, double step, int cnt, 
     }
     GVICK(ngd_cost_wait(ctx, t, &c1));
     ++cnt;
-    if (cnt == 1) ctx->last_first_accepted = c1 < c0;
+    if (cnt == 1) ctx->ngd.last_first_accepted = c1 < c0;
     if (c1 < c0) {                                 // NaN compares false -> rejected
       GVICK(gvi_ngd_accept(ctx));
-      if (spec) { g.gcur = 1 - g.gcur; g.grad_valid = true; g.grad_slot = g.cur; }
+      if (spec) take_spec_gradients(g);
       ok = 1;
       break;
     }
@@ -3071,46 +3020,37 @@ gvi_status gvi_ngd_step(gvi_ctx* ctx, double step_size_base, int max_backtrack, 
 // (tests/test_gpu_parity.py::test_ngd_run_equals_the_same_sequence_of_steps, with rejected first trials).
 namespace {
 struct PipeSnapshot {
-  int cur, gcur, grad_slot;
-  bool grad_valid, have_trial, spec_ready, cost_valid[2], solve_deferred[2], solve_pending[2], asm_pending[2], last_first_accepted;
-  double cost[2];
-  NgdState::GatherPending gpend[2];
-  int64_t n_full, n_cost;
-  long profile_count;
+  NgdBook book;
   std::vector<int> prep_slot, warm_count;
 };
 
 void pipe_save(const gvi_ctx* c, PipeSnapshot& p) {
-  const NgdState& g = c->ngd;
-  p.cur = g.cur; p.gcur = g.gcur; p.grad_slot = g.grad_slot; p.grad_valid = g.grad_valid; p.have_trial = g.have_trial;
-  p.spec_ready = g.spec_ready; p.last_first_accepted = c->last_first_accepted;
-  for (int i = 0; i < 2; ++i) {
-    p.cost_valid[i] = g.cost_valid[i]; p.cost[i] = g.cost[i]; p.gpend[i] = g.gpend[i];
-    p.solve_deferred[i] = c->solve_deferred[i]; p.solve_pending[i] = c->solve_pending[i]; p.asm_pending[i] = c->asm_pending[i];
-  }
-  p.n_full = c->n_full_pass; p.n_cost = c->n_cost_pass; p.profile_count = c->profile_count;
+  p.book = c->ngd;
   p.prep_slot.clear(); p.warm_count.clear();
   for (const auto& s : c->sets) { p.prep_slot.push_back(s->prep_slot); p.warm_count.push_back(s->warm_count); }
 }
 
 void pipe_restore(gvi_ctx* c, const PipeSnapshot& p) {
-  NgdState& g = c->ngd;
-  g.cur = p.cur; g.gcur = p.gcur; g.grad_slot = p.grad_slot; g.grad_valid = p.grad_valid; g.have_trial = p.have_trial;
-  g.spec_ready = p.spec_ready; c->last_first_accepted = p.last_first_accepted;
-  for (int i = 0; i < 2; ++i) {
-    g.cost_valid[i] = p.cost_valid[i]; g.cost[i] = p.cost[i]; g.gpend[i] = p.gpend[i];
-    c->solve_deferred[i] = p.solve_deferred[i]; c->solve_pending[i] = p.solve_pending[i]; c->asm_pending[i] = p.asm_pending[i];
-  }
-  c->n_full_pass = p.n_full; c->n_cost_pass = p.n_cost; c->profile_count = p.profile_count;
+  static_cast<NgdBook&>(c->ngd) = p.book;
   for (size_t i = 0; i < c->sets.size(); ++i) { c->sets[i]->prep_slot = p.prep_slot[i]; c->sets[i]->warm_count = p.warm_count[i]; }
 }
+
+// the pipelined run's window (gvi_ctx::PipeWindow) for the launches queued during the lifetime; the plain iteration again on
+// every way out
+struct PipeWindowScope {
+  gvi_ctx* c;
+  PipeWindowScope(gvi_ctx* ctx, const gvi_ctx::PipeWindow& w) : c(ctx) { c->pipe = w; }
+  ~PipeWindowScope() { c->pipe = gvi_ctx::PipeWindow(); }
+  PipeWindowScope(const PipeWindowScope&) = delete;
+  PipeWindowScope& operator=(const PipeWindowScope&) = delete;
+};
 
 // every launch of a queued iteration must be one of the predicated kernels: the dual chain launches, the fused factor pass or
 // the prep launch with the fused gather + the sets' moments launches (every MomArgs / OrbitArgs kernel) + the epilogue with its
 // tail, the assemble
 bool pipe_ok(const gvi_ctx* c) {
   if (!c->pipeline || dist_on(c) || c->update_rule != GVI_RULE_NGD || !c->speculate || c->fuse_trial == 0) return false;
-  if (!(c->dual_chain && c->side_solve && chain_supported(c->n) && c->T > 1)) return false;
+  if (!dual_solve(c)) return false;
   if (!c->fuse_gather || !c->pair_fuse || c->profile_all || c->sets.empty() || (int)c->sets.size() > MAX_SETS) return false;
   for (const auto& s : c->sets)
     if (s->K <= 0 || s->kind == KIND_HOST_CALLBACK) return false;       // (host-evaluated psi: the host is in the loop anyway)
@@ -3118,8 +3058,10 @@ bool pipe_ok(const gvi_ctx* c) {
 }
 }  // namespace
 
-// one iteration's launches with a fused first trial (the non-sharded branch of ngd_linesearch, first trial)
-static gvi_status pipe_enqueue(gvi_ctx* ctx, double step) {
+// one iteration's launches with a fused first trial (the non-sharded branch of ngd_linesearch, first trial), queued in
+// the window w
+static gvi_status pipe_enqueue(gvi_ctx* ctx, double step, const gvi_ctx::PipeWindow& w) {
+  PipeWindowScope window(ctx, w);
   NgdState& g = ctx->ngd;
   const int t = 1 - g.cur;
   GVICK(ngd_trial_state(ctx, step));
@@ -3144,23 +3086,26 @@ gvi_status gvi_ngd_run(gvi_ctx* ctx, int max_iters, double step_size_base, int m
     ++done;
   };
   auto finish = [&](gvi_status st) {
-    ctx->cur_pred = nullptr; ctx->pipe_tail = false; ctx->pipe_c0_imm = true; ctx->pub_ring = 0;
     if (iters_done) *iters_done = done;
     return st;
+  };
+  gvi_status plain_st = GVI_OK;
+  auto plain_iteration = [&]() {     // one gvi_ngd_step, recorded; false: the run ends here (plain_st)
+    double c0 = 0.0, c1 = 0.0;
+    int ok = 0, nt = 0;
+    plain_st = gvi_ngd_step(ctx, step_size_base, max_backtrack, &c0, &ok, &c1, &nt);
+    if (plain_st != GVI_OK) return false;
+    record(c0, ok, c1, nt);
+    return ok != 0;
   };
   bool pending = false;          // the launches of iteration `done` are already queued (speculatively; their predicate held)
   double pend_seq = 0.0;
   int pend_ring = 0;
   const double step1 = step_size_base * 0.75;
   while (done < max_iters) {
-    const bool fused_first = ctx->fuse_trial == 1 || (ctx->fuse_trial == 2 && ctx->last_first_accepted);
-    if (!pending && !(pipe_ok(ctx) && fused_first)) {           // the plain iteration
-      double c0 = 0.0, c1 = 0.0;
-      int ok = 0, nt = 0;
-      const gvi_status st = gvi_ngd_step(ctx, step_size_base, max_backtrack, &c0, &ok, &c1, &nt);
-      if (st != GVI_OK) return finish(st);
-      record(c0, ok, c1, nt);
-      if (!ok) break;
+    const bool fused_first = ctx->fuse_trial == 1 || (ctx->fuse_trial == 2 && g.last_first_accepted);
+    if (!pending && !(pipe_ok(ctx) && fused_first)) {
+      if (!plain_iteration()) return finish(plain_st);
       continue;
     }
     double c0 = 0.0, seq_i = 0.0;
@@ -3168,22 +3113,17 @@ gvi_status gvi_ngd_run(gvi_ctx* ctx, int max_iters, double step_size_base, int m
     if (!pending) {
       gvi_status st = ngd_iteration_entry(ctx, &c0);
       if (st != GVI_OK) return finish(st);
-      if (!ctx->solve_deferred[g.gcur]) {                       // not in the dual-launch state: one plain iteration
-        double c1 = 0.0;
-        int ok = 0, nt = 0;
-        st = gvi_ngd_step(ctx, step_size_base, max_backtrack, &c0, &ok, &c1, &nt);
-        if (st != GVI_OK) return finish(st);
-        record(c0, ok, c1, nt);
-        if (!ok) break;
+      if (!g.solve_deferred[g.gcur]) {                          // not in the dual-launch state
+        if (!plain_iteration()) return finish(plain_st);
         continue;
       }
       if (!ctx->pipe_dev.p) {
         HIPCK(ctx, ctx->pipe_dev.ensure(64));
         HIPCK(ctx, hipMemsetAsync(ctx->pipe_dev.p, 0, 64, ctx->stream));
       }
-      ctx->cur_pred = nullptr; ctx->pipe_tail = true; ctx->pipe_c0_imm = true; ctx->pipe_c0 = c0; ctx->pub_ring = 0;
-      st = pipe_enqueue(ctx, step1);
-      ctx->pipe_tail = false;
+      gvi_ctx::PipeWindow w;
+      w.tail = true; w.c0 = c0;                                 // unpredicated, the current cost as an immediate, ring slot 0
+      st = pipe_enqueue(ctx, step1, w);
       if (st != GVI_OK) return finish(st);
       seq_i = ctx->seq; ring_i = 0;
     } else {
@@ -3197,14 +3137,14 @@ gvi_status gvi_ngd_run(gvi_ctx* ctx, int max_iters, double step_size_base, int m
       pipe_save(ctx, snap);
       gvi_status st = gvi_ngd_accept(ctx);                      // provisional: cur <- trial slot
       if (st != GVI_OK) { pipe_restore(ctx, snap); return finish(st); }
-      g.gcur = 1 - g.gcur; g.grad_valid = true; g.grad_slot = g.cur;
-      ctx->last_first_accepted = true;
+      take_spec_gradients(g);
+      g.last_first_accepted = true;
       // (the accept words alternate like the host slots: this iteration's own tail writes the OTHER word, so its assemble,
       // which runs after that tail, still sees the predicate it was queued under)
-      ctx->cur_pred = ctx->pipe_dev.d() + ring_i; ctx->cur_pred_val = seq_i;
-      ctx->pipe_tail = true; ctx->pipe_c0_imm = false; ctx->pub_ring = 1 - ring_i;
-      st = pipe_enqueue(ctx, step1);
-      ctx->cur_pred = nullptr; ctx->pipe_tail = false; ctx->pipe_c0_imm = true; ctx->pub_ring = 0;
+      gvi_ctx::PipeWindow w;
+      w.pred = ctx->pipe_dev.d() + ring_i; w.pred_val = seq_i;
+      w.tail = true; w.c0_imm = false; w.pub_ring = 1 - ring_i;
+      st = pipe_enqueue(ctx, step1, w);
       if (st != GVI_OK) { pipe_restore(ctx, snap); return finish(st); }   // undo the provisional accept (cur / gcur flipped)
       seq_n = ctx->seq;
     }
@@ -3215,11 +3155,11 @@ gvi_status gvi_ngd_run(gvi_ctx* ctx, int max_iters, double step_size_base, int m
       if (st != GVI_OK) { if (spec_next) pipe_restore(ctx, snap); return finish(st); }
     }
     if (c1 < c0) {                                               // accepted (NaN compares false)
-      ctx->last_first_accepted = true;
+      g.last_first_accepted = true;
       if (!spec_next) {
         const gvi_status st = gvi_ngd_accept(ctx);
         if (st != GVI_OK) return finish(st);
-        g.gcur = 1 - g.gcur; g.grad_valid = true; g.grad_slot = g.cur;
+        take_spec_gradients(g);
       }
       record(c0, 1, c1, 1);
       pending = spec_next; pend_seq = seq_n; pend_ring = 1 - ring_i;
@@ -3228,7 +3168,7 @@ gvi_status gvi_ngd_run(gvi_ctx* ctx, int max_iters, double step_size_base, int m
     // first trial rejected: the device skipped everything queued for iteration i + 1
     if (spec_next) pipe_restore(ctx, snap);
     pending = false;
-    ctx->last_first_accepted = false;
+    g.last_first_accepted = false;
     double c1b = c0;
     int ok = 0, cnt = 1;
     if (cnt <= max_backtrack) {
@@ -3279,12 +3219,7 @@ gvi_status gvi_prox_gradients(gvi_ctx* ctx, double h) {
     f.m = 0; f.S = s.jko_S.d(); f.Sinv = s.jko_Sinv.d(); f.Lam = s.jko_Lam.d(); f.H = nullptr; f.Hq = nullptr; f.u0 = nullptr;
     f.jko_h = h;
     f.chol = 0;                                            // the JKO map is a function of the eigenvalues
-    const int dp = s.d + (s.d & 1);
-    const size_t lds = (size_t)(4 * dd + 2 * dp + 3 * d) * 8 + (size_t)dp * 4 + 16;
-    if (s.d <= 8) hipLaunchKernelGGL(prep_kernel<1>, dim3(s.K), dim3(64), lds, ctx->stream, f, (const double*)nullptr, (const double*)s.jko_half.d());
-    else if (s.d <= 16) hipLaunchKernelGGL(prep_kernel<4>, dim3(s.K), dim3(64), lds, ctx->stream, f, (const double*)nullptr, (const double*)s.jko_half.d());
-    else if (s.d <= 32) hipLaunchKernelGGL(prep_kernel<16>, dim3(s.K), dim3(64), lds, ctx->stream, f, (const double*)nullptr, (const double*)s.jko_half.d());
-    else return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
+    GVICK(launch_prep(ctx, f, nullptr, s.jko_half.d(), ctx->stream));
     hipLaunchKernelGGL(jko_finish_kernel, dim3((unsigned)((K * dd + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCK(ctx, hipGetLastError());
   }
@@ -3343,7 +3278,7 @@ gvi_status gvi_ngd_set_mode(gvi_ctx* ctx, int speculate, int fuse_trial) {
   if (fuse_trial < 0 || fuse_trial > 2) return fail(ctx, GVI_ERR_ARG, "fuse_trial must be 0, 1 or 2");
   ctx->speculate = speculate != 0;
   ctx->fuse_trial = fuse_trial;
-  ctx->last_first_accepted = true;
+  ctx->ngd.last_first_accepted = true;
   return GVI_OK;
 }
 
@@ -3433,9 +3368,9 @@ gvi_status gvi_dist_info(const gvi_ctx* ctx, int* rank, int* world, int* records
 
 gvi_status gvi_ngd_counters(gvi_ctx* ctx, int64_t* full_passes, int64_t* cost_passes, int reset) {
   if (!ctx) return GVI_ERR_ARG;
-  if (full_passes) *full_passes = ctx->n_full_pass;
-  if (cost_passes) *cost_passes = ctx->n_cost_pass;
-  if (reset) ctx->n_full_pass = ctx->n_cost_pass = 0;
+  if (full_passes) *full_passes = ctx->ngd.n_full_pass;
+  if (cost_passes) *cost_passes = ctx->ngd.n_cost_pass;
+  if (reset) ctx->ngd.n_full_pass = ctx->ngd.n_cost_pass = 0;
   return GVI_OK;
 }
 
@@ -3514,7 +3449,7 @@ gvi_status gvi_profile_enable(gvi_ctx* ctx, int on) {
   ctx->profile = on != 0;
   ctx->profile_all = on == 2;
   ctx->profile_every = on == 3 ? 8 : 1;
-  ctx->profile_count = 0;
+  ctx->ngd.profile_count = 0;
   for (auto& s : ctx->sets) s->ev_set[0] = s->ev_set[1] = false;
   return GVI_OK;
 }
@@ -3569,7 +3504,6 @@ gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value) {
   else if (n == "pair_fuse") ctx->pair_fuse = value != 0;
   else if (n == "fuse_gather") ctx->fuse_gather = value != 0;
   else if (n == "side_solve") ctx->side_solve = value != 0;
-  else if (n == "dual_chain") ctx->dual_chain = value != 0;
   else if (n == "warm_start") ctx->warm_start = value != 0;
   else if (n == "no_scost") ctx->no_scost = value != 0;
   else if (n == "target_waves") ctx->target_waves = std::max(1, value);

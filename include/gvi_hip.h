@@ -512,7 +512,8 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *
  *   environment          option              default  what                                                   results
  *   GVI_ORBIT            orbit               1        sign-orbit psi kernel (0: lane-per-point kernels)      agree to 1e-10
- *   GVI_FUSED            fused               1        one-launch factor pass (0: prep -> psi -> epilogue)    bit-identical
+ *   GVI_FUSED            fused               1        one-launch factor pass (0: prep -> psi -> epilogue)    rounding (chain graphs),
+ *                                                                                                            bit-identical (block3)
  *   GVI_ASM_ON_LOAD      assemble_on_load    1        assemble inside the chain's first pass                 bit-identical
  *   GVI_PIPELINE         pipeline            1        gvi_ngd_run queues iteration i + 1 ahead of cost i     bit-identical
  *   GVI_CHAIN_WAVE       chain_wave          1        lane-per-node chain kernel for T <= 65, n <= 2         bit-identical
@@ -524,7 +525,8 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *   GVI_CHAIN_MERGE      chain_merge         1        top pass + first backward pass of the chain in one     bit-identical
  *                                                     launch (0: one launch per pass)
  *   GVI_FUSE_TRIAL       (gvi_ngd_set_mode)  2        0 reference pass order, 1 fused trial, 2 adaptive      identical iterates
- *   GVI_SIDE_SOLVE       side_solve          1        gradient solve beside the trial factorisation          bit-identical
+ *   GVI_SIDE_SOLVE       side_solve          1        gradient solve beside the trial factorisation, as one  bit-identical
+ *                                                     dual launch (0, or a one-state chain: launched at once)
  *   GVI_NO_PAIR          pair_fuse           0 / 1    both chain sets in one psi launch (lane-per-point)     bit-identical
  *   GVI_NO_FUSE_GATHER   fuse_gather         0 / 1    gather inside the prep launch                          bit-identical
  *   GVI_NO_SCOST         no_scost            0        cost pass on the full kernel instead of the cost one   bit-identical
@@ -540,8 +542,8 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *                                                     the output buffer whatever the size)
  *   --                   trust_table_degree  0        gvi_factors_add_table: the table is the rule of degree p  --
  *   --                   jacobi_tol_exp      -34      stopping threshold of the symmetric-root solve         rounding
- *   --                   split_flush, target_waves, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, dual_chain,
- *                        warm_start: launch geometry / summation order of individual kernels (tests/test_gpu_parity.py A/Bs)
+ *   --                   split_flush, target_waves, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, warm_start:
+ *                        launch geometry / summation order of individual kernels (tests/test_gpu_parity.py A/Bs)
  * Build-time only: GVI_FUSED_TIMING (phase stamps; GVI_FUSED_DBG=8 prints them), built beside the in-tree library by
  * tools/build_variant.py and selected with GVI_LIB_PATH (the in-tree library is always built without defines).
  *
@@ -575,7 +577,7 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * releases); 0: one launch per pass.  The wait is bounded (1 s); on a time-out the waiting workgroups take NaN for what they
  * would have read, so the affected marginals / solution are NaN and the step is rejected -- value 2 is the test of that path
  * (the word is stored wrong on purpose).
- * Names: split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, dual_chain, warm_start, no_scost, target_waves,
+ * Names: split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, warm_start, no_scost, target_waves,
  * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge, asm_dense, chain_pair,
  * trust_table_degree, safe_publish, sample_sweep, solve_lds. */
 gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value);

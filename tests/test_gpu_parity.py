@@ -686,8 +686,8 @@ def test_step_scheduling_modes_give_identical_iterates(speculate, fuse):
 
 
 def test_side_stream_solve_gives_identical_iterates(monkeypatch):
-    """GVI_SIDE_SOLVE (default on): the gradient solve runs on a side stream beside the trial factorisation and is
-    joined before mu_trial is formed.  Same arithmetic, so the iterates are bit-identical to the one-stream order,
+    """GVI_SIDE_SOLVE: 0 launches the gradient solve at once, behind the assemble; 1 (default) parks it and sends it out
+    beside the next trial factorisation as one dual launch.  Same arithmetic, so the iterates are bit-identical,
     including rejected trials (huge base step) where the speculative buffer is dropped."""
     ch = make_chain("c2")
     out = []
