@@ -13,6 +13,7 @@ PSI_RANGE_1D, PSI_QUAD_PRIOR, PSI_FIXED_PRIOR, PSI_HOST_CALLBACK, PSI_HINGE_SDF_
 PSI_HINGE_SDF_2D_BODY, PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM = 5, 6, 7
 PSI_HINGE_SDF_2D_SEG, PSI_HINGE_SDF_3D_SEG = 8, 9
 PSI_HINGE_BOX = 10
+PSI_HINGE_HALFSPACE = 11
 RULE_NGD, RULE_PROX_JKO = 0, 1
 GVI_F64, GVI_F32 = 0, 1
 

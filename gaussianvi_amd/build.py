@@ -73,7 +73,8 @@ def build_examples(force: bool = False) -> str:
     out_dir = os.path.join(ROOT, "examples", "bin")
     os.makedirs(out_dir, exist_ok=True)
     first = None
-    for name in ("1d_example", "1d_example_prox", "planar_example", "factorwise_example", "ltv_chain_example", "planar_limits_example"):
+    for name in ("1d_example", "1d_example_prox", "planar_example", "factorwise_example", "ltv_chain_example", "planar_limits_example",
+                 "planar_corridor_example"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         exe = os.path.join(out_dir, name)
         deps = [src, os.path.join(ROOT, "include", "gvi", "gvi_host.hpp"), os.path.join(ROOT, "include", "gvi", "factorized_opts_LTV.hpp"),

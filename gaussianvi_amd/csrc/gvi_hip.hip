@@ -95,9 +95,9 @@ struct FactorSet {
   bool use_orbit = false;
   bool use_opsi = false;              // sign-orbit kernel for the non-polynomial psi kinds (kernels_orbit_psi.hpp)
   int arm_ndof = 0;
-  int seg_J = 0;                      // HINGE_SDF_*_SEG: check points per factor
+  int seg_J = 0;                      // HINGE_SDF_*_SEG: check points per factor; HINGE_HALFSPACE: rows per factor
   bool fused_pair = false;            // last resident launch went out fused with the other set
-  bool closed_form = false;           // no sigma points: NGDFactorizedLinear route (sum-of-squares kinds), box_moments.hpp (HINGE_BOX, its default)
+  bool closed_form = false;           // no sigma points: NGDFactorizedLinear route (sum-of-squares kinds), box_moments.hpp (HINGE_BOX, its default), halfspace_moments.hpp (HINGE_HALFSPACE, its default)
   bool chain_structured = false;      // start[k] == k (factor k on state k / states k, k + 1): assemble-on-load needs no CSR
   bool all_pos = false;               // every residual row has sgn = +1 (positive-definite weight)
   double jtol = 1e-34;                // ctx->jacobi_tol
@@ -920,8 +920,9 @@ struct MomPlan {
   OrbitArgs oa;              // Orbit
   int smax = 0;              // Orbit: the table's largest support (instance key beside m)
   OrbitPsiArgs pa;           // OrbitPsi
-  size_t lds = 0;            // Orbit, OrbitPsi, Generic, Closed (HINGE_BOX): dynamic LDS
+  size_t lds = 0;            // Orbit, OrbitPsi, Generic, Closed (HINGE_BOX, HINGE_HALFSPACE): dynamic LDS
   bool pipe = false;         // Sreg: the hand-pipelined body
+  int block = 64;            // Closed (HINGE_HALFSPACE): lanes per block, 64 or 256
 };
 // lane-per-point register kernels: a block's four waves take four factors, grid ((K + 3) / 4, nchunk) but for Scost's own launch
 bool lane_per_point(const MomPlan& p) { return p.route == Route::Sreg || p.route == Route::Scost || p.route == Route::Reg; }
@@ -990,6 +991,17 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
       p.lds = box_closed_lds_doubles(s.d) * 8;
       if (p.lds > 64 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_BOX kernel LDS budget (d <= 89)");
     }
+    if (s.kind == KIND_HINGE_HALFSPACE) {
+      if (s.d > 32) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_HALFSPACE kernel supports d <= 32");
+      // a wave holds G = 64 / Jp factors.  One wave per block while the launch has no more waves than the chip has SIMDs
+      // (256 CUs x 4): every wave can start at once wherever its block lands; above that four waves per block, a quarter
+      // of the workgroups to dispatch
+      const int64_t nwaves = (s.K + 64 / halfspace_group(s.seg_J) - 1) / (64 / halfspace_group(s.seg_J));
+      const int wpb = nwaves <= 1024 ? 1 : 4;
+      p.block = 64 * wpb;
+      p.grid = dim3((unsigned)((nwaves + wpb - 1) / wpb));
+      p.lds = (size_t)wpb * halfspace_closed_lds_doubles(s.d) * 8;
+    }
   } else if (orbit) {
     p.route = Route::Orbit;
     GVICK(orbit_args(c, s, &p.oa));
@@ -1038,6 +1050,10 @@ gvi_status launch_plan(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t s
       return GVI_OK;
     case Route::Closed:
       if (s.kind == KIND_HINGE_BOX) hipLaunchKernelGGL(moments_box_closed_kernel, p.grid, dim3(64), p.lds, st, a);
+      else if (s.kind == KIND_HINGE_HALFSPACE) {
+        if (p.lds > 64 * 1024) GVICK(allow_lds(c, (const void*)moments_halfspace_closed_kernel, (int)p.lds));
+        hipLaunchKernelGGL(moments_halfspace_closed_kernel, p.grid, dim3(p.block), p.lds, st, a);
+      }
       else hipLaunchKernelGGL(moments_closed_kernel, p.grid, dim3(64), 0, st, a);
       break;
     case Route::Orbit:
@@ -1478,6 +1494,15 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
       if (params_per_factor != 4 * (int64_t)d) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX needs params_per_factor = 4 d: [sigma | eps | lo | hi]");
       need = params_per_factor;
       break;
+    case GVI_PSI_HINGE_HALFSPACE: {
+      // J is a property of the set: params_per_factor = J (d + 3), exactly
+      const int64_t per = (int64_t)d + 3;
+      if (params_per_factor < per || params_per_factor % per != 0 || params_per_factor / per > HALFSPACE_MAX_J)
+        return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE needs params_per_factor = J (d + 3) with 1 <= J <= 16 rows: [sigma (J) | eps (J) | b (J) | A (J x d)]");
+      seg_J = (int)(params_per_factor / per);
+      need = params_per_factor;
+      break;
+    }
     default: return fail(ctx, GVI_ERR_ARG, "unknown psi kind");
   }
   if (need > 0 && (!psi_params || params_per_factor < need))
@@ -1494,6 +1519,26 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
       }
     }
   }
+  if (psi_kind == GVI_PSI_HINGE_HALFSPACE) {
+    const int J = seg_J;
+    for (int64_t k = 0; k < K; ++k) {
+      const double* P = psi_params + k * params_per_factor;
+      for (int64_t e = 0; e < params_per_factor; ++e)
+        if (std::isnan(P[e])) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: NaN in the parameter block");
+      for (int j = 0; j < J; ++j) {
+        if (!std::isfinite(P[j]) || P[j] < 0.0) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: sigma must be finite and >= 0");
+        if (!std::isfinite(P[J + j])) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: eps must be finite");
+        if (!std::isfinite(P[2 * J + j])) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: b must be finite");
+        bool zero = true;
+        for (int i = 0; i < d; ++i) {
+          const double v = P[3 * J + (int64_t)j * d + i];
+          if (!std::isfinite(v)) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: A must be finite");
+          zero = zero && v == 0.0;
+        }
+        if (zero && P[j] > 0.0) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: an active row (sigma > 0) needs a non-zero normal a_j");
+      }
+    }
+  }
   HIPCK(ctx, hipSetDevice(ctx->device));
 
   std::unique_ptr<FactorSet> s(new FactorSet);
@@ -1501,7 +1546,7 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   s->use_chol = ctx->chol_sqrt;
   s->unit_temperature = ctx->update_rule == GVI_RULE_PROX_JKO;    // the rule belongs to the context: a set takes it when it is added
   s->K = K; s->d = d; s->p = p; s->m = m; s->kind = psi_kind; s->seg_J = seg_J;
-  s->closed_form = psi_kind == GVI_PSI_HINGE_BOX;      // exact and cheaper than any rule on the kink; gvi_factors_set_closed_form(.., 0) for the quadrature
+  s->closed_form = psi_kind == GVI_PSI_HINGE_BOX || psi_kind == GVI_PSI_HINGE_HALFSPACE;      // exact and cheaper than any rule on the kink; gvi_factors_set_closed_form(.., 0) for the quadrature
   if (K > 0) s->start.assign(start, start + K);
   // quadrature table: shared between sets with the same (d, p)
   if (tabZ) {
@@ -1559,8 +1604,8 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   GVICK(up(s->b, b.data(), b.size() * 8));
   GVICK(up(s->sgn, sg.data(), sg.size() * 8));
   s->all_pos = std::all_of(sg.begin(), sg.end(), [](double v) { return v == 1.0; });
-  const bool raw_kind = psi_kind == GVI_PSI_RANGE_1D || sdf_kind(psi_kind) || psi_kind == GVI_PSI_HINGE_BOX;
-  if (raw_kind) {                       // raw_stride = the kind's own block (_SEG kinds: 3 + J P (d + 1), HINGE_BOX: 4 d)
+  const bool raw_kind = psi_kind == GVI_PSI_RANGE_1D || sdf_kind(psi_kind) || psi_kind == GVI_PSI_HINGE_BOX || psi_kind == GVI_PSI_HINGE_HALFSPACE;
+  if (raw_kind) {                       // raw_stride = the kind's own block (_SEG kinds: 3 + J P (d + 1), HINGE_BOX: 4 d, HINGE_HALFSPACE: J (d + 3))
     const int np = (int)need;
     std::vector<double> raw((size_t)K * np);
     for (int k = 0; k < K; ++k) memcpy(&raw[(size_t)k * np], psi_params + (size_t)k * params_per_factor, (size_t)np * 8);
@@ -1706,8 +1751,8 @@ gvi_status gvi_factors_set_arm(gvi_ctx* ctx, int set_id, int ndof, const double*
 gvi_status gvi_factors_set_closed_form(gvi_ctx* ctx, int set_id, int on) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  if (on && s->kind != KIND_QUAD_PRIOR && s->kind != KIND_FIXED_PRIOR && s->kind != KIND_HINGE_BOX)
-    return fail(ctx, GVI_ERR_ARG, "closed form exists for QUAD_PRIOR / FIXED_PRIOR / HINGE_BOX sets only");
+  if (on && s->kind != KIND_QUAD_PRIOR && s->kind != KIND_FIXED_PRIOR && s->kind != KIND_HINGE_BOX && s->kind != KIND_HINGE_HALFSPACE)
+    return fail(ctx, GVI_ERR_ARG, "closed form exists for QUAD_PRIOR / FIXED_PRIOR / HINGE_BOX / HINGE_HALFSPACE sets only");
   GVICK(sync(ctx));
   s->closed_form = on != 0;
   ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;

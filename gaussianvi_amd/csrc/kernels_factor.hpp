@@ -14,6 +14,7 @@
 //                      generic           any d <= 32, any psi kind, host psi
 //                      closed            quadrature-free moments of a quadratic psi (NGDFactorizedLinear)
 //                      box_closed        quadrature-free moments of the separable squared hinge of HINGE_BOX
+//                      halfspace_closed  quadrature-free moments of the row hinges of HINGE_HALFSPACE, several factors per wave
 //   cost_tail_kernel per-factor cost + ordered sum + publish for a cost pass, one launch
 //   jko_*            factor-level proximal (JKO) map around the prep kernel's Jacobi
 //   epilogue_kernel  ordered sum of the chunk partials, back-transform to x-space, Vdmu_k / Vddmu_k
@@ -35,14 +36,16 @@
 
 #include "box_moments.hpp"
 #include "device_common.hpp"
+#include "halfspace_moments.hpp"
 
 namespace gvi {
 
 enum { KIND_RANGE_1D = 0, KIND_QUAD_PRIOR = 1, KIND_FIXED_PRIOR = 2, KIND_HOST_CALLBACK = 3, KIND_HINGE_SDF_2D = 4,
        KIND_HINGE_SDF_2D_BODY = 5, KIND_HINGE_SDF_3D = 6, KIND_HINGE_SDF_3D_ARM = 7, KIND_HINGE_SDF_2D_SEG = 8,
-       KIND_HINGE_SDF_3D_SEG = 9, KIND_HINGE_BOX = 10 };
+       KIND_HINGE_SDF_3D_SEG = 9, KIND_HINGE_BOX = 10, KIND_HINGE_HALFSPACE = 11 };
 
 constexpr int SEG_MAX_J = 8;   // check points of one HINGE_SDF_*_SEG factor
+constexpr int HALFSPACE_MAX_J = 16;   // rows of one HINGE_HALFSPACE factor
 
 __host__ __device__ inline int npairs(int d) { return (d + 1) * (d + 2) / 2; }
 
@@ -69,7 +72,7 @@ struct FactorDev {
   const double* A;          // [K][m][d]   sum-of-squares kinds
   const double* b;          // [K][m]
   const double* sgn;        // [K][m]
-  const double* raw;        // [K][raw_stride] raw parameter block (RANGE_1D, HINGE_SDF_*, HINGE_BOX)
+  const double* raw;        // [K][raw_stride] raw parameter block (RANGE_1D, HINGE_SDF_*, HINGE_BOX, HINGE_HALFSPACE)
   int raw_stride;
   const double* temperature;  // [K]
   // per-pass products of prep_kernel
@@ -92,7 +95,7 @@ struct FactorDev {
   int chol;
   double* Vws;              // [K][d][d] eigenvectors of the previous prep (warm start) or null
   int warm;                 // 1: start the Jacobi sweeps from Vws (resident NGD iteration only)
-  int seg_J;                // HINGE_SDF_*_SEG: check points per factor (1 .. SEG_MAX_J), else 0
+  int seg_J;                // HINGE_SDF_*_SEG: check points per factor (1 .. SEG_MAX_J); HINGE_HALFSPACE: rows per factor (1 .. HALFSPACE_MAX_J); else 0
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -950,7 +953,7 @@ __device__ inline double psi_hinge_sdf3d_seg(const FactorDev& f, const double* p
   return cost;
 }
 
-// psi and / or clearance of factor k of a hinge-on-SDF or HINGE_BOX set at the state slice x [d].  psi is the kind's
+// psi and / or clearance of factor k of a hinge-on-SDF, HINGE_BOX or HINGE_HALFSPACE set at the state slice x [d].  psi is the kind's
 // psi_* function; the clearance walks the same *_points with a min-visitor.  eps and slope play no part in the clearance.
 __device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, const double* x, bool want_psi, bool want_clr,
                                                     double& psi, double& clr) {
@@ -978,6 +981,9 @@ __device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, c
   } else if (f.kind == KIND_HINGE_BOX) {      // limits on the slice itself (box_moments.hpp): the clearance is the margin
     if (want_psi) psi = psi_hinge_box(p, x, f.d);
     if (want_clr) c = box_margin(p, x, f.d);
+  } else if (f.kind == KIND_HINGE_HALFSPACE) {      // rows a_j^T x <= b_j (halfspace_moments.hpp): distance to the nearest active face
+    if (want_psi) psi = psi_hinge_halfspace(p, x, f.d, f.seg_J);
+    if (want_clr) c = halfspace_margin(p, x, f.d, f.seg_J);
   } else {                      // no clearance for this kind: the host refuses such a set before any launch
     if (want_psi) psi = __builtin_nan("");
     c = __builtin_nan("");
@@ -1105,6 +1111,74 @@ __global__ __launch_bounds__(64) void moments_box_closed_kernel(MomArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// moments_halfspace_closed_kernel: quadrature-free moments of the HINGE_HALFSPACE psi (halfspace_moments.hpp; DESIGN.md section
+// 16).  psi is a sum over rows of a squared hinge of the scalar a_j^T x, so with v_j = S^T a_j and (e0, e1, e2)_j of halfspace_row
+//   E[psi] = sum_j e0_j,   E[z psi] = sum_j v_j e1_j,   E[z z^T psi] = E[psi] I + sum_j v_j v_j^T e2_j
+// for any root S S^T = Sigma, S row-major as prep writes it.  The same packed one-chunk layout as moments_closed_kernel, so the
+// epilogue is shared.
+// Lanes are (factor, row) pairs: with Jp = J rounded up to a power of two a wave holds G = 64 / Jp factors, lane = g Jp + j;
+// wave w of the launch takes factors w G .. w G + G - 1.  A block is 1 or 4 such waves (blockDim.x / 64), each on its own slice
+// of the dynamic LDS and without a workgroup barrier: no wave reads what another wrote.
+//   phase 1: lane (g, j) forms v_j entry by entry into the wave's slice (Vs[c * 64 + lane]: consecutive lanes, consecutive
+//            banks; no d-long register array) and takes its box_side; (e1, e2) go to LDS, e0 stays in a register.  A lane of an
+//            off row, of a padding row j >= J or of a factor >= K writes nothing and carries zeros.
+//   phase 2: the Jp lanes of a group stride over the npairs(d) outputs of their factor; each output is a sum over the ACTIVE rows
+//            in ascending j (the ballot of phase 1 says which: an off row's slice was never written), m0 is the ascending-j sum
+//            of the e0 registers through shuffles.  No atomics, no tree whose shape depends on the launch: the same bits from
+//            run to run.
+// LDS: 64 d + 128 doubles per wave.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ inline int halfspace_group(int J) { int P = 1; while (P < J) P <<= 1; return P; }
+__host__ __device__ inline size_t halfspace_closed_lds_doubles(int d) { return 64 * (size_t)d + 128; }
+
+__global__ __launch_bounds__(256) void moments_halfspace_closed_kernel(MomArgs a) {
+  if (pred_skip(a.pred, a.pred_val)) return;
+  extern __shared__ double hsm[];
+  const FactorDev& f = a.f;
+  const int d = f.d, J = f.seg_J, Jp = halfspace_group(J), G = 64 / Jp;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane / Jp, j = lane % Jp, gbase = g * Jp;
+  const int64_t kw = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * G + g;
+  const bool live = kw < f.K;
+  const int k = live ? (int)kw : 0;
+  double* Vs = hsm + (size_t)wave * halfspace_closed_lds_doubles(d);      // [d][64]
+  double* e1s = Vs + 64 * d;                                             // [64]
+  double* e2s = e1s + 64;                                                // [64]
+  const double* p = f.raw + (size_t)k * f.raw_stride;
+  const bool act = live && j < J && p[j] > 0.0;
+  BoxSide r = {0.0, 0.0, 0.0};
+  if (act) r = halfspace_row(p, d, J, j, a.mu + (size_t)k * d, f.S + (size_t)k * d * d, Vs + lane, 64);
+  e1s[lane] = r.e1;
+  e2s[lane] = r.e2;
+  const unsigned long long on = __ballot(act);
+  double m0 = 0.0;
+  for (int jj = 0; jj < J; ++jj) m0 += __shfl(r.e0, gbase + jj);          // ascending j; an off row carries 0
+  wave_lds_sync();
+  if (!live) return;
+  const int npo = a.full ? npairs(d) : 1;
+  double* out = a.partial + (size_t)k * a.nchunk * npo;
+  if (j == 0) out[0] = m0;
+  if (!a.full) return;
+  for (int o = 1 + j; o < npo; o += Jp) {
+    double v = 0.0;
+    if (o <= d) {
+      const double* vc = Vs + (o - 1) * 64 + gbase;
+      for (int jj = 0; jj < J; ++jj)
+        if ((on >> (gbase + jj)) & 1ull) v = fma(vc[jj], e1s[gbase + jj], v);
+    } else {
+      int rem = o - 1 - d, row = 0;
+      while (rem >= d - row) { rem -= d - row; ++row; }
+      const double* vr = Vs + row * 64 + gbase;
+      const double* vc = Vs + (row + rem) * 64 + gbase;
+      for (int jj = 0; jj < J; ++jj)
+        if ((on >> (gbase + jj)) & 1ull) v = fma(vr[jj] * vc[jj], e2s[gbase + jj], v);
+      if (rem == 0) v += m0;
+    }
+    out[o] = v;
+  }
+}
+
 constexpr int GEN_BS = 256;
 constexpr int GEN_MAX_OUT = 3;   // outputs per thread: npairs(d) <= 768 -> d <= 37
 
@@ -1174,6 +1248,7 @@ __global__ __launch_bounds__(GEN_BS) void moments_generic_kernel(MomArgs a) {
       else if (f.kind == KIND_HINGE_SDF_2D_SEG) psi = psi_hinge_sdf2d_seg(f, f.raw + (size_t)k * f.raw_stride, xr, d);
       else if (f.kind == KIND_HINGE_SDF_3D_SEG) psi = psi_hinge_sdf3d_seg(f, f.raw + (size_t)k * f.raw_stride, xr, d);
       else if (f.kind == KIND_HINGE_BOX) psi = psi_hinge_box(f.raw + (size_t)k * f.raw_stride, xr, d);
+      else if (f.kind == KIND_HINGE_HALFSPACE) psi = psi_hinge_halfspace(f.raw + (size_t)k * f.raw_stride, xr, d, f.seg_J);
       else {
         for (int r = 0; r < m; ++r) {
           double u = bsh[r];

@@ -11,12 +11,13 @@ static const char MSG_NMAX[] = "state_dim > 16";
 static_assert(SAMPLE_NMAX == 16 && SOLVE_NMAX == 16 && INTERP_NMAX == 16, "one state_dim rule for every query");
 
 // ---- the check order ----
-// kinds with a clearance: the hinge-on-SDF kinds (sdf_kind: they need a grid) and HINGE_BOX, whose clearance is the margin to its limits
-static bool clearance_kind(int kind) { return sdf_kind(kind) || kind == KIND_HINGE_BOX; }
+// kinds with a clearance: the hinge-on-SDF kinds (sdf_kind: they need a grid), HINGE_BOX, whose clearance is the margin to its limits,
+// and HINGE_HALFSPACE, whose clearance is the distance to the nearest active face
+static bool clearance_kind(int kind) { return sdf_kind(kind) || kind == KIND_HINGE_BOX || kind == KIND_HINGE_HALFSPACE; }
 
 static gvi_status scost_check_set(gvi_ctx* ctx, const FactorSet& s, bool clearance) {
   if (s.kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_UNSUPPORTED, "a PSI_HOST_CALLBACK set has no device psi");
-  if (clearance && !clearance_kind(s.kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "clearance needs a hinge-on-SDF set");   // text kept for its callers; a HINGE_BOX set passes too
+  if (clearance && !clearance_kind(s.kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "clearance needs a hinge-on-SDF set");   // text kept for its callers; HINGE_BOX and HINGE_HALFSPACE sets pass too
   if (scost_sumsq(s.kind) && s.d > SCOST_DMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
   if (s.kind == KIND_HINGE_SDF_3D_ARM && !s.arm.p)
     return fail(ctx, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");

@@ -9,6 +9,7 @@ the C-ABI works on.  psi parameter blocks use the C-ABI layouts of include/gvi_h
   RANGE_1D    [y, mu_p, f*b, sig_r_sq, sig_p_sq]               d = 1    (src/1d_example.cpp:25-35)
   HINGE_SDF_2D_SEG / _3D_SEG  [sigma, eps, r | W_0 (P x d) | c_0 (P) | ... ]   d = n or 2n   (segment_params)
   HINGE_BOX   [sigma (d) | eps (d) | lo (d) | hi (d)]          d = n or 2n   (box_params)
+  HINGE_HALFSPACE  [sigma (J) | eps (J) | b (J) | A (J x d)]   d = n or 2n   (halfspace_params)
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ PSI_RANGE_1D, PSI_QUAD_PRIOR, PSI_FIXED_PRIOR, PSI_HOST_CALLBACK, PSI_HINGE_SDF_
 PSI_HINGE_SDF_2D_BODY, PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM = 5, 6, 7
 PSI_HINGE_SDF_2D_SEG, PSI_HINGE_SDF_3D_SEG = 8, 9
 PSI_HINGE_BOX = 10
+PSI_HINGE_HALFSPACE = 11
 
 CONFIGS = {
     # name: (cfg#, T, n, p, prior kind)
@@ -141,6 +143,69 @@ def add_box_set(chain, lo, hi, sigma=10.0, eps=0.05, p=3, pair=False, temperatur
     K, d = (T - 1, 2 * n) if pair else (T, n)
     lo, hi = np.broadcast_to(np.asarray(lo, dtype=np.float64), (d,)), np.broadcast_to(np.asarray(hi, dtype=np.float64), (d,))
     spec = dict(kind=PSI_HINGE_BOX, d=d, p=p, start=np.arange(K, dtype=np.int32), params=np.tile(box_params(sigma, eps, lo, hi), (K, 1)),
+                temperature=np.full(K, float(temperature)))
+    return dict(chain, specs=list(chain["specs"]) + [spec])
+
+
+def halfspace_params(sigma, eps, b, A, J=None):
+    """Parameter blocks [K][J (d + 3)] of a HINGE_HALFSPACE set: [sigma (J) | eps (J) | b (J) | A (J x d, row-major)], rows
+    a_j^T x <= b_j.  A is [J][d] (shared by the set), [K][J][d], or a list of K arrays [J_k][d] with their own row counts;
+    sigma, eps, b are scalars, [J], [K][J] or, beside a list A, lists of [J_k].  Every factor is padded to J rows (default:
+    the largest row count) with rows that are off: sigma = 0, eps = b = 0, a = 0."""
+    ragged = isinstance(A, (list, tuple)) and all(np.ndim(a) == 2 for a in A)
+    if ragged:
+        blocks = [np.asarray(a, dtype=np.float64) for a in A]
+        K = len(blocks)
+
+        def per(v, k):
+            v = v[k] if isinstance(v, (list, tuple)) else v
+            return np.broadcast_to(np.asarray(v, dtype=np.float64), (blocks[k].shape[0],))
+        rows = [[per(v, k) for k in range(K)] for v in (sigma, eps, b)]
+    else:
+        A = np.asarray(A, dtype=np.float64)
+        assert A.ndim in (2, 3), "A is [J][d] or [K][J][d]"
+        parts = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (sigma, eps, b)]
+        K = max([v.shape[0] for v in parts if v.ndim == 2] + [A.shape[0] if A.ndim == 3 else 1])
+        blocks = list(np.broadcast_to(A, (K,) + A.shape[-2:]))
+        rows = [list(np.broadcast_to(v, (K, A.shape[-2]))) for v in parts]
+    d = blocks[0].shape[1]
+    Jmax = max(a.shape[0] for a in blocks)
+    J = Jmax if J is None else int(J)
+    assert J >= Jmax and all(a.shape[1] == d for a in blocks), "J below a factor's row count, or rows of different dimension"
+    out = np.zeros((K, J * (d + 3)))
+    for k in range(K):
+        Jk = blocks[k].shape[0]
+        for slot in range(3):
+            out[k, slot * J:slot * J + Jk] = rows[slot][k]
+        out[k, 3 * J:3 * J + Jk * d] = blocks[k].reshape(-1)
+    return out
+
+
+def add_corridor_set(chain, normals, offsets, sigma=10.0, eps=0.05, p=3, pair=False, taus=None, dt=0.25, qc=QC, temperature=1.0):
+    """A copy of `chain` (the arrays are shared) with a HINGE_HALFSPACE set appended behind its sets: a convex corridor
+    n_j^T pos <= b_j on the first npos coordinates (the position) of the state, normals [Jn][npos] and offsets [Jn] shared by
+    the set, or [K][Jn][npos] and [K][Jn] with one polygon per factor.
+    pair = False: one factor per state (K = T, d = n), rows [n_j | 0].
+    pair = True: one factor per pair of neighbouring states (K = T - 1, d = 2n) that holds the corridor at the times taus
+    (default: the midpoint dt / 2) INSIDE the segment: the position there is W(tau) [x_i | x_i+1] + c(tau) (minacc_segment_readout
+    for the chain's constant-velocity prior with step dt and spectral density qc), so the rows are W(tau)^T n_j with offsets
+    b_j - n_j^T c(tau): J = len(taus) Jn rows, tau-major."""
+    T, n = chain["T"], chain["n"]
+    K, d = (T - 1, 2 * n) if pair else (T, n)
+    normals, offsets = np.asarray(normals, dtype=np.float64), np.asarray(offsets, dtype=np.float64)
+    Jn, npos = normals.shape[-2:]
+    N = np.broadcast_to(normals, (K, Jn, npos))
+    B = np.broadcast_to(offsets, (K, Jn))
+    if pair:
+        taus = [0.5 * dt] if taus is None else list(taus)
+        W, c = minacc_segment_readout(n // 2, qc, dt, taus, npos)                 # [L][npos][2n], [L][npos]
+        A = np.einsum("kjp,lpe->klje", N, W).reshape(K, len(taus) * Jn, d)
+        b = (B[:, None, :] - np.einsum("kjp,lp->klj", N, c)).reshape(K, len(taus) * Jn)
+    else:
+        A = np.zeros((K, Jn, d))
+        A[:, :, :npos] = N
+        b = B
+    spec = dict(kind=PSI_HINGE_HALFSPACE, d=d, p=p, start=np.arange(K, dtype=np.int32), params=halfspace_params(sigma, eps, b, A),
                 temperature=np.full(K, float(temperature)))
     return dict(chain, specs=list(chain["specs"]) + [spec])
 

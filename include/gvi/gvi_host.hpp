@@ -367,9 +367,37 @@ struct DevicePsi {
     }
     return p;
   }
-  // a set is homogeneous in its block size too: segment factors with different J stay apart
+  // Half-spaces on the factor's slice (GVI_PSI_HINGE_HALFSPACE; no reference counterpart): rows a_j^T x <= b_j of A (J x d,
+  // 1 <= J <= GVI_HALFSPACE_MAX_J), a squared hinge per row, sigma_j max(0, a_j^T x - (b_j - eps_j))^2 -- a convex corridor
+  // polygon around a state, a keep-out half-plane, a coupled limit such as |v_x| + |v_y| <= v, a terminal set; on a binary factor
+  // with rows W^T n_j, a corridor on the interpolated position between two states (MinimumAccGP::segment_readout).  A row with
+  // sigma_j = 0 is off (its a_j may be zero): factors with fewer rows pad to the J of their set this way.  Needs no field.
+  // Evaluated in closed form on the device (no sigma points); sample_clearance of such a set returns the distance to the nearest
+  // active face, min_j (b_j - a_j^T x) / |a_j|.
+  static DevicePsi hinge_halfspace(const MatrixXd& A, const VectorXd& b, const VectorXd& sigma, const VectorXd& eps) {
+    const int J = (int)A.rows(), d = (int)A.cols();
+    if (J < 1 || J > (int)GVI_HALFSPACE_MAX_J || d < 1 || b.size() != J || sigma.size() != J || eps.size() != J)
+      throw std::invalid_argument("half-space factor: A is J x d with 1 <= J <= GVI_HALFSPACE_MAX_J (16) rows; b, sigma and eps have J entries");
+    DevicePsi p{GVI_PSI_HINGE_HALFSPACE, {}};
+    for (const VectorXd* v : {&sigma, &eps, &b})
+      for (int j = 0; j < J; ++j) p.params.push_back((*v)(j));
+    for (int j = 0; j < J; ++j) {
+      if (!std::isfinite(sigma(j)) || sigma(j) < 0.0) throw std::invalid_argument("half-space factor: sigma must be finite and >= 0");
+      if (!std::isfinite(eps(j))) throw std::invalid_argument("half-space factor: eps must be finite");
+      if (!std::isfinite(b(j))) throw std::invalid_argument("half-space factor: b must be finite");
+      bool zero = true;
+      for (int i = 0; i < d; ++i) {
+        if (!std::isfinite(A(j, i))) throw std::invalid_argument("half-space factor: A must be finite");
+        zero = zero && A(j, i) == 0.0;
+        p.params.push_back(A(j, i));
+      }
+      if (zero && sigma(j) > 0.0) throw std::invalid_argument("half-space factor: an active row (sigma > 0) needs a non-zero normal");
+    }
+    return p;
+  }
+  // a set is homogeneous in its block size too: segment factors, and half-space factors, with different J stay apart
   bool same_group(const DevicePsi& o) const {
-    const bool seg = kind == GVI_PSI_HINGE_SDF_2D_SEG || kind == GVI_PSI_HINGE_SDF_3D_SEG;
+    const bool seg = kind == GVI_PSI_HINGE_SDF_2D_SEG || kind == GVI_PSI_HINGE_SDF_3D_SEG || kind == GVI_PSI_HINGE_HALFSPACE;
     return kind == o.kind && sdf2d == o.sdf2d && sdf3d == o.sdf3d && arm == o.arm && (!seg || params.size() == o.params.size());
   }
   // [sigma, epsilon, radius | W_0 (P x d, row-major) | c_0 (P) | ...]: the kinds' parameter block (DevicePsi stays an aggregate)
@@ -1642,7 +1670,7 @@ class GVIGH {
     return M;
   }
   // Minimum over the factors of set `factor_set` (the sets are formed in the order their first factor was given: factors
-  // of the same dimension, degree and psi group share one; hinge-on-SDF kinds and limit factors only) of sdf(p_b) - r_b (limit factors: of the margin to the limits) at sample j of stream `seed`: negative where the sampled trajectory touches an obstacle.
+  // of the same dimension, degree and psi group share one; hinge-on-SDF kinds, limit and half-space factors only) of sdf(p_b) - r_b (limit and half-space factors: of the margin to the limits / faces) at sample j of stream `seed`: negative where the sampled trajectory touches an obstacle.
   VectorXd sample_clearance(int n_samples, uint64_t seed, int factor_set) {
     if (n_samples < 0) throw GviError(GVI_ERR_ARG, "n_samples < 0");
     if (factor_set < 0 || factor_set >= (int)_sets.size()) throw GviError(GVI_ERR_ARG, "sample_clearance: no such factor set");

@@ -81,12 +81,30 @@ enum { GVI_F64 = 0, GVI_F32 = 1 };
  *       forms in Phi and phi of the 1-D marginals, and the set is created in CLOSED FORM (no sigma points; DESIGN.md section
  *       15); gvi_factors_set_closed_form(set, 0) selects the Gauss-Hermite quadrature of the same psi, (set, 1) returns.
  *       margin(x) = min_i min(hi_i - x_i, x_i - lo_i) is what the clearance calls return for such a set
+ *   GVI_PSI_HINGE_HALFSPACE                                                any d >= 1 (no reference counterpart)
+ *       [sigma (J) | eps (J) | b (J) | A (J x d, row-major)], params_per_factor = J (d + 3) exactly
+ *       psi(x) = sum_j sigma_j max(0, a_j^T x - (b_j - eps_j))^2: J half-spaces a_j^T x <= b_j on the factor's slice, a squared
+ *       hinge per row that starts eps_j inside the face -- a convex corridor polygon or polytope per state, a keep-out
+ *       half-plane, a coupled limit such as |v_x| + |v_y| <= v (four rows), a terminal set, or, on a binary factor, a corridor
+ *       on a linear read-out of the pair (the GP-interpolated position between two support states).
+ *       J is a property of the set: J = params_per_factor / (d + 3); the division must be exact and 1 <= J <= 16
+ *       (GVI_HALFSPACE_MAX_J), else GVI_ERR_ARG.  A row with sigma_j = 0 is OFF: it adds nothing, is skipped in the margin and its
+ *       a_j may be zero, so factors with fewer rows pad to the J of their set.
+ *       GVI_ERR_ARG: a NaN anywhere, sigma_j < 0 or not finite, eps_j, b_j or an entry of A not finite, an all-zero a_j on a row
+ *       with sigma_j > 0.  Needs no grid and no arm model (those setters refuse it).  The scalar a_j^T x of a Gaussian x is a 1-D
+ *       Gaussian, so the moments of psi are exact closed forms in Phi and phi, and the set is created in CLOSED FORM (no sigma
+ *       points; factor dimension d <= 32, above that the passes return GVI_ERR_UNSUPPORTED);
+ *       gvi_factors_set_closed_form(set, 0) selects the Gauss-Hermite quadrature of the same psi, (set, 1) returns.
+ *       margin(x) = min over the rows with sigma_j > 0 of (b_j - a_j^T x) / |a_j|, the signed Euclidean distance to the nearest
+ *       active face (+inf when every row is off; eps plays no part), is what the clearance calls return for such a set
  *   GVI_PSI_HOST_CALLBACK no parameters: psi is an opaque host function (the reference's
  *       std::function, ngd/NGDFactorizedBaseGH.h:30,46-48); use gvi_expand + gvi_moments_from_psi. */
 enum { GVI_PSI_RANGE_1D = 0, GVI_PSI_QUAD_PRIOR = 1, GVI_PSI_FIXED_PRIOR = 2, GVI_PSI_HOST_CALLBACK = 3,
        GVI_PSI_HINGE_SDF_2D = 4, GVI_PSI_HINGE_SDF_2D_BODY = 5, GVI_PSI_HINGE_SDF_3D = 6, GVI_PSI_HINGE_SDF_3D_ARM = 7,
-       GVI_PSI_HINGE_SDF_2D_SEG = 8, GVI_PSI_HINGE_SDF_3D_SEG = 9, GVI_PSI_HINGE_BOX = 10 };
+       GVI_PSI_HINGE_SDF_2D_SEG = 8, GVI_PSI_HINGE_SDF_3D_SEG = 9, GVI_PSI_HINGE_BOX = 10,
+       GVI_PSI_HINGE_HALFSPACE = 11 };
 enum { GVI_SEG_MAX_J = 8 };   /* check points of one HINGE_SDF_*_SEG factor */
+enum { GVI_HALFSPACE_MAX_J = 16 };   /* rows of one HINGE_HALFSPACE factor */
 
 const char* gvi_version(void);
 /* Message of the last failing call on this context (never NULL). */
@@ -163,8 +181,8 @@ gvi_status gvi_factors_set_arm(gvi_ctx* ctx, int set_id, int ndof, const double*
  * classify_factors sends to its linear branch (gvibase/GVI-GH-Cuda-impl.h:31-38).  No sigma points are
  * evaluated; the Gaussian 4th-moment contraction (its O(d^4) loop, :108-118) is done in the whitened
  * space where it collapses to (u0^2 + |h|^2) I + 2 h h^T per residual row.  on = 0 returns to quadrature.
- * A GVI_PSI_HINGE_BOX set has a closed form of its own and starts with it on (see the kind).  on = 1 for any other kind:
- * GVI_ERR_ARG. */
+ * A GVI_PSI_HINGE_BOX or GVI_PSI_HINGE_HALFSPACE set has a closed form of its own and starts with it on (see the kinds): Phi and
+ * phi of the 1-D marginals (HINGE_BOX) or of the rows' scalars a_j^T x (HINGE_HALFSPACE).  on = 1 for any other kind: GVI_ERR_ARG. */
 gvi_status gvi_factors_set_closed_form(gvi_ctx* ctx, int set_id, int on);
 /* factor_switch_to_high_temperature (gvibase/GVIFactorizedBase.h:212-214), batched. */
 gvi_status gvi_factors_set_temperature(gvi_ctx* ctx, int set_id, const double* temperature);
@@ -431,7 +449,8 @@ gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_
  *      The CLEARANCE of a hinge-on-SDF factor is min_b sdf(p_b) - r_b over the factor's check points b -- the points of its
  *      psi, in the same arithmetic: the one ball of HINGE_SDF_2D / _3D, the n_balls body points of _2D_BODY, the first
  *      min(d, nspheres) spheres with their own radii of _3D_ARM, the J read-outs W_j x + c_j of _2D_SEG / _3D_SEG.  epsilon and slope play no part in it.
- *      For a HINGE_BOX set the clearance is margin(x) = min_i min(hi_i - x_i, x_i - lo_i), +inf when no limit is finite.  It is the continuous
+ *      For a HINGE_BOX set the clearance is margin(x) = min_i min(hi_i - x_i, x_i - lo_i), +inf when no limit is finite; for a
+ *      HINGE_HALFSPACE set min_j (b_j - a_j^T x) / |a_j| over the rows with sigma_j > 0, +inf when every row is off.  It is the continuous
  *      quantity; the library returns no collided / not-collided indicator.
  *      S = 0 is a no-op; S < 0, a required NULL buffer, first < 0 or a set id outside the context's sets: GVI_ERR_ARG; before
  *      gvi_chain_set (gvi_ngd_*: before gvi_ngd_init): GVI_ERR_STATE, as is a hinge set whose grid (arm model) was never set; a
@@ -447,7 +466,7 @@ gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_
  *      64, ... 1).  The order depends on the sets only. ---- */
 /* cost [S][K] of one set at X [S][T][n]; host buffers, a pure operator. */
 gvi_status gvi_sample_factor_costs(gvi_ctx* ctx, int set_id, int S, const double* X, double* cost);
-/* clr [S][K]: hinge-on-SDF and HINGE_BOX sets only, every other kind: GVI_ERR_UNSUPPORTED.  The _dev twin takes device buffers and is
+/* clr [S][K]: hinge-on-SDF, HINGE_BOX and HINGE_HALFSPACE sets only, every other kind: GVI_ERR_UNSUPPORTED.  The _dev twin takes device buffers and is
  * asynchronous on the context stream. */
 gvi_status gvi_sample_clearance(gvi_ctx* ctx, int set_id, int S, const double* X, double* clr);
 gvi_status gvi_sample_clearance_dev(gvi_ctx* ctx, int set_id, int S, const double* X_dev, double* clr_dev);
