@@ -34,6 +34,7 @@ SIGNATURES = {
     "gvi_debug_asm_launches": [C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "gvi_debug_fused_launches": [C.POINTER(C.c_int64)],
     "gvi_debug_block3_launches": [C.POINTER(C.c_int64)],
+    "gvi_debug_products": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "gvi_factors_set_table": [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p],
     "gvi_factors_set_sdf2d": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p],
     "gvi_table_file_list": [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],

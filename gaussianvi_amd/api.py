@@ -652,6 +652,13 @@ class Context:
         self._ck(self.lib.gvi_debug_cost_log(self.h, entries if entries > 0 else -1, None, C.byref(seq)))
         return seq.value
 
+    def debug_products(self, sid, K, d, m):
+        """gvi_debug_products: (S, Sinv, Lam, H, u0) as the set's last prep launch left them in memory."""
+        S, Sinv, Lam = (np.zeros((K, d, d)) for _ in range(3))
+        H, u0 = np.zeros((K, d, m)), np.zeros((K, m))
+        self._ck(self.lib.gvi_debug_products(self.h, sid, _p(S), _p(Sinv), _p(Lam), _p(H) if m else None, _p(u0) if m else None))
+        return dict(S=S, Sinv=Sinv, Lam=Lam, H=H, u0=u0)
+
     def set_variant(self, v):
         self._ck(self.lib.gvi_set_variant(self.h, v))
 

@@ -235,6 +235,11 @@ struct gvi_ctx {
   // (same moments -- the quadrature is exact there -- without the Jacobi sweeps); GVI_CHOL_SQRT=0 / option "chol_sqrt"
   bool prefer_opsi = false;           // gvi_set_variant(7)
   bool chol_sqrt = true;
+  // GVI_CHOL_ROWB=1 / option "chol_rowb": the register Cholesky of the three-launch route's prep (prep_all_kernel) in its
+  // row-broadcast form (kernels_factor.hpp, prep_chol_body<DT, ROWB>) instead of v_readlane; bit-identical (A/B inside one
+  // library), and slower in that launch (profiles/r06_unit_top.txt §4), hence off.  The fused pass takes the row-broadcast
+  // form unconditionally.
+  bool chol_rowb = false;
   // option "trust_table_degree": a table handed to gvi_factors_add_table IS the Smolyak rule of the degree it is added
   // under (e.g. the generator's own table, produced once and broadcast to the other ranks); it may then take every route
   // the generated table takes (Cholesky factor for sum-of-squares psi).  Default 0: a caller's table keeps the symmetric
@@ -1347,6 +1352,7 @@ gvi_status gvi_ctx_create(int device, int dtype, gvi_ctx** out) {
   if (const char* w = getenv("GVI_ASM_DENSE")) chain_asm_dense_enabled() = atoi(w) != 0;   // (process-wide: A/B leg of the batched first-pass load)
   if (const char* w = getenv("GVI_CHAIN_PAIR")) chain_pair_enabled() = atoi(w) != 0;      // (process-wide: A/B leg of the row-broadcast eliminations)
   if (const char* w = getenv("GVI_CHAIN_MERGE")) c->chain_merge = atoi(w) != 0;
+  if (const char* w = getenv("GVI_CHOL_ROWB")) c->chol_rowb = atoi(w) != 0;
   if (const char* w = getenv("GVI_SREG_PIPE")) c->sreg_pipe = atoi(w) != 0;
   if (const char* w = getenv("GVI_MIRROR")) c->mirror = atoi(w) != 0;
   if (const char* w = getenv("GVI_NO_PAIR")) c->pair_fuse = atoi(w) == 0;
@@ -2073,10 +2079,16 @@ static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
   const size_t lds = (size_t)(4 * dmax * dmax + 2 * dp + 3 * dmax + (dp + 1) / 2 + 1 + dmax * dmax + dmax) * 8 + 16;
   const dim3 grid(L.koff[L.nsets] + extra);
   if (grid.x == 0) return GVI_OK;                                     // only empty shards
-  if (dmax <= 8) hipLaunchKernelGGL(prep_all_kernel<1>, grid, dim3(64), lds, ctx->stream, L);
-  else if (dmax <= 16) hipLaunchKernelGGL(prep_all_kernel<4>, grid, dim3(64), lds, ctx->stream, L);
-  else if (dmax <= 32) hipLaunchKernelGGL(prep_all_kernel<16>, grid, dim3(64), lds, ctx->stream, L);
-  else return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
+  if (dmax > 32) return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
+  if (ctx->chol_rowb) {
+    if (dmax <= 8) hipLaunchKernelGGL((prep_all_kernel<1, true>), grid, dim3(64), lds, ctx->stream, L);
+    else if (dmax <= 16) hipLaunchKernelGGL((prep_all_kernel<4, true>), grid, dim3(64), lds, ctx->stream, L);
+    else hipLaunchKernelGGL((prep_all_kernel<16, true>), grid, dim3(64), lds, ctx->stream, L);
+  } else {
+    if (dmax <= 8) hipLaunchKernelGGL((prep_all_kernel<1, false>), grid, dim3(64), lds, ctx->stream, L);
+    else if (dmax <= 16) hipLaunchKernelGGL((prep_all_kernel<4, false>), grid, dim3(64), lds, ctx->stream, L);
+    else hipLaunchKernelGGL((prep_all_kernel<16, false>), grid, dim3(64), lds, ctx->stream, L);
+  }
   HIPCK(ctx, hipGetLastError());
   return GVI_OK;
 }
@@ -3569,6 +3581,7 @@ gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value) {
     for (int q = 0; q < 16; ++q) ctx->host_slot[q] = 0.0;       // the two forms lay the slot out differently
   }
   else if (n == "chol_sqrt") { ctx->chol_sqrt = value != 0; for (auto& s : ctx->sets) s->use_chol = ctx->chol_sqrt; }
+  else if (n == "chol_rowb") ctx->chol_rowb = value != 0;
   else if (n == "jacobi_tol_exp") {
     // the threshold compares SQUARED off-diagonal mass with squared diagonal mass: anything looser than 1e-20 (1e-10 relative)
     // would break the 1e-9 operator parity, so it is refused rather than silently clamped
@@ -3610,6 +3623,26 @@ gvi_status gvi_debug_cost_log(gvi_ctx* ctx, int entries, double* out, double* se
     HIPCK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(gvi_dbg_log), &lg, sizeof(double*)));
   }
   if (seq_now) *seq_now = ctx->seq;
+  return GVI_OK;
+}
+
+gvi_status gvi_debug_products(gvi_ctx* ctx, int set_id, double* S, double* Sinv, double* Lam, double* H, double* u0) {
+  if (!ctx) return GVI_ERR_ARG;
+  FactorSet* s = get_set(ctx, set_id);
+  if (!s) return GVI_ERR_ARG;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  GVICK(sync(ctx));
+  const size_t dd = (size_t)s->K * s->d * s->d * 8, md = (size_t)s->K * s->m * s->d * 8, mb = (size_t)s->K * s->m * 8;
+  auto get = [&](double* out, const DevMem& src, size_t bytes) {
+    if (!out || bytes == 0) return hipSuccess;
+    if (!src.p || src.bytes < bytes) return hipErrorInvalidValue;
+    return hipMemcpy(out, src.p, bytes, hipMemcpyDeviceToHost);
+  };
+  HIPCK(ctx, get(S, s->S, dd));
+  HIPCK(ctx, get(Sinv, s->Sinv, dd));
+  HIPCK(ctx, get(Lam, s->Lam, dd));
+  HIPCK(ctx, get(H, s->H, md));
+  HIPCK(ctx, get(u0, s->u0, mb));
   return GVI_OK;
 }
 

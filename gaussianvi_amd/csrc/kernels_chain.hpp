@@ -47,6 +47,7 @@
 #include <stdint.h>
 
 #include "device_common.hpp"
+#include "dpp_rowb.hpp"
 #include "kernels_bt.hpp"
 
 namespace gvi {
@@ -325,29 +326,6 @@ __device__ __forceinline__ double readlane64(double v, int src) {
   return u.d;
 }
 
-// ---- 64-bit DPP row broadcast (gfx950: row_newbcast:n is the one DPP control of the 64-bit ALU) ----
-// Every lane reads the operand from lane P of its OWN 16-lane row (tests/test_rowbcast_semantics_gpu.py pins this on the device,
-// also for lanes switched off).  Inline asm gets no hazard handling from the compiler: a vector write of a register needs two
-// wait states before a DPP read of it.  rowb_mov opens with the s_nop that covers them (WS = 4: also the five after a vector
-// write of EXEC, for callers with divergent code in front); rowb_fmac carries none -- its caller keeps every writer of the
-// broadcast operand in front of a rowb_mov (rowb_pin fixes compiler-written values there).
-template <int P, int WS>
-__device__ __forceinline__ double rowb_mov(const double v) {
-  double o;
-  if constexpr (WS > 1) asm volatile("s_nop 4\n\tv_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(o) : "v"(v), "n"(P));
-  else asm volatile("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(o) : "v"(v), "n"(P));
-  return o;
-}
-// c += (c of lane P of the row) * b
-template <int P>
-__device__ __forceinline__ void rowb_fmac(double& c, const double b) {
-  asm volatile("v_fmac_f64_dpp %0, %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "+v"(c) : "v"(b), "n"(P));
-}
-// the value is in its register HERE (volatile asm statements keep their order)
-__device__ __forceinline__ void rowb_pin(double& v) { asm volatile("" : "+v"(v)); }
-template <int P>
-__device__ __forceinline__ int rowb_int(const int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + P, 0xf, 0xf, false); }
-
 // element el = r N + c of a padded block -> offset inside the caller's n x n block, -1 for the padding
 template <int N> __device__ __forceinline__ int ext_el(const int n, const int el) {
   if (n == N) return el;
@@ -402,7 +380,7 @@ struct ElimIO {
 // The arithmetic of the v_readlane form below: fma(-ap[r], f, col[r]) and col[r] += bcast_P(col[r]) * (-f) are the same bits.
 // Every lane of the wave runs every step (a DPP read of a lane that is switched off returns nothing).  Pivot, reciprocal and
 // factor are uniform per 16-lane ROW; the rows of a tile carry the same D columns, so they agree bit for bit.
-// Wait states: see rowb_mov.  Writers of a register a DPP operation reads, and what separates them from it --
+// Wait states: see rowb_mov (dpp_rowb.hpp).  Writers of a register a DPP operation reads, and what separates them from it --
 //   col[r], r != P : the loads / the swap (pinned in front of this step's rowb_mov) or the rowb_fmac of step P - 1 (this
 //                    step's rowb_mov and the reciprocal chain that depends on it lie between);
 //   col[P]         : the same, or the rowb_fmac immediately in front of rowb_mov (its s_nop);

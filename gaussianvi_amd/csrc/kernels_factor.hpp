@@ -36,6 +36,7 @@
 
 #include "box_moments.hpp"
 #include "device_common.hpp"
+#include "dpp_rowb.hpp"
 #include "halfspace_moments.hpp"
 
 namespace gvi {
@@ -325,7 +326,14 @@ __device__ __forceinline__ void prep_body(const FactorDev& f, const double* mu, 
 // Every psi kind that is NOT a polynomial of degree <= 2 (hinge / range factors, host-evaluated psi, gvi_expand) keeps
 // the symmetric root: there the node positions matter.  A non-positive pivot gives NaN exactly where a negative
 // eigenvalue did (the line search rejects such a trial either way).
-// lane i < d owns row i of the lower triangle; pivots / multipliers travel as wave-uniform scalars (v_readlane).
+// lane i < d owns row i of the lower triangle.  ROWB: every 16-lane row of the wave is a replica (row = lane & 15,
+// only lanes < d store) and pivots / multipliers are broadcast inside a row by DPP (dpp_rowb.hpp): a trailing update is ONE
+// v_fmac_f64_dpp instead of two v_readlane, an FMA and a 64-bit select -- 66 of them in the factorisation and 66 in L^-1 at
+// d = 12.  The same products with the same signs: bit-identical to the v_readlane form, NaN positions included (the entries
+// above the diagonal hold scratch values until their column's step zeroes them; nothing reads them before).
+// !ROWB: pivots / multipliers travel as wave-uniform scalars (v_readlane) -- what the launches of one wave per factor
+// (prep_kernel, prep_all_kernel) keep; option "chol_rowb" 1 puts prep_all_kernel on the row-broadcast instance, the bitwise
+// A/B inside one library.  The one-launch passes (factor_fused_kernel, factor_block3_kernel) take ROWB.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double chol_readlane(double v, int src) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
@@ -342,13 +350,61 @@ __device__ unsigned long long* gvi_prep_stamps;
 #define PREP_STAMP(i) do { } while (0)
 #endif
 
+// ---- the row-broadcast steps (compile-time recursion: the broadcast lane of a DPP control is an immediate) ----
+template <int DT, int J, int C>
+__device__ __forceinline__ void chol_rowb_trail(double (&row)[DT]) {
+  if constexpr (C < DT) {
+    rowb_fma<C>(row[C], row[J], row[J]);                       // row[c] -= L[c][j] * own L[.][j]
+    chol_rowb_trail<DT, J, C + 1>(row);
+  }
+}
+template <int DT, int I, int J>
+__device__ __forceinline__ void chol_rowb_xcol(double (&xcol)[DT], const double (&row)[DT]) {
+  if constexpr (J < DT) {
+    rowb_fma<J>(xcol[J], row[I], xcol[I]);                     // x_j -= L[j][i] * x_i
+    chol_rowb_xcol<DT, I, J + 1>(xcol, row);
+  }
+}
+// Wait states (dpp_rowb.hpp): the DPP-read operand of step j's updates is row[j], written by the scaling just in front --
+// rowb_settle; the pivot's rowb_mov carries its own s_nop behind the updates of step j - 1; L^-1 reads the finished rows,
+// settled in front of it.  Every lane executes every step.
+template <int DT, int J>
+__device__ __forceinline__ void chol_rowb_steps(double (&row)[DT], double (&inv)[DT], const int li) {
+  if constexpr (J < DT) {
+    const double pj = rowb_mov<J, 1>(row[J]);
+    double r = __builtin_amdgcn_rsq(pj);                      // 1 / sqrt(pj): NaN for a negative pivot
+    r = r * fma(-0.5 * pj * r, r, 1.5);
+    r = r * fma(-0.5 * pj * r, r, 1.5);
+    inv[J] = r;
+    row[J] = li == J ? pj * r : (li > J ? row[J] * r : 0.0);
+    rowb_settle(row[J]);
+    chol_rowb_trail<DT, J, J + 1>(row);
+    chol_rowb_steps<DT, J + 1>(row, inv, li);
+  }
+}
+template <int DT, int I>
+__device__ __forceinline__ void chol_rowb_inverse(double (&xcol)[DT], const double (&row)[DT], const double (&inv)[DT], const int li) {
+  if constexpr (I < DT) {
+    xcol[I] = li <= I ? xcol[I] * inv[I] : 0.0;
+    chol_rowb_xcol<DT, I, I + 1>(xcol, row);
+    chol_rowb_inverse<DT, I + 1>(xcol, row, inv, li);
+  }
+}
+
+// the form of the one-launch passes (-DGVI_CHOL_READLANE: measurement build, the fused route's A/B leg)
+#ifdef GVI_CHOL_READLANE
+constexpr bool CHOL_ROWB_DEFAULT = false;
+#else
+constexpr bool CHOL_ROWB_DEFAULT = true;
+#endif
+
 // Zs (LDS, optional): a copy of S^-T for an epilogue in the same launch (factor_fused_kernel)
 // Hs / u0s (LDS, optional; factor_fused_kernel's lean form): the psi operands H (column c at Hs + c hstride) and u0 stay in LDS
 // for the walk of the same launch and NOTHING of the per-pass products goes to memory (no S / S^-T / Sigma^-1 / H / u0
 // stores, Sigma^-1 is not formed: the caller's epilogue re-forms what it needs from Zs)
 // l_ready (LDS, optional; lean form only): ANOTHER wave of the block forms H = A L and u0 = b + A mu for this item
 // (prep_chol_hu0) -- this wave then skips the rows of A altogether and raises *l_ready once L is in its LDS area
-template <int DT>
+template <int DT, bool ROWB = CHOL_ROWB_DEFAULT>
 __device__ inline void prep_chol_body(const FactorDev& f, const double* mu, const double* Sigma, int k, double* sm, int kin, double* Zs = nullptr,
                                       double* Hs = nullptr, double* u0s = nullptr, const int hstride = 0, int* l_ready = nullptr) {
   const bool lean = Hs != nullptr;
@@ -357,7 +413,9 @@ __device__ inline void prep_chol_body(const FactorDev& f, const double* mu, cons
   double* Ll = sm;            // [d][d] L, zeros above the diagonal
   double* Xl = Ll + dd;       // [d][d] X = L^-1
   const double* Sg = Sigma + (size_t)kin * dd;
-  const int li = lane < d ? lane : d - 1;                     // lanes >= d shadow the last row (results unused)
+  static_assert(!ROWB || DT <= 16, "row-broadcast form: a row of L per lane of a 16-lane row");
+  const int lr = ROWB ? (lane & 15) : lane;                  // ROWB: the four 16-lane rows of the wave are replicas
+  const int li = lr < d ? lr : d - 1;                         // lanes >= d shadow the last row (results unused)
   // The rows of A (and b) the psi operands H = A L, u0 = b + A mu need do not depend on the factorisation: request them
   // NOW, so that their global-memory latency runs under the Cholesky instead of behind it (the prep is a chain of dependent
   // latencies: ~10 us per factor before this, profiles/r03 fused-pass stamps).  Element e = lane (+ 64) of H reads row e / d.
@@ -382,18 +440,24 @@ __device__ inline void prep_chol_body(const FactorDev& f, const double* mu, cons
   for (int c = 0; c < d; ++c) row[c] = c <= li ? Sg[li * d + c] : 0.0;      // lower triangle, like SelfAdjointEigenSolver
   PREP_STAMP(1);
   double inv[DT];
+  if constexpr (ROWB) {
 #pragma unroll
-  for (int j = 0; j < d; ++j) {
-    const double pj = chol_readlane(row[j], j);
-    double r = __builtin_amdgcn_rsq(pj);                      // 1 / sqrt(pj): NaN for a negative pivot
-    r = r * fma(-0.5 * pj * r, r, 1.5);
-    r = r * fma(-0.5 * pj * r, r, 1.5);
-    inv[j] = r;
-    row[j] = li == j ? pj * r : (li > j ? row[j] * r : 0.0);
+    for (int c = 0; c < d; ++c) rowb_pin(row[c]);
+    chol_rowb_steps<DT, 0>(row, inv, li);
+  } else {
 #pragma unroll
-    for (int c = j + 1; c < d; ++c) {
-      const double lcj = chol_readlane(row[j], c);
-      row[c] = li >= c ? fma(-row[j], lcj, row[c]) : 0.0;
+    for (int j = 0; j < d; ++j) {
+      const double pj = chol_readlane(row[j], j);
+      double r = __builtin_amdgcn_rsq(pj);                    // 1 / sqrt(pj): NaN for a negative pivot
+      r = r * fma(-0.5 * pj * r, r, 1.5);
+      r = r * fma(-0.5 * pj * r, r, 1.5);
+      inv[j] = r;
+      row[j] = li == j ? pj * r : (li > j ? row[j] * r : 0.0);
+#pragma unroll
+      for (int c = j + 1; c < d; ++c) {
+        const double lcj = chol_readlane(row[j], c);
+        row[c] = li >= c ? fma(-row[j], lcj, row[c]) : 0.0;
+      }
     }
   }
   PREP_STAMP(2);
@@ -405,11 +469,17 @@ __device__ inline void prep_chol_body(const FactorDev& f, const double* mu, cons
   double xcol[DT];
 #pragma unroll
   for (int i = 0; i < d; ++i) xcol[i] = li == i ? 1.0 : 0.0;
+  if constexpr (ROWB) {
 #pragma unroll
-  for (int i = 0; i < d; ++i) {
-    xcol[i] = li <= i ? xcol[i] * inv[i] : 0.0;
+    for (int c = 0; c < d; ++c) rowb_settle(row[c]);
+    chol_rowb_inverse<DT, 0>(xcol, row, inv, li);
+  } else {
 #pragma unroll
-    for (int j = i + 1; j < d; ++j) xcol[j] = fma(-chol_readlane(row[i], j), xcol[i], xcol[j]);
+    for (int i = 0; i < d; ++i) {
+      xcol[i] = li <= i ? xcol[i] * inv[i] : 0.0;
+#pragma unroll
+      for (int j = i + 1; j < d; ++j) xcol[j] = fma(-chol_readlane(row[i], j), xcol[i], xcol[j]);
+    }
   }
   PREP_STAMP(3);
   if (lane < d) {
@@ -622,15 +692,17 @@ __device__ __forceinline__ bool prep_is_chol(const FactorDev& f) {
   return f.chol && (f.d == 2 || f.d == 4 || f.d == 6 || f.d == 8 || f.d == 12);
 }
 
-template <int EPLP>
+// ROWB: the form of the register Cholesky (prep_chol_body).  The launches of one wave per factor keep v_readlane unless asked:
+// measured on the d = 24 + 12 chain's prep launch the row-broadcast form is 1.3 us SLOWER there (profiles/r06_unit_top.txt §4)
+template <int EPLP, bool ROWB = false>
 __device__ inline void prep_body_d(const FactorDev& f, const double* mu, const double* Sigma, int k, double* sm, int kin, double* Zs = nullptr) {
   if (f.chol) {
     switch (f.d) {
-      case 2: prep_chol_body<2>(f, mu, Sigma, k, sm, kin, Zs); return;
-      case 4: prep_chol_body<4>(f, mu, Sigma, k, sm, kin, Zs); return;
-      case 6: prep_chol_body<6>(f, mu, Sigma, k, sm, kin, Zs); return;
-      case 8: prep_chol_body<8>(f, mu, Sigma, k, sm, kin, Zs); return;
-      case 12: prep_chol_body<12>(f, mu, Sigma, k, sm, kin, Zs); return;
+      case 2: prep_chol_body<2, ROWB>(f, mu, Sigma, k, sm, kin, Zs); return;
+      case 4: prep_chol_body<4, ROWB>(f, mu, Sigma, k, sm, kin, Zs); return;
+      case 6: prep_chol_body<6, ROWB>(f, mu, Sigma, k, sm, kin, Zs); return;
+      case 8: prep_chol_body<8, ROWB>(f, mu, Sigma, k, sm, kin, Zs); return;
+      case 12: prep_chol_body<12, ROWB>(f, mu, Sigma, k, sm, kin, Zs); return;
       default: prep_chol_lds_body<EPLP>(f, mu, Sigma, k, sm, kin, Zs); return;
     }
   }
@@ -731,7 +803,8 @@ struct PrepList {
   double pred_val;
 };
 
-template <int EPLP>
+// ROWB: the form of the register Cholesky (option "chol_rowb"; default 0, v_readlane), an instance of its own each
+template <int EPLP, bool ROWB = false>
 __global__ __launch_bounds__(64) void prep_all_kernel(PrepList L) {
   extern __shared__ double sm[];
   const int lane = threadIdx.x;
@@ -744,7 +817,7 @@ __global__ __launch_bounds__(64) void prep_all_kernel(PrepList L) {
   int si = 0;
   while (si + 1 < L.nsets && (int)blockIdx.x >= L.koff[si + 1]) ++si;
   const int k = (int)blockIdx.x - L.koff[si];
-  if (!L.gather) { prep_body_d<EPLP>(L.f[si], L.mu[si], L.Sigma[si], k, sm, k); return; }
+  if (!L.gather) { prep_body_d<EPLP, ROWB>(L.f[si], L.mu[si], L.Sigma[si], k, sm, k); return; }
   const FactorDev& f = L.f[si];
   const int d = f.d, dd = d * d, dp = d + (d & 1), n = L.n, nn = n * n;
   double* Sl = sm + 4 * dd + 2 * dp + 3 * d + (dp + 1) / 2 + 1;  // behind prep_body's own LDS
@@ -767,7 +840,7 @@ __global__ __launch_bounds__(64) void prep_all_kernel(PrepList L) {
     L.mu_k[si][(size_t)k * d + e] = v;
   }
   wave_lds_sync();
-  prep_body_d<EPLP>(f, ml, Sl, k, sm, 0);
+  prep_body_d<EPLP, ROWB>(f, ml, Sl, k, sm, 0);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -517,6 +517,11 @@ gvi_status gvi_debug_fused_launches(int64_t counts[3]);
  * most four chunks per factor; options "fused" and "pair_fuse" on): how many launches of it this PROCESS has issued since the
  * library was loaded.  Read-only; a pass that took the three launches (products, moments, epilogue) does not count. */
 gvi_status gvi_debug_block3_launches(int64_t* count);
+/* Test hook of the per-pass products (option "chol_rowb"): copies what the last prep launch of the set left in memory -- S
+ * [K][d][d], S^-T [K][d][d], Sigma^-1 [K][d][d], H [K][d][m] (column-major per factor), u0 [K][m] -- after a stream sync.
+ * Any pointer may be NULL.  The one-launch factor pass keeps its products in LDS and leaves these arrays as they were: read
+ * them behind a pass of the three-launch route (option "fused" 0). */
+gvi_status gvi_debug_products(gvi_ctx* ctx, int set_id, double* S, double* Sinv, double* Lam, double* H, double* u0);
 /* Kernel variant override for A/B runs: 0 = auto (sum-of-squares sets with m = 6 / 12 on a table that decomposes into sign
  * orbits take the sign-orbit kernel; otherwise 5 / 2 / 1 as instantiated), 1 = generic LDS kernel, 2 = register kernel
  * (psi operands in LDS), 5 = register kernel with psi operands in SGPRs, 6 = sign-orbit kernel where supported, 7 = auto, with
@@ -543,7 +548,10 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *                                                     v_readlane kernels, one node per wave, in every pass)
  *   GVI_CHAIN_MERGE      chain_merge         1        top pass + first backward pass of the chain in one     bit-identical
  *                                                     launch (0: one launch per pass)
- *   GVI_FUSE_TRIAL       (gvi_ngd_set_mode)  2        0 reference pass order, 1 fused trial, 2 adaptive      identical iterates
+ *   GVI_CHOL_ROWB        chol_rowb           0        three-launch prep: register Cholesky with DPP row-     bit-identical
+ *                                                     broadcast multipliers (0: the v_readlane form; the
+ *                                                     one-launch factor passes always take the DPP form)
+ *   GVI_FUSE_TRIAL       (gvi_ngd_set_mode)  2       0 reference pass order, 1 fused trial, 2 adaptive      identical iterates
  *   GVI_SIDE_SOLVE       side_solve          1        gradient solve beside the trial factorisation, as one  bit-identical
  *                                                     dual launch (0, or a one-state chain: launched at once)
  *   GVI_NO_PAIR          pair_fuse           0 / 1    both chain sets in one psi launch (lane-per-point)     bit-identical
@@ -596,7 +604,14 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * releases); 0: one launch per pass.  The wait is bounded (1 s); on a time-out the waiting workgroups take NaN for what they
  * would have read, so the affected marginals / solution are NaN and the step is rejected -- value 2 is the test of that path
  * (the word is stored wrong on purpose).
- * Names: split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, warm_start, no_scost, target_waves,
+ * chol_rowb (default 0; environment GVI_CHOL_ROWB): the register Cholesky of the sum-of-squares sets (d = 2, 4, 6, 8, 12) in its
+ * row-broadcast form keeps a replica of the factor in every 16-lane row of the wave and broadcasts pivots and multipliers inside a
+ * row by DPP (row_newbcast): one v_fmac_f64_dpp per trailing update instead of two v_readlane, an FMA and a select.  Same
+ * products, same signs: bit-identical, NaN positions of a non-positive pivot included.  The one-launch factor passes always take
+ * that form (it shortens their one-wave-per-item products phase; a library built with -DGVI_CHOL_READLANE takes v_readlane there:
+ * the A/B leg of the fused route).  The option selects it for the three-launch route's prep launch too (an instance of its own),
+ * where it measured slower than v_readlane: there it is the bitwise A/B of the two forms inside one library.
+ * Names: chol_rowb, split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, warm_start, no_scost, target_waves,
  * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge, asm_dense, chain_pair,
  * trust_table_degree, safe_publish, sample_sweep, solve_lds. */
 gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value);
