@@ -68,7 +68,7 @@ struct Table {
   bool coded = false;
   // sign-orbit form (orbits.hpp; moments_orbit_kernel): host copy keeps only the tile lists, the rest lives on the device
   OrbitHost orb;
-  DevMem orb_cpk, orb_rpk, orb_mag, orb_w;
+  DevMem orb_cpk, orb_rpk, orb_mag, orb_w, orb_tau2;
   std::map<int, std::unique_ptr<DevMem>> orb_bounds;   // nchunk -> [nchunk + 1] tile bounds
 };
 
@@ -489,6 +489,8 @@ gvi_status upload_table(gvi_ctx* c, Table& t, int d, int p, int64_t N, const dou
       HIPCK(c, hipMemcpy(t.orb_cpk.p, o.cpk.data(), o.cpk.size() * 8, hipMemcpyHostToDevice));
       HIPCK(c, hipMemcpy(t.orb_mag.p, o.mag.data(), o.mag.size() * 8, hipMemcpyHostToDevice));
       HIPCK(c, hipMemcpy(t.orb_w.p, o.w.data(), o.w.size() * 8, hipMemcpyHostToDevice));
+      HIPCK(c, t.orb_tau2.ensure(o.tau2.size() * 8));
+      HIPCK(c, hipMemcpy(t.orb_tau2.p, o.tau2.data(), o.tau2.size() * 8, hipMemcpyHostToDevice));
       std::vector<uint64_t>().swap(o.cpk);
       std::vector<uint64_t>().swap(o.rpk);
       std::vector<double>().swap(o.mag);
@@ -725,6 +727,7 @@ gvi_status orbit_dev(gvi_ctx* c, FactorSet& s, OrbitDev* out) {
   }
   OrbitDev& ob = *out;
   ob.cpk = (const uint64_t*)t.orb_cpk.p; ob.rpk = (const uint64_t*)t.orb_rpk.p; ob.mag = t.orb_mag.d(); ob.w = t.orb_w.d();
+  ob.tau2 = t.orb_tau2.d();
   ob.bounds = it->second->i();
   ob.norb_p = t.orb.norb_p; ob.w0 = t.orb.w0;
   // the tile list as kernel arguments: class ends and, for up to four chunks, the chunk bounds

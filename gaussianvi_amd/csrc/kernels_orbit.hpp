@@ -9,16 +9,22 @@
 //   * the 2^s sign patterns are walked in Gray-code order, one coordinate flips per step:  v += +-2 m_j H[:, c_j]  (M FMAs);
 //   * only HALF the orbit is walked: for a +-pair the cross terms cancel (kernels_factor.hpp, sreg_pipe_body):
 //         psi(z) + psi(-z) = 2 (q + k0),  psi(z) - psi(-z) = 4 l,   q = sum_r s_r v_r^2,  l = sum_r (s_r u0_r) v_r,  v = H z;
-//   * within the orbit the moments are sign-weighted sums of those two scalars (Walsh sums):
-//         m0 += 2w sum(q + k0);   m1[c_i] += 4w m_i sum sigma_i l;   M2[c_i][c_j] += 2w m_i m_j sum sigma_i sigma_j (q + k0);
+//   * within the orbit the EVEN moments are sign-weighted sums of q (Walsh sums):
+//         m0 += 2w sum(q + k0);   M2[c_i][c_j] += 2w m_i m_j sum sigma_i sigma_j (q + k0);
 //     they are accumulated in registers with compile-time signs and added to the factor's accumulators ONCE per orbit;
+//   * the odd scalar l is NOT walked.  It is linear in v = sum_j sigma_j m_j H[:, c_j], so in sum_sigma sigma_i l every cross
+//     term cancels over the half orbit: = 2^(s-1) m_i a_{c_i}, a_c = sum_r s_r u0_r H[r][c], and the table's whole sum is
+//         m1[c] = tau2[c] a_c,   tau2[c] = 2 sum_k w_k z_kc^2   (per table, host: orbits.hpp),
+//     d M FMAs per factor behind the walk (orbit_wave; chunk 0 carries it).  The m1 slots of the accumulator layout stay
+//     where they are and are never added to.  It is the quadrature's m1 for THAT table -- tau2 / 2 misses 1 by 2e-12 at
+//     (12,5) -- formed without the cancellation noise of 17 k signed terms;
 //   * those adds go to data-dependent entries (the orbit's coordinates): LDS atomics (ds_add_f64).  The lanes of one
 //     instruction are served in a fixed order and every wave owns its accumulators, so results are run-to-run
 //     bit-identical (tests/test_gpu_parity.py checks it); the chunk partials are summed in fixed order by the epilogue as
 //     for every other kernel.
-// Per evaluation at (12,5): ~14 fp64 instructions in the walk + ~9 of per-orbit work, against 96 for the +-paired
-// lane-per-point kernel and 319 FMAs for the reference's x-space algorithm.  Registers: ~110 (M = 6, s = 4), so four and
-// more waves per SIMD instead of two.  The same kernel serves d = 24 (M = 12, s <= 6): accumulators and H sit in LDS, not
+// Per evaluation at (12,5): 11.3 fp64 instructions (6 for the flip, 6 for q, the rest Walsh sums and per-orbit scaling; 16.0
+// while l was walked too), against 96 for the +-paired lane-per-point kernel and 319 FMAs for the reference's x-space
+// algorithm.  Registers: ~100 (M = 6, s = 4), so four and more waves per SIMD instead of two.  The same kernel serves d = 24 (M = 12, s <= 6): accumulators and H sit in LDS, not
 // in registers, so the factor dimension no longer decides the kernel family.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +43,7 @@ struct OrbitDev {
   const uint64_t* rpk;       // [norb_p] packed-triangle row bases of the coordinates, ten bits each (OrbitRec)
   const double* mag;         // [smax][norb_p]
   const double* w;           // [norb_p]
+  const double* tau2;        // [d] 2 sum_k w_k z_kc^2 over the whole table (orbits.hpp): m1[c] = tau2[c] a_c (orbit_wave)
   const int32_t* bounds;     // [nchunk + 1] tile ranges of the chunks
   int64_t norb_p;
   double w0;                 // weight of the origin
@@ -119,10 +126,8 @@ __device__ __forceinline__ void lds_add_f64(double* p, double v) {
 // copy of entry 0; entry e lives at accb + (e << sh), sh = log2(copies) + 3.
 template <int S, typename Pre>
 __device__ __forceinline__ void orbit_accumulate(const int sh, const int (&c)[S], const uint64_t rpk, const double (&mg)[S], const double wp,
-                                                 const double E0, const double (&Eij)[S * (S - 1) / 2 + 1], const double (&Oi)[S],
-                                                 double* accb, Pre&& pre) {
-  constexpr int NV = 2 * S + S * (S - 1) / 2;
-  const double w4 = wp + wp;
+                                                 const double E0, const double (&Eij)[S * (S - 1) / 2 + 1], double* accb, Pre&& pre) {
+  constexpr int NV = S + S * (S - 1) / 2;
   double val[NV];
   {
     // The scale factors w m_i, w m_i m_j depend on the record alone: left to itself the scheduler forms all of them at the
@@ -135,7 +140,6 @@ __device__ __forceinline__ void orbit_accumulate(const int sh, const int (&c)[S]
 #pragma unroll
     for (int i = 0; i < S; ++i) {
       const double wm = wp * mgl[i];
-      val[n++] = w4 * mgl[i] * Oi[i];
       val[n++] = wm * mgl[i] * E0;
 #pragma unroll
       for (int j = i + 1; j < S; ++j) val[n++] = wm * mgl[j] * Eij[e++];
@@ -143,7 +147,6 @@ __device__ __forceinline__ void orbit_accumulate(const int sh, const int (&c)[S]
   }
   pre();
   char* const base = (char*)accb;
-  char* const base1 = base + (1u << sh);                         // m1[0]
   unsigned A[S], B[S];
 #pragma unroll
   for (int i = 0; i < S; ++i) {
@@ -155,7 +158,6 @@ __device__ __forceinline__ void orbit_accumulate(const int sh, const int (&c)[S]
   int n = 0;
 #pragma unroll
   for (int i = 0; i < S; ++i) {
-    lds_add_f64((double*)(base1 + B[i]), val[n]); ++n;
     lds_add_f64((double*)(base + (A[i] + B[i])), val[n]); ++n;
 #pragma unroll
     for (int j = i + 1; j < S; ++j) { lds_add_f64((double*)(base + (A[i] + B[j])), val[n]); ++n; }
@@ -167,8 +169,8 @@ __device__ __forceinline__ void orbit_accumulate(const int sh, const int (&c)[S]
 // NEXT tile's records (orbit_class)
 template <int M, int S, bool FULL, bool SIGNED, typename Pre>
 __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, const uint64_t rpk, const double (&mg)[S], const double w,
-                                           const double* Hl, double* accl, const double (&su0)[M], const double (&sg)[M],
-                                           const double k0, double& m0, Pre&& pre) {
+                                           const double* Hl, double* accl, const double (&sg)[M], const double k0, double& m0,
+                                           Pre&& pre) {
   int c[S];
 #pragma unroll
   for (int j = 0; j < S; ++j) c[j] = (int)((cpk >> (8 * j)) & 255u);
@@ -212,26 +214,23 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
 #pragma unroll
     for (int r = 0; r < M; ++r) h0[r] = hp[0][r];
   }
-  // Sign-weighted (Walsh) sums.  The two scalars of 8 consecutive half-points (a reflected Gray code walks the low three
-  // coordinates through all their sign patterns before it touches a higher one) are kept and ONE Walsh-Hadamard butterfly
-  // per scalar yields their sums over every mask of those coordinates: 2 x 24 additions instead of 8 x (1 + 6 + 4) at
-  // s = 4 (unused outputs are dead code); the signs of the higher coordinates are constant inside a block and multiply the
-  // block's sums.  WHT_BIG: also for s = 5, 6 (needs the registers: not at m = 12).
+  // Sign-weighted (Walsh) sums.  The scalar c+ of 8 consecutive half-points (a reflected Gray code walks the low three
+  // coordinates through all their sign patterns before it touches a higher one) is kept and ONE Walsh-Hadamard butterfly
+  // yields its sums over every mask of those coordinates: 24 additions instead of 8 x (1 + 6) at s = 4 (unused outputs
+  // are dead code); the signs of the higher coordinates are constant inside a block and multiply the block's sums.  WHT_BIG: also for s = 5, 6 (needs the registers: not at m = 12).
   constexpr bool WHT_BIG = M <= 6;
   constexpr bool WHT = FULL && S >= 2 && (S <= 4 || WHT_BIG);
   // coordinates whose signs vary inside a block of 2^LB consecutive Gray steps.  s = 4 takes two blocks of four instead of
-  // one of eight: the same number of additions (two 4-point butterflies per scalar + 11 signed adds for the second block
-  // against one 8-point butterfly) with 16 fewer live registers -- which is what lets the next tile's records be requested
+  // one of eight: the same number of additions (two 4-point butterflies + 7 signed adds for the second block against one
+  // 8-point butterfly) with fewer live registers -- which is what lets the next tile's records be requested
   // under the current tile's accumulator adds without spilling (orbit_class)
   constexpr int LBMAX = S == 4 ? 2 : 3;
   constexpr int LB = S - 1 < LBMAX ? S - 1 : LBMAX;
   constexpr int BLK = 1 << LB;
-  double cpv[WHT ? BLK : 1], lv[WHT ? BLK : 1];
-  double E0 = 0.0, Eij[S * (S - 1) / 2 + 1], Oi[S];
+  double cpv[WHT ? BLK : 1];
+  double E0 = 0.0, Eij[S * (S - 1) / 2 + 1];
 #pragma unroll
   for (int e = 0; e < S * (S - 1) / 2 + 1; ++e) Eij[e] = 0.0;
-#pragma unroll
-  for (int j = 0; j < S; ++j) Oi[j] = 0.0;
 #pragma unroll
   for (int g = 0; g < NH; ++g) {
     const int jn = g + 1 < NH ? __builtin_ctz(g + 1) : 0;        // coordinate of the next flip (compile-time after unrolling)
@@ -245,30 +244,25 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
         for (int r = 0; r < M; ++r) hn[r] = hp[jn][r];
       }
     }
-    double q = 0.0, l = 0.0;
+    double q = 0.0;
 #pragma unroll
-    for (int r = 0; r < M; ++r) {
-      q = SIGNED ? fma(sg[r] * v[r], v[r], q) : fma(v[r], v[r], q);
-      if (FULL) l = fma(su0[r], v[r], l);
-    }
+    for (int r = 0; r < M; ++r) q = SIGNED ? fma(sg[r] * v[r], v[r], q) : fma(v[r], v[r], q);
     const double cp = q + k0;
     if constexpr (WHT) {
-      // keep (c+, l) of this sign pattern of the low coordinates; at the end of a block: butterfly, then add the block's
+      // keep c+ of this sign pattern of the low coordinates; at the end of a block: butterfly, then add the block's
       // sums into the accumulators with the (compile-time) signs of the higher coordinates
       int b = 0;
 #pragma unroll
       for (int j = 0; j < LB; ++j) b |= (sig[j] > 0 ? 1 : 0) << j;             // compile-time after unrolling
       cpv[b] = cp;
-      lv[b] = l;
       if ((g & (BLK - 1)) == BLK - 1) {
 #pragma unroll
         for (int j = 0; j < LB; ++j) {
 #pragma unroll
           for (int bb = 0; bb < BLK; ++bb) {
             if (!(bb & (1 << j))) {            // (x[bit = 0], x[bit = 1]) -> (x0 + x1, x1 - x0): index = mask of multiplying signs
-              const double c0v = cpv[bb], c1v = cpv[bb | (1 << j)], l0v = lv[bb], l1v = lv[bb | (1 << j)];
+              const double c0v = cpv[bb], c1v = cpv[bb | (1 << j)];
               cpv[bb] = c0v + c1v; cpv[bb | (1 << j)] = c1v - c0v;
-              lv[bb] = l0v + l1v; lv[bb | (1 << j)] = l1v - l0v;
             }
           }
         }
@@ -277,11 +271,6 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
         int e = 0;
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-          {
-            const double t = i < LB ? lv[1 << i] : lv[0];
-            const bool pos = i < LB || sig[i] > 0;
-            Oi[i] = first ? (pos ? t : -t) : (pos ? Oi[i] + t : Oi[i] - t);
-          }
 #pragma unroll
           for (int j = i + 1; j < S; ++j) {
             const double t = j < LB ? cpv[(1 << i) | (1 << j)] : (i < LB ? cpv[1 << i] : cpv[0]);
@@ -297,7 +286,6 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
         int e = 0;
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-          Oi[i] = sig[i] > 0 ? Oi[i] + l : Oi[i] - l;
 #pragma unroll
           for (int j = i + 1; j < S; ++j) { Eij[e] = sig[i] * sig[j] > 0 ? Eij[e] + cp : Eij[e] - cp; ++e; }
         }
@@ -313,41 +301,35 @@ __device__ __forceinline__ void orbit_walk(const int lc, const uint64_t cpk, con
   const double wp = w + w;
   m0 = fma(wp, E0, m0);
   if constexpr (FULL) {
-    orbit_accumulate<S>(lc + 3, c, rpk, mg, wp, E0, Eij, Oi, accl, pre);
+    orbit_accumulate<S>(lc + 3, c, rpk, mg, wp, E0, Eij, accl, pre);
   } else {
     pre();
   }
 }
 
 // m = 12 with s = 4 / 5 / 6 (BASELINE configs[4]: d = 24, degree 7): the twelve rows as TWO walks of six.  Every accumulated
-// quantity is LINEAR in the two scalars of a point, q = sum_r s_r v_r^2 (+ k0) and l = sum_r s_r u0_r v_r, and both are sums
-// over the rows: the first walk accumulates with (q over rows 0..5 + k0, l over rows 0..5), the second with the rest, into the
-// same registers.  What that buys: the support's columns of six rows fit the registers (36 doubles at s = 6), so no column is
+// quantity is LINEAR in the scalar of a point, q = sum_r s_r v_r^2 (+ k0), which is a sum over the rows: the first walk
+// accumulates with q over rows 0..5 + k0, the second with the rest, into the same registers.  What that buys: the support's columns of six rows fit the registers (36 doubles at s = 6), so no column is
 // fetched from LDS inside the walk -- orbit_walk at m = 12 fetches twelve doubles at (almost) every Gray step, and its wave
 // waits for LDS in 15 % of its cycles -- and the Walsh butterfly of the sign-weighted sums (registers again) applies at
 // s = 5 / 6 as it does at m = 6.  Same number of fp64 instructions per orbit; sums re-associated (rows 0..5 first).
 template <int S, bool SIGNED, typename Pre>
 __device__ __forceinline__ void orbit_walk_split(const int lc, const uint64_t cpk, const uint64_t rpk, const double (&mg)[S], const double w,
-                                                 const double* Hl, double* accl, const double (&su0)[12], const double (&sg)[12],
-                                                 const double k0, double& m0, Pre&& pre) {
+                                                 const double* Hl, double* accl, const double (&sg)[12], const double k0, double& m0,
+                                                 Pre&& pre) {
   constexpr int MH = 6, HS = orbit_hstride(12), NH = 1 << (S - 1), LB = 3, BLK = 8;
   static_assert(S >= 4 && S <= 6, "split walk: s = 4, 5, 6 (blocks of 8 Gray steps)");
   int c[S];
 #pragma unroll
   for (int j = 0; j < S; ++j) c[j] = (int)((cpk >> (8 * j)) & 255u);
-  double E0 = 0.0, Eij[S * (S - 1) / 2 + 1], Oi[S];
+  double E0 = 0.0, Eij[S * (S - 1) / 2 + 1];
 #pragma unroll
   for (int e = 0; e < S * (S - 1) / 2 + 1; ++e) Eij[e] = 0.0;
-#pragma unroll
-  for (int j = 0; j < S; ++j) Oi[j] = 0.0;
 #pragma clang loop unroll(disable)
   for (int half = 0; half < 2; ++half) {
-    double suh[MH], sgh[MH];
+    double sgh[MH];
 #pragma unroll
-    for (int r = 0; r < MH; ++r) {
-      suh[r] = half ? su0[MH + r] : su0[r];
-      sgh[r] = SIGNED ? (half ? sg[MH + r] : sg[r]) : 1.0;
-    }
+    for (int r = 0; r < MH; ++r) sgh[r] = SIGNED ? (half ? sg[MH + r] : sg[r]) : 1.0;
     const double kk = half ? 0.0 : k0;
     double hcol[S][MH];
 #pragma unroll
@@ -367,31 +349,26 @@ __device__ __forceinline__ void orbit_walk_split(const int lc, const uint64_t cp
 #pragma unroll
       for (int r = 0; r < MH; ++r) v[r] = fma(-mg[j], hcol[j][r], v[r]);
     }
-    double cpv[BLK], lv[BLK];
+    double cpv[BLK];
 #pragma unroll
     for (int g = 0; g < NH; ++g) {
       const int jn = g + 1 < NH ? __builtin_ctz(g + 1) : 0;
-      double q = 0.0, l = 0.0;
+      double q = 0.0;
 #pragma unroll
-      for (int r = 0; r < MH; ++r) {
-        q = SIGNED ? fma(sgh[r] * v[r], v[r], q) : fma(v[r], v[r], q);
-        l = fma(suh[r], v[r], l);
-      }
+      for (int r = 0; r < MH; ++r) q = SIGNED ? fma(sgh[r] * v[r], v[r], q) : fma(v[r], v[r], q);
       const double cp = q + kk;
       int b = 0;
 #pragma unroll
       for (int j = 0; j < LB; ++j) b |= (sig[j] > 0 ? 1 : 0) << j;
       cpv[b] = cp;
-      lv[b] = l;
       if ((g & (BLK - 1)) == BLK - 1) {
 #pragma unroll
         for (int j = 0; j < LB; ++j) {
 #pragma unroll
           for (int bb = 0; bb < BLK; ++bb) {
             if (!(bb & (1 << j))) {
-              const double c0v = cpv[bb], c1v = cpv[bb | (1 << j)], l0v = lv[bb], l1v = lv[bb | (1 << j)];
+              const double c0v = cpv[bb], c1v = cpv[bb | (1 << j)];
               cpv[bb] = c0v + c1v; cpv[bb | (1 << j)] = c1v - c0v;
-              lv[bb] = l0v + l1v; lv[bb | (1 << j)] = l1v - l0v;
             }
           }
         }
@@ -399,11 +376,6 @@ __device__ __forceinline__ void orbit_walk_split(const int lc, const uint64_t cp
         int e = 0;
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-          {
-            const double t = i < LB ? lv[1 << i] : lv[0];
-            const bool pos = i < LB || sig[i] > 0;
-            Oi[i] = pos ? Oi[i] + t : Oi[i] - t;
-          }
 #pragma unroll
           for (int j = i + 1; j < S; ++j) {
             const double t = j < LB ? cpv[(1 << i) | (1 << j)] : (i < LB ? cpv[1 << i] : cpv[0]);
@@ -423,14 +395,14 @@ __device__ __forceinline__ void orbit_walk_split(const int lc, const uint64_t cp
   }
   const double wp = w + w;
   m0 = fma(wp, E0, m0);
-  orbit_accumulate<S>(lc + 3, c, rpk, mg, wp, E0, Eij, Oi, accl, pre);
+  orbit_accumulate<S>(lc + 3, c, rpk, mg, wp, E0, Eij, accl, pre);
 }
 
 // The Gray walk of ONE orbit, the support's columns in registers (orbit_walk's HREG case as a function of its own): the
-// sign-weighted sums E0 = sum (q + k0), Oi = sum sigma_i l, Eij = sum sigma_i sigma_j (q + k0) over the half orbit.
+// sign-weighted sums E0 = sum (q + k0), Eij = sum sigma_i sigma_j (q + k0) over the half orbit.
 template <int M, int S, bool FULL, bool SIGNED>
-__device__ __forceinline__ void orbit_gray(const double (&hcol)[S][M], const double (&mg)[S], const double (&su0)[M], const double (&sg)[M],
-                                           const double k0, double& E0, double (&Eij)[S * (S - 1) / 2 + 1], double (&Oi)[S]) {
+__device__ __forceinline__ void orbit_gray(const double (&hcol)[S][M], const double (&mg)[S], const double (&sg)[M], const double k0,
+                                           double& E0, double (&Eij)[S * (S - 1) / 2 + 1]) {
   static_assert(S <= 3, "orbit_gray: one butterfly block");
   constexpr int NH = 1 << (S - 1), LB = S - 1, BLK = NH;
   constexpr bool WHT = FULL && S >= 2;
@@ -445,37 +417,30 @@ __device__ __forceinline__ void orbit_gray(const double (&hcol)[S][M], const dou
 #pragma unroll
     for (int r = 0; r < M; ++r) v[r] = fma(-mg[j], hcol[j][r], v[r]);
   }
-  double cpv[WHT ? BLK : 1], lv[WHT ? BLK : 1];
+  double cpv[WHT ? BLK : 1];
   E0 = 0.0;
 #pragma unroll
   for (int e = 0; e < S * (S - 1) / 2 + 1; ++e) Eij[e] = 0.0;
 #pragma unroll
-  for (int j = 0; j < S; ++j) Oi[j] = 0.0;
-#pragma unroll
   for (int g = 0; g < NH; ++g) {
     const int jn = g + 1 < NH ? __builtin_ctz(g + 1) : 0;
-    double q = 0.0, l = 0.0;
+    double q = 0.0;
 #pragma unroll
-    for (int r = 0; r < M; ++r) {
-      q = SIGNED ? fma(sg[r] * v[r], v[r], q) : fma(v[r], v[r], q);
-      if (FULL) l = fma(su0[r], v[r], l);
-    }
+    for (int r = 0; r < M; ++r) q = SIGNED ? fma(sg[r] * v[r], v[r], q) : fma(v[r], v[r], q);
     const double cp = q + k0;
     if constexpr (WHT) {
       int b = 0;
 #pragma unroll
       for (int j = 0; j < LB; ++j) b |= (sig[j] > 0 ? 1 : 0) << j;
       cpv[b] = cp;
-      lv[b] = l;
       if (g == NH - 1) {
 #pragma unroll
         for (int j = 0; j < LB; ++j) {
 #pragma unroll
           for (int bb = 0; bb < BLK; ++bb) {
             if (!(bb & (1 << j))) {
-              const double c0v = cpv[bb], c1v = cpv[bb | (1 << j)], l0v = lv[bb], l1v = lv[bb | (1 << j)];
+              const double c0v = cpv[bb], c1v = cpv[bb | (1 << j)];
               cpv[bb] = c0v + c1v; cpv[bb | (1 << j)] = c1v - c0v;
-              lv[bb] = l0v + l1v; lv[bb | (1 << j)] = l1v - l0v;
             }
           }
         }
@@ -483,9 +448,8 @@ __device__ __forceinline__ void orbit_gray(const double (&hcol)[S][M], const dou
         int e = 0;
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-          Oi[i] = i < LB ? lv[1 << i] : lv[0];              // (the last coordinate keeps its + sign)
 #pragma unroll
-          for (int j = i + 1; j < S; ++j) { Eij[e] = j < LB ? cpv[(1 << i) | (1 << j)] : cpv[1 << i]; ++e; }
+          for (int j = i + 1; j < S; ++j) { Eij[e] = j < LB ? cpv[(1 << i) | (1 << j)] : cpv[1 << i]; ++e; }   // (the last coordinate keeps its + sign)
         }
       }
     } else {
@@ -494,7 +458,6 @@ __device__ __forceinline__ void orbit_gray(const double (&hcol)[S][M], const dou
         int e = 0;
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-          Oi[i] = sig[i] > 0 ? Oi[i] + l : Oi[i] - l;
 #pragma unroll
           for (int j = i + 1; j < S; ++j) { Eij[e] = sig[i] * sig[j] > 0 ? Eij[e] + cp : Eij[e] - cp; ++e; }
         }
@@ -525,10 +488,10 @@ __device__ __forceinline__ void orbit_load_wm(const OrbitDev& ob, const uint32_t
 // the current one is scaled into the sums.  Local tile tl of the class; t0, t1, tfirst wave-uniform.
 template <int M, int S, bool FULL, bool SIGNED>
 __device__ __forceinline__ void orbit_class_grouped(const OrbitDev& ob, const int lc, const int t0, const int t1, const int tfirst,
-                                                    const uint32_t lane8, const double* Hl, double* accl, const double (&su0)[M],
-                                                    const double (&sg)[M], const double k0, double& m0) {
+                                                    const uint32_t lane8, const double* Hl, double* accl, const double (&sg)[M],
+                                                    const double k0, double& m0) {
   static_assert(M * S <= 36, "support-major classes keep the support's columns in registers");
-  constexpr int NV = 2 * S + S * (S - 1) / 2;
+  constexpr int NV = S + S * (S - 1) / 2;
   const int G = ob.cgrp[S];
   const uint32_t gstride8 = (uint32_t)ob.cstride[S] * 8u;
   for (int t = t0; t < t1; ++t) {
@@ -553,8 +516,8 @@ __device__ __forceinline__ void orbit_class_grouped(const OrbitDev& ob, const in
 #pragma unroll
       for (int j = 0; j < S; ++j) mg[j] = cur.mg[j];
       const double w = cur.w;
-      double E0, Eij[S * (S - 1) / 2 + 1], Oi[S];
-      orbit_gray<M, S, FULL, SIGNED>(hcol, mg, su0, sg, k0, E0, Eij, Oi);
+      double E0, Eij[S * (S - 1) / 2 + 1];
+      orbit_gray<M, S, FULL, SIGNED>(hcol, mg, sg, k0, E0, Eij);
       // the next orbit of the lane (the last one requests itself again: no branch)
       const uint32_t bn = boff0 + (uint32_t)(g + 1 < G ? g + 1 : g) * gstride8;
       __builtin_amdgcn_sched_barrier(0);
@@ -563,12 +526,10 @@ __device__ __forceinline__ void orbit_class_grouped(const OrbitDev& ob, const in
       const double wp = w + w;
       m0 = fma(wp, E0, m0);
       if constexpr (FULL) {
-        const double w4 = wp + wp;
         int n = 0, e = 0;
 #pragma unroll
         for (int i = 0; i < S; ++i) {
           const double wm = wp * mg[i];
-          acc[n] = fma(w4 * mg[i], Oi[i], acc[n]); ++n;
           acc[n] = fma(wm * mg[i], E0, acc[n]); ++n;
 #pragma unroll
           for (int j = i + 1; j < S; ++j) { acc[n] = fma(wm * mg[j], Eij[e], acc[n]); ++n; ++e; }
@@ -578,7 +539,6 @@ __device__ __forceinline__ void orbit_class_grouped(const OrbitDev& ob, const in
     if constexpr (FULL) {
       const int sh = lc + 3;
       char* const base = (char*)accl;
-      char* const base1 = base + (1u << sh);
       unsigned A[S], B[S];
 #pragma unroll
       for (int i = 0; i < S; ++i) {
@@ -589,7 +549,6 @@ __device__ __forceinline__ void orbit_class_grouped(const OrbitDev& ob, const in
       int n = 0;
 #pragma unroll
       for (int i = 0; i < S; ++i) {
-        lds_add_f64((double*)(base1 + B[i]), acc[n]); ++n;
         lds_add_f64((double*)(base + (A[i] + B[i])), acc[n]); ++n;
 #pragma unroll
         for (int j = i + 1; j < S; ++j) { lds_add_f64((double*)(base + (A[i] + B[j])), acc[n]); ++n; }
@@ -607,8 +566,7 @@ constexpr int ORBIT_GROUP_SMAX = 3;
 // tried: the record stays live through every class loop -- 14 registers, spills -- for no gain.)
 template <int M, int S, bool FULL, bool SIGNED>
 __device__ __forceinline__ void orbit_class(const OrbitDev& ob, const int lc, const int t0, const int t1, const int tfirst, const uint32_t lane8,
-                                            const double* Hl, double* accl, const double (&su0)[M], const double (&sg)[M], const double k0,
-                                            double& m0) {
+                                            const double* Hl, double* accl, const double (&sg)[M], const double k0, double& m0) {
   if (t0 >= t1) return;
   // pipelined up to s = 3 only.  s >= 4: a tile is long enough (290 VALU instructions and more) for its own load latency
   // not to matter, and its walk leaves no 14 registers for the next tile's records
@@ -632,8 +590,8 @@ __device__ __forceinline__ void orbit_class(const OrbitDev& ob, const int lc, co
     double mg[S];
 #pragma unroll
     for (int j = 0; j < S; ++j) mg[j] = cur.mg[j];
-    if constexpr (M == 12 && S >= 4 && FULL) orbit_walk_split<S, SIGNED>(lc, cpk, rpk, mg, w, Hl, accl, su0, sg, k0, m0, pre);
-    else orbit_walk<M, S, FULL, SIGNED>(lc, cpk, rpk, mg, w, Hl, accl, su0, sg, k0, m0, pre);
+    if constexpr (M == 12 && S >= 4 && FULL) orbit_walk_split<S, SIGNED>(lc, cpk, rpk, mg, w, Hl, accl, sg, k0, m0, pre);
+    else orbit_walk<M, S, FULL, SIGNED>(lc, cpk, rpk, mg, w, Hl, accl, sg, k0, m0, pre);
   }
 }
 
@@ -671,16 +629,20 @@ __device__ __forceinline__ void orbit_wave(const OrbitArgs& a, const int k, cons
   if (FULL)
     for (int e = lane; e < NP * C; e += 64) accl[e] = 0.0;
   double* accme = accl + (lane & (C - 1));
+  // s_r u0_r of factor kf (= k: opaque where the value is to be read again instead of kept)
+  auto su0_at = [&](const int kf, const int r, double& u) {
+    if (u0pre) {                                   // wave-uniform value through LDS: back into SGPRs
+      const double t = u0pre[r];
+      u = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(t)), __builtin_amdgcn_readfirstlane(__double2loint(t)));
+    } else u = FRESH ? __builtin_nontemporal_load(a.u0 + (size_t)kf * M + r) : a.u0[(size_t)kf * M + r];
+    return SIGNED ? a.sgn[(size_t)kf * M + r] * u : u;
+  };
   double su0[M], sg[M], k0 = 0.0;
 #pragma unroll
   for (int r = 0; r < M; ++r) {
     double u;
-    if (u0pre) {                                   // wave-uniform value through LDS: back into SGPRs
-      const double t = u0pre[r];
-      u = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(t)), __builtin_amdgcn_readfirstlane(__double2loint(t)));
-    } else u = FRESH ? __builtin_nontemporal_load(a.u0 + (size_t)k * M + r) : a.u0[(size_t)k * M + r];
+    su0[r] = su0_at(k, r, u);                      // unsigned: u0 itself -- a wave-uniform scalar load, it stays in SGPRs
     sg[r] = SIGNED ? a.sgn[(size_t)k * M + r] : 1.0;
-    su0[r] = SIGNED ? sg[r] * u : u;               // unsigned: u0 itself -- a wave-uniform scalar load, it stays in SGPRs
     k0 = fma(su0[r], u, k0);
   }
   wave_lds_sync();
@@ -699,8 +661,8 @@ __device__ __forceinline__ void orbit_wave(const OrbitArgs& a, const int k, cons
   {                                                                                                   \
     const int e_ = te < ob.cend[S_] ? te : ob.cend[S_];                                                \
     if (tcur < e_) {                                                                                  \
-      if constexpr (S_ <= ORBIT_GROUP_SMAX && M * S_ <= 36) orbit_class_grouped<M, S_, FULL, SIGNED>(ob, lc, tcur, e_, ob.cend[S_ + 1], lane8, Hl, accme, su0, sg, k0, m0); \
-      else orbit_class<M, S_, FULL, SIGNED>(ob, lc, tcur, e_, ob.cend[S_ + 1], lane8, Hl, accme, su0, sg, k0, m0);            \
+      if constexpr (S_ <= ORBIT_GROUP_SMAX && M * S_ <= 36) orbit_class_grouped<M, S_, FULL, SIGNED>(ob, lc, tcur, e_, ob.cend[S_ + 1], lane8, Hl, accme, sg, k0, m0); \
+      else orbit_class<M, S_, FULL, SIGNED>(ob, lc, tcur, e_, ob.cend[S_ + 1], lane8, Hl, accme, sg, k0, m0);            \
       ORBIT_CLASS_STAMP(S_, e_ - tcur); tcur = e_;                                                     \
     }                                                                                                 \
   }
@@ -719,12 +681,32 @@ __device__ __forceinline__ void orbit_wave(const OrbitArgs& a, const int k, cons
   wave_lds_sync();
   if (lane == 0) out[0] = m0;
   if (FULL) {
+    // m1, the odd part of psi.  l = sum_r s_r u0_r v_r is LINEAR in v = sum_j sigma_j m_j H[:, c_j], so over the walked half
+    // orbit (last sign fixed, the others free) every cross term cancels: sum_sigma sigma_i l = 2^(s-1) m_i a_{c_i} with
+    // a_c = sum_r s_r u0_r H[r][c], and the table's whole sum is m1[c] = tau2[c] a_c (tau2: orbits.hpp).  Nothing of it is
+    // walked: lane c forms a_c from the factor's H (M FMAs in row order); chunk 0 carries the value, the others zero.
+    if (lane < d) {
+      double ac = 0.0;
+      if constexpr (SIGNED) {
+        // s_r u0_r read again here: M vector registers are not kept across the walk for it
+        int kf = k;
+        asm volatile("" : "+s"(kf));
+#pragma unroll
+        for (int r = 0; r < M; ++r) { double u; ac = fma(su0_at(kf, r, u), Hl[lane * orbit_hstride(M) + r], ac); }
+      } else {
+#pragma unroll
+        for (int r = 0; r < M; ++r) ac = fma(su0[r], Hl[lane * orbit_hstride(M) + r], ac);
+      }
+      out[1 + lane] = chunk == 0 ? ob.tau2[lane] * ac : 0.0;
+    }
     // copies in a fixed, lane-rotated order: with every lane starting at copy 0 each fourth lane sits on the same banks.
     // The usual eight copies: all reads of an entry in flight before the first add (with the run-time copy count the loop
-    // below is eight DEPENDENT LDS round trips per entry: 4400 cycles of a wave's 30 000 at (12,5), walk stamps)
+    // below is eight DEPENDENT LDS round trips per entry: 4400 cycles of a wave's 30 000 at (12,5), walk stamps).
+    // The loop starts behind the m1 slots; the rotation is taken from the ENTRY (= the lane's when the loop started at
+    // entry 1: every entry keeps the order in which its copies are summed, so m0 and M2 keep their bits)
     if (C == 8) {
-      for (int e = 1 + lane; e < NP; e += 64) {
-        int rot = (lane >> 2) & 7;
+      for (int e = 1 + d + lane; e < NP; e += 64) {
+        int rot = ((e - 1) >> 2) & 7;
         // (opaque: the eight rotated addresses are otherwise hoisted out of the fused pass's item loop and kept -- spilled --
         // across the whole walk: 32 of its 56 bytes of scratch per lane)
         asm volatile("" : "+v"(rot));
@@ -737,8 +719,8 @@ __device__ __forceinline__ void orbit_wave(const OrbitArgs& a, const int k, cons
         out[e] = t;
       }
     } else {
-      for (int e = 1 + lane; e < NP; e += 64) {
-        const int rot = (lane >> 2) & (C - 1);
+      for (int e = 1 + d + lane; e < NP; e += 64) {
+        const int rot = ((e - 1) >> 2) & (C - 1);
         double t = accl[e * C + rot];
         for (int q = 1; q < C; ++q) t += accl[e * C + ((q + rot) & (C - 1))];
         out[e] = t;

@@ -7,6 +7,7 @@
 // moments_orbit_kernel (kernels_orbit.hpp) walks an orbit per lane instead of a point per lane.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <unordered_map>
@@ -37,6 +38,11 @@ struct OrbitHost {
   // slot q is entry tile_first + lane + g * tile_gstride (cpk / rpk are repeated in every plane).
   std::vector<int32_t> tile_s, tile_first, tile_g, tile_gstride;
   int32_t cbase[ORBIT_SMAX + 2] = {0}, cgrp[ORBIT_SMAX + 2] = {0}, cstride[ORBIT_SMAX + 2] = {0};   // per class: first entry, G, stride
+  // [d] tau2[c] = 2 sum_k w_k z_kc^2 over the whole table = 2 sum over the orbits that hold c of 2^s w m_c^2: what the odd
+  // part of psi needs of the table (kernels_orbit.hpp: m1[c] = tau2[c] a_c).  The exact value is 2 for a rule of degree
+  // >= 2, but the table's own sum misses it by up to 2e-12 at (12,5) and the quadrature's m1 is the table's.  The terms
+  // cancel by ~1e4 (sum |w| = 1.2e4 at (12,5)): compensated (Neumaier) sum in table order, terms formed as (w m) m.
+  std::vector<double> tau2;
 };
 
 // cost of one tile in shader cycles of an unimpeded wave (walk stamps of the timing build, m = 6: 3100 per s = 4 tile,
@@ -72,6 +78,21 @@ inline OrbitHost build_orbits(int d, int64_t N, const double* Z, const double* w
     covered += (int64_t)1 << s;
   }
   if (covered != N) return o;                                   // some sign pattern is missing (or duplicated)
+  {
+    std::vector<double> sum((size_t)d, 0.0), comp((size_t)d, 0.0);
+    for (const Rep& r : reps) {
+      const double* z = Z + (size_t)r.row * d;
+      for (int a = 0; a < d; ++a) {
+        if (z[a] == 0.0) continue;
+        const double term = (double)((int64_t)1 << r.s) * ((w[r.row] * z[a]) * z[a]);      // (the power of two: exact)
+        const double t = sum[(size_t)a] + term;
+        comp[(size_t)a] += std::fabs(sum[(size_t)a]) >= std::fabs(term) ? (sum[(size_t)a] - t) + term : (term - t) + sum[(size_t)a];
+        sum[(size_t)a] = t;
+      }
+    }
+    o.tau2.resize((size_t)d);
+    for (int a = 0; a < d; ++a) o.tau2[(size_t)a] = 2.0 * (sum[(size_t)a] + comp[(size_t)a]);
+  }
   if (verify) {
     // key = |z| bit patterns of the row; every point must find its representative with an identical weight
     auto hash_row = [&](const double* z) {
