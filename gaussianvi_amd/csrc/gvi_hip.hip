@@ -31,6 +31,7 @@
 #include "kernels_solve.hpp"
 #include "kernels_interp.hpp"
 #include "kernels_sample_cost.hpp"
+#include "options.hpp"
 #include "orbits.hpp"
 #include "spgh.hpp"
 
@@ -100,10 +101,10 @@ struct FactorSet {
   bool closed_form = false;           // no sigma points: NGDFactorizedLinear route (sum-of-squares kinds), box_moments.hpp (HINGE_BOX, its default), halfspace_moments.hpp (HINGE_HALFSPACE, its default)
   bool chain_structured = false;      // start[k] == k (factor k on state k / states k, k + 1): assemble-on-load needs no CSR
   bool all_pos = false;               // every residual row has sgn = +1 (positive-definite weight)
-  double jtol = 1e-34;                // ctx->jacobi_tol
-  bool use_chol = true;               // ctx->chol_sqrt
+  double jtol = 1e-34;                // ctx->opt.jacobi_tol
+  bool use_chol = true;               // ctx->opt.chol_sqrt
   bool force_sym = false;             // set around passes whose caller sees the sigma points
-  bool use_mirror = true;             // evaluate +-pairs from the mirror-half table where the kernel supports it (ctx->mirror)
+  bool use_mirror = true;             // evaluate +-pairs from the mirror-half table where the kernel supports it (ctx->opt.mirror)
   int prep_slot = -1;                 // NGD slot whose (mu_k, Sigma_k) the per-pass products belong to
   hipStream_t st = nullptr;           // the set's own stream: prep -> moments -> epilogue overlap across sets
   hipEvent_t done = nullptr;
@@ -132,7 +133,7 @@ struct FactorSet {
     // Cholesky factor instead of the symmetric root: sum-of-squares psi on a generated table of degree >= 3 (exact
     // quadrature -- kernels_factor.hpp, prep_chol_body), the instantiated dimensions, and not when the caller is going
     // to look at the sigma points themselves (force_sym: gvi_expand / gvi_moments_from_psi) or runs the JKO map
-    f.chol = (use_chol && !force_sym && (kind == KIND_QUAD_PRIOR || kind == KIND_FIXED_PRIOR) && table->p >= 3 && d <= 32) ? 1 : 0;
+    f.chol = (use_chol && !force_sym && psi_kind_is<PSI_SUMSQ>(kind) && table->p >= 3 && d <= 32) ? 1 : 0;
     f.sdf = sdf.d(); f.sdf_rows = sdf_rows; f.sdf_cols = sdf_cols; f.sdf_ox = sdf_ox; f.sdf_oy = sdf_oy; f.sdf_cell = sdf_cell; f.sdf_inv_cell = 1.0 / sdf_cell; f.sdf_nz = sdf_nz; f.sdf_oz = sdf_oz; f.arm = arm.p ? arm.d() : nullptr;
     return f;
   }
@@ -156,8 +157,8 @@ struct NgdBook {
   // solve_deferred[gb]: the solve of gradient buffer gb is not launched yet -- it goes out fused with the next trial
   // factorisation (the dual launch of ngd_trial_state: same three launches, no second stream), or with its first other reader
   bool solve_deferred[2] = {false, false};
-  bool asm_pending[2] = {false, false};   // gradient buffer gb is NOT assembled yet (assemble-on-load, see gvi_ctx::asm_on_load)
-  bool last_first_accepted = true;        // adaptive fusing (gvi_ctx::fuse_trial = 2)
+  bool asm_pending[2] = {false, false};   // gradient buffer gb is NOT assembled yet (assemble-on-load, see Options::asm_on_load)
+  bool last_first_accepted = true;        // adaptive fusing (Options::fuse_trial = 2)
   int64_t n_full_pass = 0, n_cost_pass = 0;   // psi passes launched over all sets (gvi_ngd_counters)
   long profile_count = 0;                 // eligible launches seen by the profile sampling (gvi_ctx::profile_every)
 };
@@ -179,11 +180,9 @@ struct Posterior {
   // samplers / log-density (kernels_sample.hpp): workspaces of their own, so that a call between NGD steps touches nothing
   // the iteration reads or writes
   DevMem smp_ws, smp_io, smp_cws, smp_cwsi;
-  bool sample_sweep = true;           // option "sample_sweep" = 0: the samplers and the multi-solve run the factorisation only (tools/*_bench.py)
   // multi-right-hand-side solve / covariance columns (kernels_solve.hpp): the sampler's factor workspace (smp_ws) and staging
   // (smp_io), plus the node list of the columns
   DevMem slv_idx;
-  bool solve_lds = true;              // option "solve_lds" = 0: the sweep keeps its vectors in the output buffer whatever the size
   // dense-time queries (kernels_interp.hpp): the prepared set of gvi_interp_set in buffers of its own -- the samplers and the
   // solves overwrite smp_ws / smp_io, which only stage the inputs and outputs of a call here
   DevMem itp_ops, itp_qt, itp_idx, itp_bad;
@@ -206,65 +205,19 @@ struct gvi_ctx {
   NgdState ngd;
   DevMem Wbuf, Ibuf, vbuf, scratch, hldtmp;
   std::string err;
-  int variant = 0;
-  bool warm_start = true;             // resident NGD: Jacobi warm start from the previous eigenvectors
-  // gvi_ngd_step: trial cost from the full moments pass at the trial point (one psi pass per accepted iteration).
-  // 0 never, 1 always (first trial), 2 adaptive (default): fused while first trials keep being accepted, the m0-only
-  // cost pass after a rejection (a rejected fused trial wastes the moment accumulation)
-  int fuse_trial = 2;
-  bool speculate = true;              // gvi_ngd_step: queue the next gradients behind the first trial
+  Options opt;                        // every switch of gvi_set_option / the environment (options.hpp)
+  int variant = 0;                    // gvi_set_variant
+  bool prefer_opsi = false;           // gvi_set_variant(7)
+  bool speculate = true;              // gvi_ngd_step: queue the next gradients behind the first trial (gvi_ngd_set_mode)
   bool profile = false;
   bool profile_all = false;           // events around every moments / cost launch (else: set 0, full pass only)
   int profile_every = 1;              // on = 3: bracket only every 8th dominant launch (an event pair costs ~14 us of queue gaps)
-  int target_waves = 2048;
-  bool mirror = true;                 // GVI_MIRROR=0: never pair z with -z (A/B; results agree to rounding)
-  int split_flush = SPLIT_FLUSH;      // GVI_SPLIT_FLUSH=0: plain recursive sums in the split kernel (A/B of the (24,7) rounding)
-  bool sreg_pipe = true;              // GVI_SREG_PIPE=0: full pass on the compiler-scheduled body (A/B; bit-identical results)
-  bool no_scost = false;              // GVI_NO_SCOST=1: cost pass on the one-factor-per-wave kernel (A/B)
-  // sum-of-squares sets on the sign-orbit kernel (kernels_orbit.hpp) when the table decomposes; GVI_ORBIT=0: the
-  // lane-per-point kernels (A/B; results agree to rounding)
-  bool orbit = true;
-  // full moments pass of the resident iteration as ONE launch (kernels_fused.hpp) where every set runs the sign-orbit kernel;
-  // GVI_FUSED=0 / option "fused": the three-launch route prep -> psi -> epilogue (A/B; same numbers at four chunks per factor)
-  bool fused = true;
-  int orbit_waves = 4096;             // waves the orbit launch of one set aims for (chunks = orbit_waves / K, <= tiles)
-  // prep: cyclic Jacobi stops when (sum of squared off-diagonals) <= jacobi_tol * (sum of squared diagonals); option
-  // "jacobi_tol_exp" / GVI_JACOBI_TOL_EXP sets 10^value
-  double jacobi_tol = 1e-34;
-  // sum-of-squares sets: per-pass products from the Cholesky factor of the marginal instead of its symmetric square root
-  // (same moments -- the quadrature is exact there -- without the Jacobi sweeps); GVI_CHOL_SQRT=0 / option "chol_sqrt"
-  bool prefer_opsi = false;           // gvi_set_variant(7)
-  bool chol_sqrt = true;
-  // GVI_CHOL_ROWB=1 / option "chol_rowb": the register Cholesky of the three-launch route's prep (prep_all_kernel) in its
-  // row-broadcast form (kernels_factor.hpp, prep_chol_body<DT, ROWB>) instead of v_readlane; bit-identical (A/B inside one
-  // library), and slower in that launch (profiles/r06_unit_top.txt §4), hence off.  The fused pass takes the row-broadcast
-  // form unconditionally.
-  bool chol_rowb = false;
-  // option "trust_table_degree": a table handed to gvi_factors_add_table IS the Smolyak rule of the degree it is added
-  // under (e.g. the generator's own table, produced once and broadcast to the other ranks); it may then take every route
-  // the generated table takes (Cholesky factor for sum-of-squares psi).  Default 0: a caller's table keeps the symmetric
-  // root, as the reference maps the nodes.
-  bool trust_table_degree = false;
-  int orbit_min_tiles = 6;            // GVI_ORBIT_MIN_TILES
-  bool orbit_stack = true;            // two-set launch: block b takes item b of both sets (GVI_ORBIT_STACK=0: set 1 behind set 0)
-  int orbit_copies = 8;               // private LDS copies of the accumulators (1, 2, 4, 8, 16; fewer when LDS is short)
   static constexpr int cost_chunk_mult = 8;   // cost pass of the F-factor kernel: chunks per factor relative to the full pass
   int update_rule = 0;                // 0 natural gradient (NGD-GH), 1 proximal / JKO (ProxGVI-GH)
-  bool pair_fuse = true;              // GVI_NO_PAIR=1: one launch per set
-  bool fuse_gather = true;            // GVI_NO_FUSE_GATHER=1: stand-alone gather launch before the trial's prep
-  // the chain solve of the gradients goes out beside the next trial factorisation (independent given Vddmu), as one dual
-  // launch (dual_solve, NgdBook::solve_deferred); GVI_SIDE_SOLVE=0, or a one-state chain: the solve is launched at once
-  bool side_solve = true;
-  // assemble-on-load (GVI_ASM_ON_LOAD=0 / option "assemble_on_load": the stand-alone assemble launch): on chain-structured
-  // graphs the ordered assemble of (g, V_D, V_U) is not launched behind the factor pass but done by the first pass of the
-  // chain operations that consume it (kernels_chain.hpp, AsmList; NgdBook::asm_pending)
-  bool asm_on_load = true;
   DevMem Wbuf2, Ibuf2;                // second BCR workspace (the two chains are in flight together)
   // merged top + backward launch of the chain (chain_launch.hpp::ChainSync): a ring of word pairs, one pair per launch
   DevMem chain_sync;
   unsigned chain_seq = 0;
-  bool chain_merge = true;
-  bool chain_merge_fault = false;     // option chain_merge = 2: the hand-over word is stored wrong (test of the bounded wait)
   DevMem tail_counter;                // arrival counter of cost_tail_kernel (last block reduces)
   DevMem epi_counter;                 // two-level arrival counters of epilogue_all_kernel's tail
   // ---- sharded factors (one process per GPU): the exchange steps run inside the library, on the context stream ----
@@ -295,11 +248,6 @@ struct gvi_ctx {
     int pub_ring = 0;                 // host slot the next publish goes to
   } pipe;
   DevMem pipe_dev;                    // doubles: [0..1] accept words (ring), [2..3] cost of the state in NGD slot 0 / 1
-  // Option "pipeline" (GVI_PIPELINE=0 switches it off): gvi_ngd_run queues iteration i + 1 (predicated) before it has read
-  // the cost of iteration i.  Round 2 measured no gain (129.7 vs 130.5 us per C3 iteration: the early publish of the trial
-  // cost already gave the host its head start); with the round-3 kernels the iteration is short enough for the host's
-  // hand-over to show again: 109.3 -> 107.4 us at C3, 45.8 -> 44.3 us at C2.  On by default since then.
-  bool pipeline = true;
   double* host_slot = nullptr;        // host-mapped {cost value, sequence}: one 16-byte device store (publish_to_host)
   // kernels whose dynamic-LDS limit was raised on THIS context's device (the attribute is per device, and a
   // process may hold contexts on several devices)
@@ -311,9 +259,7 @@ struct gvi_ctx {
   struct StageRec { int stage; hipEvent_t e0, e1; };
   std::vector<StageRec> stage_recs;
   std::vector<hipEvent_t> stage_pool;
-  int spin_ms = 2;                    // wall-time bound of the host spin on the publish word (GVI_SPIN_MS)
   double* host_slot_dev = nullptr;
-  bool safe_publish = false;          // option "safe_publish": checked publish + release / acquire arrival counters (device_common.hpp)
   DevMem dbg_log;                     // gvi_debug_cost_log: ring of the costs the epilogue tails published, indexed by sequence
   int dbg_mask = 0;
   Posterior post;                     // state of the posterior queries (posterior_host.inc)
@@ -503,7 +449,7 @@ gvi_status upload_table(gvi_ctx* c, Table& t, int d, int p, int64_t N, const dou
 
 // device address of the current publish slot (four doubles per ring entry); bit 0 tags the checked form (publish_to_host)
 double* pub_slot(const gvi_ctx* c) {
-  return (double*)((unsigned long long)(c->host_slot_dev + 4 * c->pipe.pub_ring) | (c->safe_publish ? 1ull : 0ull));
+  return (double*)((unsigned long long)(c->host_slot_dev + 4 * c->pipe.pub_ring) | (c->opt.safe_publish ? 1ull : 0ull));
 }
 
 FactorSet* get_set(gvi_ctx* c, int id) {
@@ -511,12 +457,23 @@ FactorSet* get_set(gvi_ctx* c, int id) {
   return c->sets[id].get();
 }
 
-static_assert(SEG_MAX_J == GVI_SEG_MAX_J, "the device's and the header's limit on check points per segment factor");
+// What every setter that changes what the factors compute owes the resident iteration: the costs of both slots, the
+// gradients and the speculative gradients at the trial state were computed under the old setting.  Parked work (gpend,
+// solve_deferred, asm_pending), have_trial and the sets' prep_slot are not its business.
+void ngd_invalidate(gvi_ctx* c) {
+  c->ngd.cost_valid[0] = c->ngd.cost_valid[1] = false;
+  c->ngd.grad_valid = false;
+  c->ngd.spec_ready = false;
+}
+
+static_assert(Options{}.split_flush == SPLIT_FLUSH, "the default of option split_flush is the split kernel's own constant");
 
 // ---- the compiled instances of the factor kernels ----
 // Every kernel family has ONE list, with_<family>_instance: it hands f a tag that carries the template arguments of the
 // instance compiled for the shape and returns true, or returns false where there is none.  <family>_supported asks the list
 // with a no-op and the launch instantiates the kernel from the tag, so a new instance is registered by one line in its list.
+// These lists and the shape predicates (chain_pair_shape, planar_shape) choose KERNELS by kind; every FACT about a kind --
+// what it keeps, reads and offers -- is a row of psi_kinds.hpp.
 template <int D, typename Psi> struct RegInst {};
 template <int D, int M, bool PIPE> struct SregInst { static constexpr bool pipe = PIPE; };   // PIPE: the hand-pipelined body fits 256 registers
 template <int D, int M> struct ScostInst {};
@@ -524,14 +481,11 @@ template <int D, int R> struct SplitInst {};
 template <int M, int SMAX, int WAVES, bool PAIR> struct OrbitInst { static constexpr int waves = WAVES; static constexpr bool pair = PAIR; };
 template <int KIND> struct OrbitPsiInst {};
 template <int M, int SMAX, int WAVES, int D0, int D1> struct FusedInst {};
+struct ClosedSumsq {};
+struct ClosedBox {};
+struct ClosedHalfspace {};
 constexpr auto any_instance = [](auto) {};
 template <class F, class Inst> bool hit(F& f, Inst inst) { f(inst); return true; }
-
-// the hinge-on-SDF kinds: psi reads a signed-distance grid (gvi_factors_set_sdf2d / _sdf3d)
-bool sdf_kind(int kind) {
-  return kind == KIND_HINGE_SDF_2D || kind == KIND_HINGE_SDF_2D_BODY || kind == KIND_HINGE_SDF_3D || kind == KIND_HINGE_SDF_3D_ARM ||
-         kind == KIND_HINGE_SDF_2D_SEG || kind == KIND_HINGE_SDF_3D_SEG;
-}
 
 // moments_reg_kernel<D, Psi, full>: lane-per-point, psi operands in LDS
 template <class F>
@@ -660,12 +614,24 @@ bool with_fused_instance(int m, int smax, int d0, int d1, F&& f) {
   return false;
 }
 
+// the quadrature-free kernels (PSI_CLOSED kinds): moments_closed_kernel, moments_box_closed_kernel, moments_halfspace_closed_kernel
+template <class F>
+bool with_closed_instance(int kind, F&& f) {
+  switch (kind) {
+    case KIND_QUAD_PRIOR:
+    case KIND_FIXED_PRIOR: return hit(f, ClosedSumsq{});
+    case KIND_HINGE_BOX: return hit(f, ClosedBox{});
+    case KIND_HINGE_HALFSPACE: return hit(f, ClosedHalfspace{});
+  }
+  return false;
+}
+
 bool reg_supported(int kind, int d, int m) { return with_reg_instance(kind, d, m, any_instance); }
 bool sreg_supported(const FactorSet& s) { return with_sreg_instance(s.kind, s.d, s.m, any_instance); }
 bool scost_supported(const FactorSet& s) { return with_scost_instance(s.kind, s.d, s.m, any_instance); }
 // sum-of-squares kinds on a coded table
 bool split_supported(const FactorSet& s) {
-  return (s.kind == KIND_QUAD_PRIOR || s.kind == KIND_FIXED_PRIOR) && s.table->coded && with_split_instance(s.d, s.m, any_instance);
+  return psi_kind_is<PSI_SUMSQ>(s.kind) && s.table->coded && with_split_instance(s.d, s.m, any_instance);
 }
 bool orbit_pair_supported(int m, int smax) {
   bool pair = false;
@@ -691,7 +657,7 @@ void chunk_tiles(FactorSet& s, int64_t nch) {
   s.nchunk = (int)((Np + s.chunk - 1) / s.chunk);
 }
 // lane-per-point kernels: target_waves waves over the set; generic kernel: ~1024 blocks
-void plan_chunks(gvi_ctx* c, FactorSet& s, bool reg) { chunk_tiles(s, ((reg ? c->target_waves : 1024) + s.K - 1) / s.K); }
+void plan_chunks(gvi_ctx* c, FactorSet& s, bool reg) { chunk_tiles(s, ((reg ? c->opt.target_waves : 1024) + s.K - 1) / s.K); }
 
 template <int D, typename Psi>
 void launch_reg(const MomArgs& a, dim3 grid, hipStream_t st) {
@@ -708,8 +674,8 @@ void launch_sreg(const MomArgs& a, dim3 grid, hipStream_t st, bool pipe) {
 
 // ---- sign-orbit kernel (kernels_orbit.hpp) ----
 bool orbit_supported(const gvi_ctx* c, const FactorSet& s) {
-  if (!c->orbit || !(c->variant == 0 || c->variant == 6)) return false;
-  if (s.kind != KIND_QUAD_PRIOR && s.kind != KIND_FIXED_PRIOR) return false;
+  if (!c->opt.orbit || !(c->variant == 0 || c->variant == 6)) return false;
+  if (!psi_kind_is<PSI_SUMSQ>(s.kind)) return false;
   const OrbitHost& o = s.table->orb;
   return s.d <= 32 && o.ok && !o.tile_s.empty() && with_orbit_instance(s.m, o.smax, any_instance);
 }
@@ -765,7 +731,7 @@ gvi_status orbit_args(gvi_ctx* c, FactorSet& s, OrbitArgs* out) {
   if (!waves) return fail(c, GVI_ERR_STATE, "orbit_args: no sign-orbit instance for this set");
   const size_t lds_cap = std::min<size_t>(64 * 1024, 160 * 1024 / waves);
   a.copies = 1;
-  while (a.copies * 2 <= c->orbit_copies && (size_t)4 * orbit_lds_doubles(s.d, s.m, a.copies * 2) * 8 <= lds_cap) a.copies *= 2;
+  while (a.copies * 2 <= c->opt.orbit_copies && (size_t)4 * orbit_lds_doubles(s.d, s.m, a.copies * 2) * 8 <= lds_cap) a.copies *= 2;
   GVICK(orbit_dev(c, s, &a.ob));
   *out = a;
   return GVI_OK;
@@ -783,27 +749,23 @@ void launch_orbit_t(const OrbitArgs& a, bool full, bool all_pos, dim3 grid, size
 // (hipExtLaunchKernel: the kernel's own begin / end timestamps, what rocprofv3 reports -- a hipEventRecord pair around a
 // 28 us launch reads ~3 us more than the kernel runs)
 template <int M, int SMAX, int WAVES>
-void launch_orbit_pair_t(const OrbitArgs& a0, const OrbitArgs& a1, bool full, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1,
-                         bool stack) {
+void launch_orbit_pair_t(const OrbitArgs& a0, const OrbitArgs& a1, bool full, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   const int nbx0 = (a0.K + 3) / 4, nbx1 = (a1.K + 3) / 4;
   const int nb0 = nbx0 * a0.nchunk, nb1 = nbx1 * a1.nchunk;
-  // stacked: block b takes item b of both sets (negative nbx1 tells the kernel); else set 1's blocks behind set 0's
-  const int grid = stack ? std::max(nb0, nb1) : nb0 + nb1;
-  const int nx1 = stack ? -nbx1 : nbx1;
+  const int grid = std::max(nb0, nb1);      // block b takes item b of both sets
   if (full)
     hipExtLaunchKernelGGL((moments_orbit_pair_kernel<M, SMAX, true, false, WAVES>), dim3(grid), dim3(256), (uint32_t)lds, st, e0, e1, 0,
-                          a0, a1, nbx0, nb0, nx1);
+                          a0, a1, nbx0, nb0, nbx1);
   else
     hipExtLaunchKernelGGL((moments_orbit_pair_kernel<M, SMAX, false, false, WAVES>), dim3(grid), dim3(256), (uint32_t)lds, st, e0, e1, 0,
-                          a0, a1, nbx0, nb0, nx1);
+                          a0, a1, nbx0, nb0, nbx1);
 }
 
 // m and smax as orbit_pair_supported accepted them
-void launch_orbit_pair(const OrbitArgs& a0, const OrbitArgs& a1, int m, int smax, bool full, hipStream_t st, bool stack,
-                       hipEvent_t e0, hipEvent_t e1) {
+void launch_orbit_pair(const OrbitArgs& a0, const OrbitArgs& a1, int m, int smax, bool full, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   const size_t lds = (size_t)4 * std::max(orbit_lds_doubles(a0.d, m, a0.copies), orbit_lds_doubles(a1.d, m, a1.copies)) * 8;
   with_orbit_instance(m, smax, [&]<int M, int SMAX, int WAVES, bool PAIR>(OrbitInst<M, SMAX, WAVES, PAIR>) {
-    if constexpr (PAIR) launch_orbit_pair_t<M, SMAX, WAVES>(a0, a1, full, lds, st, e0, e1, stack);
+    if constexpr (PAIR) launch_orbit_pair_t<M, SMAX, WAVES>(a0, a1, full, lds, st, e0, e1);
   });
 }
 
@@ -896,12 +858,12 @@ gvi_status run_prep(gvi_ctx* c, FactorSet& s, const double* mu, const double* Si
 // (three independent kernels for these kinds); the arm graph's 0.27 ms launch was its d = 28 PRIOR set on the generic kernel,
 // which now takes the m = 14 instance of the sign-orbit kernel.
 bool orbit_psi_supported(const gvi_ctx* c, const FactorSet& s) {
-  if (!c->orbit) return false;
+  if (!c->opt.orbit) return false;
   if (!(c->variant == 0 && c->prefer_opsi)) return false;
   if (!with_orbit_psi_instance(s.kind, any_instance)) return false;
   const OrbitHost& o = s.table->orb;
   if (!(o.ok && o.smax >= 1 && o.smax <= 4 && !o.tile_s.empty()) || s.d > 32) return false;
-  if (s.kind == KIND_HINGE_SDF_3D_ARM && (s.arm_ndof < 1 || s.arm_ndof > orbit_psi_rows(KIND_HINGE_SDF_3D_ARM))) return false;
+  if (psi_kind_is<PSI_ARM>(s.kind) && (s.arm_ndof < 1 || s.arm_ndof > orbit_psi_rows(s.kind))) return false;
   return orbit_psi_rows(s.kind) <= s.d;
 }
 
@@ -935,15 +897,48 @@ struct MomPlan {
 // lane-per-point register kernels: a block's four waves take four factors, grid ((K + 3) / 4, nchunk) but for Scost's own launch
 bool lane_per_point(const MomPlan& p) { return p.route == Route::Sreg || p.route == Route::Scost || p.route == Route::Reg; }
 
+// grid, block and LDS of a closed-form launch, and the launch itself, per kernel of with_closed_instance (p.grid = K blocks on entry)
+gvi_status plan_closed(gvi_ctx*, const FactorSet&, MomPlan&, ClosedSumsq) { return GVI_OK; }
+gvi_status plan_closed(gvi_ctx* c, const FactorSet& s, MomPlan& p, ClosedBox) {
+  p.lds = box_closed_lds_doubles(s.d) * 8;
+  if (p.lds > 64 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_BOX kernel LDS budget (d <= 89)");
+  return GVI_OK;
+}
+gvi_status plan_closed(gvi_ctx* c, const FactorSet& s, MomPlan& p, ClosedHalfspace) {
+  if (s.d > 32) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_HALFSPACE kernel supports d <= 32");
+  // a wave holds G = 64 / Jp factors.  One wave per block while the launch has no more waves than the chip has SIMDs
+  // (256 CUs x 4): every wave can start at once wherever its block lands; above that four waves per block, a quarter
+  // of the workgroups to dispatch
+  const int64_t nwaves = (s.K + 64 / halfspace_group(s.seg_J) - 1) / (64 / halfspace_group(s.seg_J));
+  const int wpb = nwaves <= 1024 ? 1 : 4;
+  p.block = 64 * wpb;
+  p.grid = dim3((unsigned)((nwaves + wpb - 1) / wpb));
+  p.lds = (size_t)wpb * halfspace_closed_lds_doubles(s.d) * 8;
+  return GVI_OK;
+}
+gvi_status launch_closed(gvi_ctx*, const MomPlan& p, hipStream_t st, ClosedSumsq) {
+  hipLaunchKernelGGL(moments_closed_kernel, p.grid, dim3(64), 0, st, p.a);
+  return GVI_OK;
+}
+gvi_status launch_closed(gvi_ctx*, const MomPlan& p, hipStream_t st, ClosedBox) {
+  hipLaunchKernelGGL(moments_box_closed_kernel, p.grid, dim3(64), p.lds, st, p.a);
+  return GVI_OK;
+}
+gvi_status launch_closed(gvi_ctx* c, const MomPlan& p, hipStream_t st, ClosedHalfspace) {
+  if (p.lds > 64 * 1024) GVICK(allow_lds(c, (const void*)moments_halfspace_closed_kernel, (int)p.lds));
+  hipLaunchKernelGGL(moments_halfspace_closed_kernel, p.grid, dim3(p.block), p.lds, st, p.a);
+  return GVI_OK;
+}
+
 // Everything before the launch: state checks, route under `variant` and the options, chunking (s.nchunk / chunk / use_*),
 // the partial buffer, the kernel arguments.  prep must have run for (mu, Sigma) before the plan is launched.
 gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double* psi_ext, int full, MomPlan* out) {
   MomPlan& p = *out;
   p.route = Route::Empty; p.full = full;
   if (s.K == 0) { s.nchunk = 1; s.chunk = s.table->Np; s.use_reg = s.use_split = s.use_orbit = s.use_opsi = false; return GVI_OK; }   // empty shard
-  if (s.kind == KIND_HINGE_SDF_3D_ARM && !psi_ext && !s.arm.p)
+  if (psi_kind_is<PSI_ARM>(s.kind) && !psi_ext && !s.arm.p)
     return fail(c, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");
-  if (sdf_kind(s.kind) && !psi_ext && s.sdf_rows == 0)
+  if (psi_kind_is<PSI_SDF>(s.kind) && !psi_ext && s.sdf_rows == 0)
     return fail(c, GVI_ERR_STATE, "HINGE_SDF set without a grid: call gvi_factors_set_sdf2d / gvi_factors_set_sdf3d");
   bool reg = reg_supported(s.kind, s.d, s.m) && !psi_ext && c->variant != 1;
   if (c->variant == 2 && !reg && !psi_ext)
@@ -958,8 +953,8 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
     const int64_t tiles = (int64_t)s.table->orb.tile_s.size();
     // chunks: enough waves to fill the chip, but at least orbit_min_tiles tiles per wave -- a wave's prologue (H into LDS,
     // zeroing the accumulator copies) and its reduction of the copies cost about as much as two tiles
-    const int64_t by_waves = std::max<int64_t>(1, (c->orbit_waves + s.K - 1) / s.K);
-    const int64_t by_tiles = std::max<int64_t>(1, tiles / std::max(1, c->orbit_min_tiles));
+    const int64_t by_waves = std::max<int64_t>(1, (c->opt.orbit_waves + s.K - 1) / s.K);
+    const int64_t by_tiles = std::max<int64_t>(1, tiles / std::max(1, c->opt.orbit_min_tiles));
     s.nchunk = (int)std::min<int64_t>(tiles, std::min(by_waves, by_tiles));
     s.chunk = s.table->Np;
   } else if (split) {
@@ -973,7 +968,7 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
   // auto (variants 0 and 5): psi operands from SGPRs where instantiated (fastest for both passes); otherwise the operand-
   // resident kernel for the cost pass and the LDS-operand kernel for the full pass
   const bool sgpr = reg && (c->variant == 5 || c->variant == 0);
-  const bool scost = sgpr && !full && scost_supported(s) && !c->no_scost;
+  const bool scost = sgpr && !full && scost_supported(s) && !c->opt.no_scost;
   if (scost) chunk_tiles(s, (int64_t)s.nchunk * c->cost_chunk_mult);   // two factors per wave: keep the wave count up with more, shorter chunks
   s.use_reg = reg;
   s.use_split = split;
@@ -982,9 +977,9 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
   const size_t need = (size_t)s.K * s.nchunk * npairs(s.d) * 8;
   HIPCK(c, s.partial.ensure(need));
   MomArgs& a = p.a;
-  s.use_mirror = c->mirror;
+  s.use_mirror = c->opt.mirror;
   a.f = s.dev(); a.mu = mu; a.psi_ext = psi_ext; a.partial = s.partial.d();
-  a.chunk = s.chunk; a.nchunk = s.nchunk; a.full = full; a.flush = c->split_flush;
+  a.chunk = s.chunk; a.nchunk = s.nchunk; a.full = full; a.flush = c->opt.split_flush;
   a.mchunk = 0;
   a.pred = c->pipe.pred; a.pred_val = c->pipe.pred_val;
   if (s.table->Nmp > 0) {                                   // same number of chunks over the mirror-half table
@@ -995,21 +990,9 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
   if (closed) {
     p.route = Route::Closed;
     p.grid = dim3(s.K);
-    if (s.kind == KIND_HINGE_BOX) {
-      p.lds = box_closed_lds_doubles(s.d) * 8;
-      if (p.lds > 64 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_BOX kernel LDS budget (d <= 89)");
-    }
-    if (s.kind == KIND_HINGE_HALFSPACE) {
-      if (s.d > 32) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_HALFSPACE kernel supports d <= 32");
-      // a wave holds G = 64 / Jp factors.  One wave per block while the launch has no more waves than the chip has SIMDs
-      // (256 CUs x 4): every wave can start at once wherever its block lands; above that four waves per block, a quarter
-      // of the workgroups to dispatch
-      const int64_t nwaves = (s.K + 64 / halfspace_group(s.seg_J) - 1) / (64 / halfspace_group(s.seg_J));
-      const int wpb = nwaves <= 1024 ? 1 : 4;
-      p.block = 64 * wpb;
-      p.grid = dim3((unsigned)((nwaves + wpb - 1) / wpb));
-      p.lds = (size_t)wpb * halfspace_closed_lds_doubles(s.d) * 8;
-    }
+    gvi_status rc = GVI_OK;
+    with_closed_instance(s.kind, [&](auto inst) { rc = plan_closed(c, s, p, inst); });
+    GVICK(rc);
   } else if (orbit) {
     p.route = Route::Orbit;
     GVICK(orbit_args(c, s, &p.oa));
@@ -1023,7 +1006,7 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
     GVICK(orbit_dev(c, s, &pa.ob));                         // table pointers, class layout, chunk bounds
     const int NR = orbit_psi_rows(s.kind);
     pa.copies = 1;
-    while (pa.copies * 2 <= c->orbit_copies && (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies * 2, true) * 8 <= 64 * 1024) pa.copies *= 2;
+    while (pa.copies * 2 <= c->opt.orbit_copies && (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies * 2, true) * 8 <= 64 * 1024) pa.copies *= 2;
     p.lds = (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies, full != 0) * 8;
   } else if (split) {
     p.route = Route::Split;
@@ -1033,7 +1016,7 @@ gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double
     p.grid = dim3((s.K + 7) / 8, s.nchunk);
   } else if (sgpr && sreg_supported(s)) {
     p.route = Route::Sreg;
-    with_sreg_instance(s.kind, s.d, s.m, [&](auto inst) { p.pipe = inst.pipe && c->sreg_pipe && s.table->Zq.p; });
+    with_sreg_instance(s.kind, s.d, s.m, [&](auto inst) { p.pipe = inst.pipe && c->opt.sreg_pipe && s.table->Zq.p; });
   } else if (reg) {
     p.route = Route::Reg;
   } else {
@@ -1057,12 +1040,7 @@ gvi_status launch_plan(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t s
     case Route::Empty:
       return GVI_OK;
     case Route::Closed:
-      if (s.kind == KIND_HINGE_BOX) hipLaunchKernelGGL(moments_box_closed_kernel, p.grid, dim3(64), p.lds, st, a);
-      else if (s.kind == KIND_HINGE_HALFSPACE) {
-        if (p.lds > 64 * 1024) GVICK(allow_lds(c, (const void*)moments_halfspace_closed_kernel, (int)p.lds));
-        hipLaunchKernelGGL(moments_halfspace_closed_kernel, p.grid, dim3(p.block), p.lds, st, a);
-      }
-      else hipLaunchKernelGGL(moments_closed_kernel, p.grid, dim3(64), 0, st, a);
+      hit = with_closed_instance(s.kind, [&](auto inst) { rc = launch_closed(c, p, st, inst); });
       break;
     case Route::Orbit:
       hit = with_orbit_instance(s.m, p.smax, [&]<int M, int SMAX, int WAVES, bool PAIR>(OrbitInst<M, SMAX, WAVES, PAIR>) {
@@ -1101,7 +1079,7 @@ gvi_status launch_plan(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t s
 // warm-started Jacobi of the symmetric-root products: the set's last eigenvectors go to the launch; a cold start every 32nd
 // prep bounds the drift
 gvi_status warm_start_of(gvi_ctx* ctx, FactorSet& s, FactorDev& f) {
-  if (!ctx->warm_start) return GVI_OK;
+  if (!ctx->opt.warm_start) return GVI_OK;
   if (s.Vws.bytes == 0) { HIPCK(ctx, s.Vws.ensure((size_t)s.K * s.d * s.d * 8)); s.warm_count = 0; }
   f.Vws = s.Vws.d();
   f.warm = (s.warm_count % 32) != 0;
@@ -1133,7 +1111,7 @@ gvi_status fill_epi_tail(gvi_ctx* ctx, int nitems, int publish_slot, EpiTail* ou
   tail.on = 0; tail.acc = nullptr; tail.half_logdet = nullptr; tail.host_out = nullptr; tail.seq = 0.0; tail.counter = nullptr;
   tail.pred = ctx->pipe.pred; tail.pred_val = ctx->pipe.pred_val;
   tail.accept = nullptr; tail.cost_dev = nullptr; tail.slot_cur = tail.slot_trial = 0; tail.c0_use_imm = 1; tail.c0_imm = 0.0;
-  tail.safe = ctx->safe_publish ? 1 : 0;
+  tail.safe = ctx->opt.safe_publish ? 1 : 0;
   if (publish_slot < 0) return GVI_OK;
   const size_t need = (size_t)128 * (2 + (size_t)nitems / EPI_GROUP);
   if (ctx->epi_counter.bytes < need) {
@@ -1259,7 +1237,7 @@ gvi_status run_chain(gvi_ctx* c, const ChainArgs& a0, const ChainArgs& a1, bool 
   hipStream_t st = c->stream;
   StageScope scope(c, STAGE_CHAIN);
   ChainSync sy;
-  if (c->chain_merge) {
+  if (c->opt.chain_merge) {
     constexpr unsigned RING = 64;
     if (!c->chain_sync.p) {
       HIPCK(c, c->chain_sync.ensure(RING * 2 * sizeof(unsigned)));
@@ -1271,7 +1249,7 @@ gvi_status run_chain(gvi_ctx* c, const ChainArgs& a0, const ChainArgs& a1, bool 
     if (++c->chain_seq == 0) ++c->chain_seq;       // 0 is the cleared state of a word
     sy.seq = c->chain_seq;
     sy.words = (unsigned*)c->chain_sync.p + 2 * (sy.seq % RING);
-    sy.fault = c->chain_merge_fault ? 0x40000000u : 0u;
+    sy.fault = c->opt.chain_merge_fault ? 0x40000000u : 0u;
   }
   const hipError_t e = chain_launch(c->n, chain_plan(c->T, c->n), a0, a1, on0, on1, st, AL, sy);
   if (e == hipErrorInvalidValue) return fail(c, GVI_ERR_UNSUPPORTED, "chain kernels: block size / LDS budget");
@@ -1346,24 +1324,7 @@ gvi_status gvi_ctx_create(int device, int dtype, gvi_ctx** out) {
   c->device = device; c->dtype = dtype;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
     return fail(nullptr, GVI_ERR_HIP, "hipStreamCreate failed");
-  if (const char* w = getenv("GVI_NO_SCOST")) c->no_scost = atoi(w) != 0;
-  if (const char* w = getenv("GVI_ORBIT")) c->orbit = atoi(w) != 0;
-  if (const char* w = getenv("GVI_FUSED")) c->fused = atoi(w) != 0;
-  if (const char* w = getenv("GVI_ASM_ON_LOAD")) c->asm_on_load = atoi(w) != 0;
-  if (const char* w = getenv("GVI_PIPELINE")) c->pipeline = atoi(w) != 0;
-  if (const char* w = getenv("GVI_CHAIN_WAVE")) chain_wave_enabled() = atoi(w) != 0;     // (process-wide: A/B leg of kernels_chain_wave.hpp)
-  if (const char* w = getenv("GVI_ASM_DENSE")) chain_asm_dense_enabled() = atoi(w) != 0;   // (process-wide: A/B leg of the batched first-pass load)
-  if (const char* w = getenv("GVI_CHAIN_PAIR")) chain_pair_enabled() = atoi(w) != 0;      // (process-wide: A/B leg of the row-broadcast eliminations)
-  if (const char* w = getenv("GVI_CHAIN_MERGE")) c->chain_merge = atoi(w) != 0;
-  if (const char* w = getenv("GVI_CHOL_ROWB")) c->chol_rowb = atoi(w) != 0;
-  if (const char* w = getenv("GVI_SREG_PIPE")) c->sreg_pipe = atoi(w) != 0;
-  if (const char* w = getenv("GVI_MIRROR")) c->mirror = atoi(w) != 0;
-  if (const char* w = getenv("GVI_NO_PAIR")) c->pair_fuse = atoi(w) == 0;
-  if (const char* w = getenv("GVI_NO_FUSE_GATHER")) c->fuse_gather = atoi(w) == 0;
-  if (const char* w = getenv("GVI_SIDE_SOLVE")) c->side_solve = atoi(w) != 0;
-  if (const char* w = getenv("GVI_FUSE_TRIAL")) c->fuse_trial = std::min(2, std::max(0, atoi(w)));
-  if (const char* w = getenv("GVI_SPIN_MS")) c->spin_ms = std::max(0, atoi(w));
-  if (const char* w = getenv("GVI_SAFE_PUBLISH")) c->safe_publish = atoi(w) != 0;
+  options_from_env(c->opt, getenv);
   if (hipHostMalloc((void**)&c->host_slot, 128, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
       hipHostGetDevicePointer((void**)&c->host_slot_dev, c->host_slot, 0) != hipSuccess)
     return fail(nullptr, GVI_ERR_HIP, "host-mapped slot allocation failed");
@@ -1478,89 +1439,22 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
       return fail(ctx, GVI_ERR_ARG, "start index out of range");
   int m = 0, seg_J = 0;
   int64_t need = 0;
-  switch (psi_kind) {
-    case GVI_PSI_RANGE_1D: if (d != 1) return fail(ctx, GVI_ERR_ARG, "RANGE_1D needs d == 1"); need = 5; break;
-    case GVI_PSI_QUAD_PRIOR: if (d % 2) return fail(ctx, GVI_ERR_ARG, "QUAD_PRIOR needs even d"); m = d / 2; need = 2 * (int64_t)m * m; break;
-    case GVI_PSI_FIXED_PRIOR: m = d; need = d + (int64_t)d * d; break;
-    case GVI_PSI_HOST_CALLBACK: need = 0; break;
-    case GVI_PSI_HINGE_SDF_2D: if (d < 2) return fail(ctx, GVI_ERR_ARG, "HINGE_SDF_2D needs d >= 2"); need = 3; break;
-    case GVI_PSI_HINGE_SDF_2D_BODY: if (d < 3) return fail(ctx, GVI_ERR_ARG, "HINGE_SDF_2D_BODY needs d >= 3"); need = 6; break;
-    case GVI_PSI_HINGE_SDF_3D: if (d < 3) return fail(ctx, GVI_ERR_ARG, "HINGE_SDF_3D needs d >= 3"); need = 3; break;
-    case GVI_PSI_HINGE_SDF_3D_ARM: need = 2; break;
-    case GVI_PSI_HINGE_SDF_2D_SEG:
-    case GVI_PSI_HINGE_SDF_3D_SEG: {
-      // J is a property of the set: params_per_factor = 3 + J P (d + 1), exactly
-      const int64_t per = (int64_t)(psi_kind == GVI_PSI_HINGE_SDF_2D_SEG ? 2 : 3) * (d + 1);
-      const int64_t body = params_per_factor - 3;
-      if (body < per || body % per != 0 || body / per > SEG_MAX_J)
-        return fail(ctx, GVI_ERR_ARG, "HINGE_SDF_*_SEG needs params_per_factor = 3 + J P (d + 1) with 1 <= J <= 8 check points "
-                                      "(P = 2 for _2D_SEG, 3 for _3D_SEG)");
-      seg_J = (int)(body / per);
-      need = params_per_factor;
-      break;
-    }
-    case GVI_PSI_HINGE_BOX:
-      if (params_per_factor != 4 * (int64_t)d) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX needs params_per_factor = 4 d: [sigma | eps | lo | hi]");
-      need = params_per_factor;
-      break;
-    case GVI_PSI_HINGE_HALFSPACE: {
-      // J is a property of the set: params_per_factor = J (d + 3), exactly
-      const int64_t per = (int64_t)d + 3;
-      if (params_per_factor < per || params_per_factor % per != 0 || params_per_factor / per > HALFSPACE_MAX_J)
-        return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE needs params_per_factor = J (d + 3) with 1 <= J <= 16 rows: [sigma (J) | eps (J) | b (J) | A (J x d)]");
-      seg_J = (int)(params_per_factor / per);
-      need = params_per_factor;
-      break;
-    }
-    default: return fail(ctx, GVI_ERR_ARG, "unknown psi kind");
-  }
-  if (need > 0 && (!psi_params || params_per_factor < need))
-    return fail(ctx, GVI_ERR_ARG, "psi_params missing or params_per_factor too small for this kind");
-  if (psi_kind == GVI_PSI_HINGE_BOX) {
-    for (int64_t k = 0; k < K; ++k) {
-      const double* P = psi_params + k * params_per_factor;
-      for (int i = 0; i < d; ++i) {
-        const double sg = P[i], ep = P[d + i], lo = P[2 * d + i], hi = P[3 * d + i];
-        if (!std::isfinite(sg) || sg < 0.0) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX: sigma must be finite and >= 0");
-        if (!std::isfinite(ep)) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX: eps must be finite");
-        if (std::isnan(lo) || std::isnan(hi)) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX: NaN limit");
-        if (!(lo < hi)) return fail(ctx, GVI_ERR_ARG, "HINGE_BOX: lo must be below hi (lo = -inf / hi = +inf switch a side off)");
-      }
-    }
-  }
-  if (psi_kind == GVI_PSI_HINGE_HALFSPACE) {
-    const int J = seg_J;
-    for (int64_t k = 0; k < K; ++k) {
-      const double* P = psi_params + k * params_per_factor;
-      for (int64_t e = 0; e < params_per_factor; ++e)
-        if (std::isnan(P[e])) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: NaN in the parameter block");
-      for (int j = 0; j < J; ++j) {
-        if (!std::isfinite(P[j]) || P[j] < 0.0) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: sigma must be finite and >= 0");
-        if (!std::isfinite(P[J + j])) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: eps must be finite");
-        if (!std::isfinite(P[2 * J + j])) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: b must be finite");
-        bool zero = true;
-        for (int i = 0; i < d; ++i) {
-          const double v = P[3 * J + (int64_t)j * d + i];
-          if (!std::isfinite(v)) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: A must be finite");
-          zero = zero && v == 0.0;
-        }
-        if (zero && P[j] > 0.0) return fail(ctx, GVI_ERR_ARG, "HINGE_HALFSPACE: an active row (sigma > 0) needs a non-zero normal a_j");
-      }
-    }
-  }
+  const char* why = nullptr;
+  if (gvi_status rc = psi_kind_layout(psi_kind, d, params_per_factor, &m, &seg_J, &need, &why)) return fail(ctx, rc, why);
+  if (gvi_status rc = psi_kind_check_params(psi_kind, d, seg_J, params_per_factor, K, psi_params, &why)) return fail(ctx, rc, why);
   HIPCK(ctx, hipSetDevice(ctx->device));
 
   std::unique_ptr<FactorSet> s(new FactorSet);
-  s->jtol = ctx->jacobi_tol;
-  s->use_chol = ctx->chol_sqrt;
+  s->jtol = ctx->opt.jacobi_tol;
+  s->use_chol = ctx->opt.chol_sqrt;
   s->unit_temperature = ctx->update_rule == GVI_RULE_PROX_JKO;    // the rule belongs to the context: a set takes it when it is added
   s->K = K; s->d = d; s->p = p; s->m = m; s->kind = psi_kind; s->seg_J = seg_J;
-  s->closed_form = psi_kind == GVI_PSI_HINGE_BOX || psi_kind == GVI_PSI_HINGE_HALFSPACE;      // exact and cheaper than any rule on the kink; gvi_factors_set_closed_form(.., 0) for the quadrature
+  s->closed_form = psi_kind_is<PSI_CLOSED_DEFAULT>(psi_kind);      // gvi_factors_set_closed_form(.., 0) for the quadrature
   if (K > 0) s->start.assign(start, start + K);
   // quadrature table: shared between sets with the same (d, p)
   if (tabZ) {
     auto t = std::make_shared<Table>();
-    GVICK(upload_table(ctx, *t, d, ctx->trust_table_degree ? p : -1, tabN, tabZ, tabw));
+    GVICK(upload_table(ctx, *t, d, ctx->opt.trust_table_degree ? p : -1, tabN, tabZ, tabw));
     s->table = t;
   }
   for (auto& t : ctx->tables) if (!s->table && t->d == d && t->p == p) s->table = t;
@@ -1574,22 +1468,23 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   }
   // psi operands
   std::vector<double> A((size_t)K * m * d, 0.0), b((size_t)K * m, 0.0), sg((size_t)K * m, 1.0);
-  if (psi_kind == GVI_PSI_QUAD_PRIOR || psi_kind == GVI_PSI_FIXED_PRIOR) {
+  if (psi_kind_is<PSI_SUMSQ>(psi_kind)) {
+    const bool quad = PSI_KINDS[psi_kind].rows == M_HALF_D;      // r = Phi x1 - x2 on [Phi | Qinv], else r = x - mu0 on [mu0 | Qinv]
     std::vector<double> Q, lam, W;
     for (int k = 0; k < K; ++k) {
       const double* P = psi_params + (size_t)k * params_per_factor;
-      const double* Qin = psi_kind == GVI_PSI_QUAD_PRIOR ? P + (size_t)m * m : P + d;
+      const double* Qin = quad ? P + (size_t)m * m : P + d;
       Q.assign((size_t)m * m, 0.0);
       for (int i = 0; i < m; ++i)
         for (int j = 0; j < m; ++j) Q[(size_t)i * m + j] = 0.5 * (Qin[i * m + j] + Qin[j * m + i]);
       jacobi_eigh(m, Q, lam, W);
       // psi = c * r^T Qinv r = sum_r sign(e_r) (sqrt(c |e_r|) w_r^T r)^2 ,  c = 1/2 (QUAD) or 1 (FIXED)
-      const double cfac = psi_kind == GVI_PSI_QUAD_PRIOR ? 0.5 : 1.0;
+      const double cfac = quad ? 0.5 : 1.0;
       for (int r = 0; r < m; ++r) {
         const double sc = std::sqrt(cfac * std::fabs(lam[r]));
         sg[(size_t)k * m + r] = lam[r] < 0 ? -1.0 : 1.0;
         double* Arow = &A[((size_t)k * m + r) * d];
-        if (psi_kind == GVI_PSI_QUAD_PRIOR) {      // r = Phi x1 - x2 = [Phi, -I] x
+        if (quad) {                                // r = Phi x1 - x2 = [Phi, -I] x
           for (int a = 0; a < m; ++a) {
             double acc = 0.0;
             for (int j = 0; j < m; ++j) acc += W[(size_t)j * m + r] * P[j * m + a];
@@ -1613,8 +1508,7 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   GVICK(up(s->b, b.data(), b.size() * 8));
   GVICK(up(s->sgn, sg.data(), sg.size() * 8));
   s->all_pos = std::all_of(sg.begin(), sg.end(), [](double v) { return v == 1.0; });
-  const bool raw_kind = psi_kind == GVI_PSI_RANGE_1D || sdf_kind(psi_kind) || psi_kind == GVI_PSI_HINGE_BOX || psi_kind == GVI_PSI_HINGE_HALFSPACE;
-  if (raw_kind) {                       // raw_stride = the kind's own block (_SEG kinds: 3 + J P (d + 1), HINGE_BOX: 4 d, HINGE_HALFSPACE: J (d + 3))
+  if (psi_kind_is<PSI_RAW>(psi_kind)) {                       // raw_stride = the kind's own block (_SEG kinds: 3 + J P (d + 1), HINGE_BOX: 4 d, HINGE_HALFSPACE: J (d + 3))
     const int np = (int)need;
     std::vector<double> raw((size_t)K * np);
     for (int k = 0; k < K; ++k) memcpy(&raw[(size_t)k * np], psi_params + (size_t)k * params_per_factor, (size_t)np * 8);
@@ -1687,9 +1581,7 @@ gvi_status gvi_factors_set_table(gvi_ctx* ctx, int set_id, int64_t N, const doub
   GVICK(upload_table(ctx, *t, s->d, -1, N, Z, w));
   s->table = t;
   s->prep_slot = -1;
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;   // cost / gradients of the old table are stale
-  ctx->ngd.grad_valid = false;
-  ctx->ngd.spec_ready = false;
+  ngd_invalidate(ctx);                // cost / gradients of the old table are stale
   return GVI_OK;
 }
 
@@ -1697,7 +1589,7 @@ gvi_status gvi_factors_set_sdf2d(gvi_ctx* ctx, int set_id, double origin_x, doub
                                  int cols, const double* data) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  if (s->kind != KIND_HINGE_SDF_2D && s->kind != KIND_HINGE_SDF_2D_BODY && s->kind != KIND_HINGE_SDF_2D_SEG)
+  if (!psi_kind_is<PSI_SDF_2D>(s->kind))
     return fail(ctx, GVI_ERR_ARG, "set is not GVI_PSI_HINGE_SDF_2D / _2D_BODY / _2D_SEG");
   if (rows < 2 || cols < 2 || !(cell_size > 0) || !data) return fail(ctx, GVI_ERR_ARG, "bad grid");
   HIPCK(ctx, hipSetDevice(ctx->device));
@@ -1705,8 +1597,7 @@ gvi_status gvi_factors_set_sdf2d(gvi_ctx* ctx, int set_id, double origin_x, doub
   HIPCK(ctx, s->sdf.ensure((size_t)rows * cols * 8));
   HIPCK(ctx, hipMemcpy(s->sdf.p, data, (size_t)rows * cols * 8, hipMemcpyHostToDevice));
   s->sdf_rows = rows; s->sdf_cols = cols; s->sdf_ox = origin_x; s->sdf_oy = origin_y; s->sdf_cell = cell_size;
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 
@@ -1714,7 +1605,7 @@ gvi_status gvi_factors_set_sdf3d(gvi_ctx* ctx, int set_id, const double* origin,
                                  int nz, const double* data) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  if (s->kind != KIND_HINGE_SDF_3D && s->kind != KIND_HINGE_SDF_3D_ARM && s->kind != KIND_HINGE_SDF_3D_SEG)
+  if (!psi_kind_is<PSI_SDF_3D>(s->kind))
     return fail(ctx, GVI_ERR_ARG, "set is not GVI_PSI_HINGE_SDF_3D / _3D_ARM / _3D_SEG");
   if (rows < 2 || cols < 2 || nz < 2 || !(cell_size > 0) || !data || !origin) return fail(ctx, GVI_ERR_ARG, "bad grid");
   HIPCK(ctx, hipSetDevice(ctx->device));
@@ -1724,8 +1615,7 @@ gvi_status gvi_factors_set_sdf3d(gvi_ctx* ctx, int set_id, const double* origin,
   HIPCK(ctx, hipMemcpy(s->sdf.p, data, bytes, hipMemcpyHostToDevice));
   s->sdf_rows = rows; s->sdf_cols = cols; s->sdf_nz = nz;
   s->sdf_ox = origin[0]; s->sdf_oy = origin[1]; s->sdf_oz = origin[2]; s->sdf_cell = cell_size;
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 
@@ -1734,7 +1624,7 @@ gvi_status gvi_factors_set_arm(gvi_ctx* ctx, int set_id, int ndof, const double*
                                const double* radii) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  if (s->kind != KIND_HINGE_SDF_3D_ARM) return fail(ctx, GVI_ERR_ARG, "set is not GVI_PSI_HINGE_SDF_3D_ARM");
+  if (!psi_kind_is<PSI_ARM>(s->kind)) return fail(ctx, GVI_ERR_ARG, "set is not GVI_PSI_HINGE_SDF_3D_ARM");
   if (ndof < 1 || ndof > s->d || nspheres < s->d || !a || !alpha || !d || !theta_bias || !frames || !centers || !radii)
     return fail(ctx, GVI_ERR_ARG, "bad arm model (need 1 <= ndof <= factor dimension <= nspheres: n_balls = factor dimension)");
   for (int q = 0; q < nspheres; ++q)
@@ -1752,20 +1642,18 @@ gvi_status gvi_factors_set_arm(gvi_ctx* ctx, int set_id, int ndof, const double*
   GVICK(sync(ctx));
   HIPCK(ctx, s->arm.ensure(pk.size() * 8));
   HIPCK(ctx, hipMemcpy(s->arm.p, pk.data(), pk.size() * 8, hipMemcpyHostToDevice));
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 
 gvi_status gvi_factors_set_closed_form(gvi_ctx* ctx, int set_id, int on) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
-  if (on && s->kind != KIND_QUAD_PRIOR && s->kind != KIND_FIXED_PRIOR && s->kind != KIND_HINGE_BOX && s->kind != KIND_HINGE_HALFSPACE)
+  if (on && !psi_kind_is<PSI_CLOSED>(s->kind))
     return fail(ctx, GVI_ERR_ARG, "closed form exists for QUAD_PRIOR / FIXED_PRIOR / HINGE_BOX / HINGE_HALFSPACE sets only");
   GVICK(sync(ctx));
   s->closed_form = on != 0;
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 
@@ -1775,8 +1663,7 @@ gvi_status gvi_factors_set_temperature(gvi_ctx* ctx, int set_id, const double* t
   HIPCK(ctx, hipSetDevice(ctx->device));
   GVICK(sync(ctx));
   HIPCK(ctx, hipMemcpy(s->temperature.p, temperature, (size_t)s->K * 8, hipMemcpyHostToDevice));
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 
@@ -1795,7 +1682,7 @@ gvi_status gvi_moments_dev(gvi_ctx* ctx, int set_id, const double* mu, const dou
                            double* Vdmu, double* Vddmu) {
   FactorSet* s = get_set(ctx, set_id);
   GVICK(check_pass_args(ctx, s, mu, Sigma));
-  if (s->kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_ARG, "HOST_CALLBACK set: use gvi_expand + gvi_moments_from_psi");
+  if (psi_kind_is<PSI_NO_DEVICE>(s->kind)) return fail(ctx, GVI_ERR_ARG, "HOST_CALLBACK set: use gvi_expand + gvi_moments_from_psi");
   HIPCK(ctx, hipSetDevice(ctx->device));
   GVICK(run_prep(ctx, *s, mu, Sigma));
   GVICK(run_moments(ctx, *s, mu, nullptr, 1));
@@ -1805,7 +1692,7 @@ gvi_status gvi_moments_dev(gvi_ctx* ctx, int set_id, const double* mu, const dou
 gvi_status gvi_costs_dev(gvi_ctx* ctx, int set_id, const double* mu, const double* Sigma, double* cost) {
   FactorSet* s = get_set(ctx, set_id);
   GVICK(check_pass_args(ctx, s, mu, Sigma));
-  if (s->kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_ARG, "HOST_CALLBACK set has no device psi");
+  if (psi_kind_is<PSI_NO_DEVICE>(s->kind)) return fail(ctx, GVI_ERR_ARG, "HOST_CALLBACK set has no device psi");
   HIPCK(ctx, hipSetDevice(ctx->device));
   GVICK(run_prep(ctx, *s, mu, Sigma));
   GVICK(run_moments(ctx, *s, mu, nullptr, 0));
@@ -1836,7 +1723,7 @@ gvi_status gvi_raw_moments(gvi_ctx* ctx, int set_id, const double* mu, const dou
                            double* E_xmuphi, double* E_xxphi) {
   FactorSet* s = get_set(ctx, set_id);
   GVICK(check_pass_args(ctx, s, mu, Sigma));
-  if (s->kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_ARG, "HOST_CALLBACK set has no device psi");
+  if (psi_kind_is<PSI_NO_DEVICE>(s->kind)) return fail(ctx, GVI_ERR_ARG, "HOST_CALLBACK set has no device psi");
   HIPCK(ctx, hipSetDevice(ctx->device));
   GVICK(upload_pass_inputs(ctx, s, mu, Sigma));
   HIPCK(ctx, s->raw1.ensure((size_t)s->K * s->d * 8));
@@ -2058,7 +1945,7 @@ static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
   int dmax = 0;
   bool all = true;
   for (auto& s : ctx->sets) {
-    if (s->kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_UNSUPPORTED, "resident NGD needs device psi kinds");
+    if (psi_kind_is<PSI_NO_DEVICE>(s->kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "resident NGD needs device psi kinds");
     if (s->prep_slot == i) { all = false; break; }
   }
   if (g.gpend[i].on && !all) GVICK(ngd_flush_gather(ctx, i));      // cannot happen (a pending gather resets every prep_slot)
@@ -2083,7 +1970,7 @@ static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
   const dim3 grid(L.koff[L.nsets] + extra);
   if (grid.x == 0) return GVI_OK;                                     // only empty shards
   if (dmax > 32) return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
-  if (ctx->chol_rowb) {
+  if (ctx->opt.chol_rowb) {
     if (dmax <= 8) hipLaunchKernelGGL((prep_all_kernel<1, true>), grid, dim3(64), lds, ctx->stream, L);
     else if (dmax <= 16) hipLaunchKernelGGL((prep_all_kernel<4, true>), grid, dim3(64), lds, ctx->stream, L);
     else hipLaunchKernelGGL((prep_all_kernel<16, true>), grid, dim3(64), lds, ctx->stream, L);
@@ -2173,7 +2060,7 @@ static gvi_status ngd_gather_now(gvi_ctx* ctx, int i, const double* mu_from, con
 // the same gather left to the prep launch of slot i that follows (trial state: a cost or full pass of the slot always does;
 // any other reader flushes it, ngd_flush_gather); option fuse_gather = 0: launched now
 static gvi_status ngd_gather_with_prep(gvi_ctx* ctx, int i, const double* mu_from, const double* dmu, double step) {
-  if (!ctx->fuse_gather || ctx->sets.empty()) return ngd_gather_now(ctx, i, mu_from, dmu, step);
+  if (!ctx->opt.fuse_gather || ctx->sets.empty()) return ngd_gather_now(ctx, i, mu_from, dmu, step);
   for (auto& s : ctx->sets) if (s->prep_slot == i) s->prep_slot = -1;
   ctx->ngd.gpend[i] = {true, mu_from, dmu, step};
   return GVI_OK;
@@ -2250,7 +2137,7 @@ static gvi_status ngd_cost_wait(gvi_ctx* ctx, int i, double* out, double seq_exp
   // window between two 8-byte loads
   const double* slot = ctx->host_slot + 4 * rg;
   typedef double v2d __attribute__((vector_size(16), aligned(16)));
-  const bool safe = ctx->safe_publish;
+  const bool safe = ctx->opt.safe_publish;
   auto poll = [&](double* val) {
     if (safe) {
       // checked form [sequence | value | value | sequence]: taken only when both sequence words and both copies agree
@@ -2274,7 +2161,7 @@ static gvi_status ngd_cost_wait(gvi_ctx* ctx, int i, double* out, double seq_exp
     if (poll(&v)) { seen = true; break; }
     cpu_relax();
     if ((spins & 1023) == 1023 &&
-        std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(ctx->spin_ms)) break;
+        std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(ctx->opt.spin_ms)) break;
   }
   if (!seen) {
     // long passes (config 5: seconds per pass): sleep-poll the word and, every millisecond, the stream itself, so a
@@ -2512,7 +2399,7 @@ static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full, const Mom
   MomPlan own[MAX_SETS];
   if (!P) { GVICK(plan_sets(ctx, slot, full, own)); P = own; }
   const size_t ns = ctx->sets.size();
-  const bool fuse = ctx->pair_fuse && !ctx->profile_all;
+  const bool fuse = ctx->opt.pair_fuse && !ctx->profile_all;
   if (fuse && ns == 2) {
     FactorSet &s0 = *ctx->sets[0], &s1 = *ctx->sets[1];
     const int smax = std::max(P[0].smax, P[1].smax);
@@ -2520,7 +2407,7 @@ static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full, const Mom
     if (P[0].route == Route::Orbit && P[1].route == Route::Orbit && s0.m == s1.m && s0.all_pos && s1.all_pos &&
         orbit_pair_supported(s0.m, smax)) {
       GVICK(prof_open(ctx, s0, 0, full != 0, false, ctx->stream, &b));
-      launch_orbit_pair(P[0].oa, P[1].oa, s0.m, smax, full != 0, ctx->stream, ctx->orbit_stack, b.e0, b.e1);
+      launch_orbit_pair(P[0].oa, P[1].oa, s0.m, smax, full != 0, ctx->stream, b.e0, b.e1);
       HIPCK(ctx, hipGetLastError());
       s0.fused_pair = s1.fused_pair = true;
       return prof_close(ctx, b);
@@ -2587,7 +2474,7 @@ static FusedKey fused_key(const gvi_ctx* ctx) {
 }
 
 static bool fused_ok(const gvi_ctx* ctx, int slot) {
-  if (!ctx->fused || !ctx->pair_fuse || ctx->profile_all || ctx->sets.empty() || ctx->sets.size() > 2) return false;
+  if (!ctx->opt.fused || !ctx->opt.pair_fuse || ctx->profile_all || ctx->sets.empty() || ctx->sets.size() > 2) return false;
   if (ctx->update_rule != GVI_RULE_NGD) return false;     // the JKO map reads the sets' Sigma^-1 after the pass
   const FusedKey k = fused_key(ctx);
   for (auto& sp : ctx->sets) {
@@ -2655,7 +2542,7 @@ static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot) {
 // caller takes the three launches, with the plans made here where *planned.
 static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, MomPlan* P, bool* planned, bool* done) {
   *done = *planned = false;
-  if (!ctx->fused || !ctx->pair_fuse || ctx->profile_all || !planar_shape(ctx)) return GVI_OK;
+  if (!ctx->opt.fused || !ctx->opt.pair_fuse || ctx->profile_all || !planar_shape(ctx)) return GVI_OK;
   if (ctx->update_rule != GVI_RULE_NGD) return GVI_OK;     // the JKO map reads the sets' Sigma^-1 after the pass
   FactorSet* ss[3] = {ctx->sets[0].get(), ctx->sets[1].get(), ctx->sets[2].get()};
   for (auto* q : ss)
@@ -2700,7 +2587,7 @@ static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, MomP
 static gvi_status ngd_moments_full(gvi_ctx* ctx, int slot, int publish_slot = -1) {
   if ((int)ctx->sets.size() > MAX_SETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
   for (auto& s : ctx->sets)
-    if (s->kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_UNSUPPORTED, "resident NGD needs device psi kinds");
+    if (psi_kind_is<PSI_NO_DEVICE>(s->kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "resident NGD needs device psi kinds");
   StageScope scope(ctx, STAGE_FACTORS);
   if (fused_ok(ctx, slot)) return ngd_fused_full(ctx, slot, publish_slot);
   MomPlan plans[MAX_SETS];
@@ -2714,12 +2601,12 @@ static gvi_status ngd_moments_full(gvi_ctx* ctx, int slot, int publish_slot = -1
 
 // the gradient solve is parked and goes out beside the next trial factorisation, as the dual launch (ngd_trial_state);
 // else (option side_solve = 0, a one-state chain) it is launched at once
-static bool dual_solve(const gvi_ctx* ctx) { return ctx->side_solve && chain_supported(ctx->n) && ctx->T > 1; }
+static bool dual_solve(const gvi_ctx* ctx) { return ctx->opt.side_solve && chain_supported(ctx->n) && ctx->T > 1; }
 
 // assemble-on-load applies: every set chain-structured, the solve of this buffer will go out through the dual launch (or
 // the flushing solve), nobody needs [g | V_D | V_U] in memory before that
 static bool asm_on_load_ok(const gvi_ctx* ctx) {
-  if (!ctx->asm_on_load || dist_on(ctx) || ctx->update_rule != GVI_RULE_NGD || ctx->sets.empty()) return false;
+  if (!ctx->opt.asm_on_load || dist_on(ctx) || ctx->update_rule != GVI_RULE_NGD || ctx->sets.empty()) return false;
   if (!dual_solve(ctx)) return false;
   for (auto& s : ctx->sets)
     if (!s->chain_structured && !(s->d == ctx->n && s->K <= ASM_SPARSE_MAX)) return false;    // (sparse unary sets: AsmSet::sp)
@@ -2969,7 +2856,7 @@ gvi_status gvi_ngd_accept(gvi_ctx* ctx) {
 static gvi_status ngd_iteration_entry(gvi_ctx* ctx, double* c0) {
   NgdState& g = ctx->ngd;
   const bool have_grad = g.grad_valid && g.grad_slot == g.cur;
-  if (!g.cost_valid[g.cur] && !have_grad && ctx->fuse_trial != 0 && !dist_on(ctx) && !ctx->sets.empty()) {
+  if (!g.cost_valid[g.cur] && !have_grad && ctx->opt.fuse_trial != 0 && !dist_on(ctx) && !ctx->sets.empty()) {
     ctx->ngd.solve_deferred[g.gcur] = false;
     GVICK(ngd_moments_full(ctx, g.cur, g.cur));          // epilogue + ordered cost sum + publish in one launch
     GVICK(ngd_scatter(ctx, g.cur, g.gcur));
@@ -2994,7 +2881,7 @@ static gvi_status ngd_linesearch(gvi_ctx* ctx, double c0, double step, int cnt, 
     const int t = 1 - g.cur;
     const bool spec = cnt == 0 && ctx->speculate;
     GVICK(ngd_trial_state(ctx, step));
-    const bool fuse = spec && (ctx->fuse_trial == 1 || (ctx->fuse_trial == 2 && ctx->ngd.last_first_accepted));
+    const bool fuse = spec && (ctx->opt.fuse_trial == 1 || (ctx->opt.fuse_trial == 2 && ctx->ngd.last_first_accepted));
     if (fuse) {
       // Fused form: ONE full moments pass at the trial point serves both the trial cost (its m0 column)
       // and -- if the trial is accepted -- the next iteration's gradients.  Same numbers, one psi pass
@@ -3109,11 +2996,11 @@ struct PipeWindowScope {
 // the prep launch with the fused gather + the sets' moments launches (every MomArgs / OrbitArgs kernel) + the epilogue with its
 // tail, the assemble
 bool pipe_ok(const gvi_ctx* c) {
-  if (!c->pipeline || dist_on(c) || c->update_rule != GVI_RULE_NGD || !c->speculate || c->fuse_trial == 0) return false;
+  if (!c->opt.pipeline || dist_on(c) || c->update_rule != GVI_RULE_NGD || !c->speculate || c->opt.fuse_trial == 0) return false;
   if (!dual_solve(c)) return false;
-  if (!c->fuse_gather || !c->pair_fuse || c->profile_all || c->sets.empty() || (int)c->sets.size() > MAX_SETS) return false;
+  if (!c->opt.fuse_gather || !c->opt.pair_fuse || c->profile_all || c->sets.empty() || (int)c->sets.size() > MAX_SETS) return false;
   for (const auto& s : c->sets)
-    if (s->K <= 0 || s->kind == KIND_HOST_CALLBACK) return false;       // (host-evaluated psi: the host is in the loop anyway)
+    if (s->K <= 0 || psi_kind_is<PSI_NO_DEVICE>(s->kind)) return false;       // (host-evaluated psi: the host is in the loop anyway)
   return true;
 }
 }  // namespace
@@ -3163,7 +3050,7 @@ gvi_status gvi_ngd_run(gvi_ctx* ctx, int max_iters, double step_size_base, int m
   int pend_ring = 0;
   const double step1 = step_size_base * 0.75;
   while (done < max_iters) {
-    const bool fused_first = ctx->fuse_trial == 1 || (ctx->fuse_trial == 2 && g.last_first_accepted);
+    const bool fused_first = ctx->opt.fuse_trial == 1 || (ctx->opt.fuse_trial == 2 && g.last_first_accepted);
     if (!pending && !(pipe_ok(ctx) && fused_first)) {
       if (!plain_iteration()) return finish(plain_st);
       continue;
@@ -3247,8 +3134,7 @@ gvi_status gvi_ngd_set_update_rule(gvi_ctx* ctx, int rule) {
   GVICK(sync(ctx));
   ctx->update_rule = rule;
   for (auto& s : ctx->sets) { s->unit_temperature = rule == GVI_RULE_PROX_JKO; s->prep_slot = -1; }
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 
@@ -3337,7 +3223,7 @@ gvi_status gvi_ngd_set_mode(gvi_ctx* ctx, int speculate, int fuse_trial) {
   if (!ctx) return GVI_ERR_ARG;
   if (fuse_trial < 0 || fuse_trial > 2) return fail(ctx, GVI_ERR_ARG, "fuse_trial must be 0, 1 or 2");
   ctx->speculate = speculate != 0;
-  ctx->fuse_trial = fuse_trial;
+  ctx->opt.fuse_trial = fuse_trial;
   ctx->ngd.last_first_accepted = true;
   return GVI_OK;
 }
@@ -3401,8 +3287,7 @@ gvi_status gvi_dist_init_rccl(gvi_ctx* ctx, int rank, int world, const void* id1
   d.rank = rank; d.world = world; d.fn = nullptr; d.user = nullptr;
   d.rccl_lib = r.lib; d.comm = comm; d.ncclAllGather = r.AllGather; d.ncclCommDestroy = r.CommDestroy;
   d.ranges_valid = false;
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 
@@ -3413,8 +3298,7 @@ gvi_status gvi_dist_init_callback(gvi_ctx* ctx, int rank, int world, gvi_allgath
   if (d.comm && d.ncclCommDestroy) { d.ncclCommDestroy(d.comm); d.comm = nullptr; }
   d.rank = rank; d.world = world; d.fn = fn; d.user = user;
   d.ranges_valid = false;
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 
@@ -3558,49 +3442,14 @@ gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value) {
   if (!ctx || !name) return GVI_ERR_ARG;
   const std::string n(name);
   if (ctx->ngd.ready) { GVICK(ngd_flush_assemble(ctx, 0)); GVICK(ngd_flush_assemble(ctx, 1)); }
-  if (n == "split_flush") ctx->split_flush = std::max(0, value);
-  else if (n == "sreg_pipe") ctx->sreg_pipe = value != 0;
-  else if (n == "mirror") ctx->mirror = value != 0;
-  else if (n == "pair_fuse") ctx->pair_fuse = value != 0;
-  else if (n == "fuse_gather") ctx->fuse_gather = value != 0;
-  else if (n == "side_solve") ctx->side_solve = value != 0;
-  else if (n == "warm_start") ctx->warm_start = value != 0;
-  else if (n == "no_scost") ctx->no_scost = value != 0;
-  else if (n == "target_waves") ctx->target_waves = std::max(1, value);
-  else if (n == "orbit") ctx->orbit = value != 0;
-  else if (n == "fused") ctx->fused = value != 0;
-  else if (n == "assemble_on_load") ctx->asm_on_load = value != 0;
-  else if (n == "pipeline") ctx->pipeline = value != 0;
-  else if (n == "chain_wave") chain_wave_enabled() = value != 0;
-  else if (n == "asm_dense") chain_asm_dense_enabled() = value != 0;
-  else if (n == "chain_pair") chain_pair_enabled() = value != 0;
-  else if (n == "sample_sweep") ctx->post.sample_sweep = value != 0;
-  else if (n == "solve_lds") ctx->post.solve_lds = value != 0;
-  else if (n == "chain_merge") { ctx->chain_merge = value != 0; ctx->chain_merge_fault = value == 2; }
-  else if (n == "trust_table_degree") ctx->trust_table_degree = value != 0;
-  else if (n == "safe_publish") {
-    GVICK(sync(ctx));
-    ctx->safe_publish = value != 0;
-    for (int q = 0; q < 16; ++q) ctx->host_slot[q] = 0.0;       // the two forms lay the slot out differently
-  }
-  else if (n == "chol_sqrt") { ctx->chol_sqrt = value != 0; for (auto& s : ctx->sets) s->use_chol = ctx->chol_sqrt; }
-  else if (n == "chol_rowb") ctx->chol_rowb = value != 0;
-  else if (n == "jacobi_tol_exp") {
-    // the threshold compares SQUARED off-diagonal mass with squared diagonal mass: anything looser than 1e-20 (1e-10 relative)
-    // would break the 1e-9 operator parity, so it is refused rather than silently clamped
-    if (value > -20) return fail(ctx, GVI_ERR_ARG, "jacobi_tol_exp must be <= -20 (threshold 10^value on squared magnitudes)");
-    ctx->jacobi_tol = std::pow(10.0, (double)value);
-    for (auto& s : ctx->sets) s->jtol = ctx->jacobi_tol;
-  }
-  else if (n == "orbit_waves") ctx->orbit_waves = std::max(1, value);
-  else if (n == "orbit_min_tiles") ctx->orbit_min_tiles = std::max(1, value);
-  else if (n == "orbit_stack") ctx->orbit_stack = value != 0;
-  else if (n == "orbit_copies") ctx->orbit_copies = std::min(16, std::max(1, value));
-  else return fail(ctx, GVI_ERR_ARG, "unknown option: " + n);
-  for (auto& s : ctx->sets) s->prep_slot = -1;
-  ctx->ngd.cost_valid[0] = ctx->ngd.cost_valid[1] = false;
-  ctx->ngd.grad_valid = false;
-  ctx->ngd.spec_ready = false;
+  if (n == "safe_publish") GVICK(sync(ctx));                   // nothing in flight publishes in the other form
+  std::string why;
+  if (!option_set(ctx->opt, name, value, &why)) return fail(ctx, GVI_ERR_ARG, why);
+  // what a switch owes the context beyond its field
+  if (n == "safe_publish") for (int q = 0; q < 16; ++q) ctx->host_slot[q] = 0.0;       // the two forms lay the slot out differently
+  if (n == "chain_merge") ctx->opt.chain_merge_fault = value == 2;
+  for (auto& s : ctx->sets) { s->use_chol = ctx->opt.chol_sqrt; s->jtol = ctx->opt.jacobi_tol; s->prep_slot = -1; }
+  ngd_invalidate(ctx);
   return GVI_OK;
 }
 

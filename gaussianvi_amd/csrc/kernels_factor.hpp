@@ -38,15 +38,9 @@
 #include "device_common.hpp"
 #include "dpp_rowb.hpp"
 #include "halfspace_moments.hpp"
+#include "psi_kinds.hpp"
 
 namespace gvi {
-
-enum { KIND_RANGE_1D = 0, KIND_QUAD_PRIOR = 1, KIND_FIXED_PRIOR = 2, KIND_HOST_CALLBACK = 3, KIND_HINGE_SDF_2D = 4,
-       KIND_HINGE_SDF_2D_BODY = 5, KIND_HINGE_SDF_3D = 6, KIND_HINGE_SDF_3D_ARM = 7, KIND_HINGE_SDF_2D_SEG = 8,
-       KIND_HINGE_SDF_3D_SEG = 9, KIND_HINGE_BOX = 10, KIND_HINGE_HALFSPACE = 11 };
-
-constexpr int SEG_MAX_J = 8;   // check points of one HINGE_SDF_*_SEG factor
-constexpr int HALFSPACE_MAX_J = 16;   // rows of one HINGE_HALFSPACE factor
 
 __host__ __device__ inline int npairs(int d) { return (d + 1) * (d + 2) / 2; }
 
@@ -1026,42 +1020,41 @@ __device__ inline double psi_hinge_sdf3d_seg(const FactorDev& f, const double* p
   return cost;
 }
 
-// psi and / or clearance of factor k of a hinge-on-SDF, HINGE_BOX or HINGE_HALFSPACE set at the state slice x [d].  psi is the kind's
-// psi_* function; the clearance walks the same *_points with a min-visitor.  eps and slope play no part in the clearance.
+// psi of factor k of a set that keeps its raw parameter block (PSI_RAW, psi_kinds.hpp) at the state slice x [d]: THE chain
+// from a kind to its psi_* function.  NaN for a kind without raw psi (sum of squares: the caller's (A, b, sgn) form; host psi).
+__device__ __forceinline__ double psi_point(const FactorDev& f, int k, const double* x) {
+  const double* p = f.raw + (size_t)k * f.raw_stride;
+  if (f.kind == KIND_RANGE_1D) return psi_range_1d(p, x[0]);
+  if (f.kind == KIND_HINGE_SDF_2D) return psi_hinge_sdf2d(f, p, x[0], x[1]);
+  if (f.kind == KIND_HINGE_SDF_2D_BODY) return psi_hinge_sdf2d_body(f, p, x[0], x[1], x[2]);
+  if (f.kind == KIND_HINGE_SDF_3D) return psi_hinge_sdf3d(f, p, x[0], x[1], x[2]);
+  if (f.kind == KIND_HINGE_SDF_3D_ARM) return psi_hinge_sdf3d_arm(f, p, x, f.d);
+  if (f.kind == KIND_HINGE_SDF_2D_SEG) return psi_hinge_sdf2d_seg(f, p, x, f.d);
+  if (f.kind == KIND_HINGE_SDF_3D_SEG) return psi_hinge_sdf3d_seg(f, p, x, f.d);
+  if (f.kind == KIND_HINGE_BOX) return psi_hinge_box(p, x, f.d);
+  if (f.kind == KIND_HINGE_HALFSPACE) return psi_hinge_halfspace(p, x, f.d, f.seg_J);
+  return __builtin_nan("");
+}
+
+// psi and / or clearance of factor k of a raw-block set at the state slice x [d].  psi is psi_point; the clearance (PSI_CLEARANCE
+// kinds) walks the same *_points as the kind's psi with a min-visitor.  eps and slope play no part in the clearance.
 __device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, const double* x, bool want_psi, bool want_clr,
                                                     double& psi, double& clr) {
+  if (want_psi) psi = psi_point(f, k, x);
+  if (!want_clr) return;
   const double* p = f.raw + (size_t)k * f.raw_stride;
   double c = __builtin_inf();
   auto keep = [&](double sd, double r) { c = fmin(c, sd - r); };
-  if (f.kind == KIND_HINGE_SDF_2D) {
-    if (want_psi) psi = psi_hinge_sdf2d(f, p, x[0], x[1]);
-    if (want_clr) hinge_sdf2d_points(f, p, x[0], x[1], keep);
-  } else if (f.kind == KIND_HINGE_SDF_2D_BODY) {
-    if (want_psi) psi = psi_hinge_sdf2d_body(f, p, x[0], x[1], x[2]);
-    if (want_clr) hinge_sdf2d_body_points(f, p, x[0], x[1], x[2], keep);
-  } else if (f.kind == KIND_HINGE_SDF_3D) {
-    if (want_psi) psi = psi_hinge_sdf3d(f, p, x[0], x[1], x[2]);
-    if (want_clr) hinge_sdf3d_points(f, p, x[0], x[1], x[2], keep);
-  } else if (f.kind == KIND_HINGE_SDF_3D_ARM) {
-    if (want_psi) psi = psi_hinge_sdf3d_arm(f, p, x, f.d);
-    if (want_clr) hinge_sdf3d_arm_points(f, x, f.d, keep);
-  } else if (f.kind == KIND_HINGE_SDF_2D_SEG) {
-    if (want_psi) psi = psi_hinge_sdf2d_seg(f, p, x, f.d);
-    if (want_clr) hinge_sdf2d_seg_points(f, p, x, f.d, keep);
-  } else if (f.kind == KIND_HINGE_SDF_3D_SEG) {
-    if (want_psi) psi = psi_hinge_sdf3d_seg(f, p, x, f.d);
-    if (want_clr) hinge_sdf3d_seg_points(f, p, x, f.d, keep);
-  } else if (f.kind == KIND_HINGE_BOX) {      // limits on the slice itself (box_moments.hpp): the clearance is the margin
-    if (want_psi) psi = psi_hinge_box(p, x, f.d);
-    if (want_clr) c = box_margin(p, x, f.d);
-  } else if (f.kind == KIND_HINGE_HALFSPACE) {      // rows a_j^T x <= b_j (halfspace_moments.hpp): distance to the nearest active face
-    if (want_psi) psi = psi_hinge_halfspace(p, x, f.d, f.seg_J);
-    if (want_clr) c = halfspace_margin(p, x, f.d, f.seg_J);
-  } else {                      // no clearance for this kind: the host refuses such a set before any launch
-    if (want_psi) psi = __builtin_nan("");
-    c = __builtin_nan("");
-  }
-  if (want_clr) clr = c;
+  if (f.kind == KIND_HINGE_SDF_2D) hinge_sdf2d_points(f, p, x[0], x[1], keep);
+  else if (f.kind == KIND_HINGE_SDF_2D_BODY) hinge_sdf2d_body_points(f, p, x[0], x[1], x[2], keep);
+  else if (f.kind == KIND_HINGE_SDF_3D) hinge_sdf3d_points(f, p, x[0], x[1], x[2], keep);
+  else if (f.kind == KIND_HINGE_SDF_3D_ARM) hinge_sdf3d_arm_points(f, x, f.d, keep);
+  else if (f.kind == KIND_HINGE_SDF_2D_SEG) hinge_sdf2d_seg_points(f, p, x, f.d, keep);
+  else if (f.kind == KIND_HINGE_SDF_3D_SEG) hinge_sdf3d_seg_points(f, p, x, f.d, keep);
+  else if (f.kind == KIND_HINGE_BOX) c = box_margin(p, x, f.d);                        // limits on the slice itself (box_moments.hpp): the margin
+  else if (f.kind == KIND_HINGE_HALFSPACE) c = halfspace_margin(p, x, f.d, f.seg_J);   // rows a_j^T x <= b_j (halfspace_moments.hpp): distance to the nearest active face
+  else c = __builtin_nan("");   // no clearance for this kind: the host refuses such a set before any launch
+  clr = c;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1313,15 +1306,7 @@ __global__ __launch_bounds__(GEN_BS) void moments_generic_kernel(MomArgs a) {
         xr[r] = x;
       }
       if (a.psi_ext) psi = a.psi_ext[(size_t)k * f.N + i];
-      else if (f.kind == KIND_RANGE_1D) psi = psi_range_1d(f.raw + (size_t)k * f.raw_stride, xr[0]);
-      else if (f.kind == KIND_HINGE_SDF_2D) psi = psi_hinge_sdf2d(f, f.raw + (size_t)k * f.raw_stride, xr[0], xr[1]);
-      else if (f.kind == KIND_HINGE_SDF_2D_BODY) psi = psi_hinge_sdf2d_body(f, f.raw + (size_t)k * f.raw_stride, xr[0], xr[1], xr[2]);
-      else if (f.kind == KIND_HINGE_SDF_3D) psi = psi_hinge_sdf3d(f, f.raw + (size_t)k * f.raw_stride, xr[0], xr[1], xr[2]);
-      else if (f.kind == KIND_HINGE_SDF_3D_ARM) psi = psi_hinge_sdf3d_arm(f, f.raw + (size_t)k * f.raw_stride, xr, d);
-      else if (f.kind == KIND_HINGE_SDF_2D_SEG) psi = psi_hinge_sdf2d_seg(f, f.raw + (size_t)k * f.raw_stride, xr, d);
-      else if (f.kind == KIND_HINGE_SDF_3D_SEG) psi = psi_hinge_sdf3d_seg(f, f.raw + (size_t)k * f.raw_stride, xr, d);
-      else if (f.kind == KIND_HINGE_BOX) psi = psi_hinge_box(f.raw + (size_t)k * f.raw_stride, xr, d);
-      else if (f.kind == KIND_HINGE_HALFSPACE) psi = psi_hinge_halfspace(f.raw + (size_t)k * f.raw_stride, xr, d, f.seg_J);
+      else if (psi_kind_is<PSI_RAW>(f.kind)) psi = psi_point(f, k, xr);
       else {
         for (int r = 0; r < m; ++r) {
           double u = bsh[r];

@@ -48,7 +48,6 @@ struct SampleCostList {
 };
 static_assert(sizeof(SampleCostList) <= 4096, "kernel arguments");
 
-__host__ __device__ inline bool scost_sumsq(int kind) { return kind == KIND_QUAD_PRIOR || kind == KIND_FIXED_PRIOR; }
 __host__ __device__ inline int scost_group(int m) { int P = 1; while (P < m) P <<= 1; return P; }
 
 __device__ __forceinline__ bool scost_finite(double v) { return fabs(v) < __builtin_inf(); }   // false for NaN
@@ -106,10 +105,7 @@ __device__ __forceinline__ void scost_point_body(const SampleCostList& L, const 
   double* cost = L.cost[si];
   double* clr = L.clr[si];
   double psi = __builtin_nan(""), cl = __builtin_nan("");
-  if (fin) {
-    if (f.kind == KIND_RANGE_1D) psi = psi_range_1d(f.raw + (size_t)k * f.raw_stride, xs[0]);
-    else hinge_psi_clearance(f, k, xs, cost != nullptr, clr != nullptr, psi, cl);
-  }
+  if (fin) hinge_psi_clearance(f, k, xs, cost != nullptr, clr != nullptr, psi, cl);
   if (cost) cost[s * L.ld_cost[si] + k] = psi / f.temperature[k];
   if (clr) clr[s * L.ld_clr[si] + k] = cl;
 }
@@ -119,7 +115,7 @@ __global__ __launch_bounds__(SCOST_THREADS) void sample_cost_kernel(SampleCostLi
   int si = 0;
   while (si + 1 < L.nsets && (int)blockIdx.x >= L.boff[si + 1]) ++si;
   const int blk = (int)blockIdx.x - L.boff[si];
-  if (!scost_sumsq(L.f[si].kind)) { scost_point_body(L, si, blk); return; }
+  if (!psi_kind_is<PSI_SUMSQ>(L.f[si].kind)) { scost_point_body(L, si, blk); return; }
   if constexpr (NM >= 8) {
     if (2 * L.f[si].d <= NM) { scost_sumsq_body<NM / 2>(L, si, blk); return; }   // the unary set beside a binary one
   }

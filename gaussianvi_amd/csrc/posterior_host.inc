@@ -11,17 +11,13 @@ static const char MSG_NMAX[] = "state_dim > 16";
 static_assert(SAMPLE_NMAX == 16 && SOLVE_NMAX == 16 && INTERP_NMAX == 16, "one state_dim rule for every query");
 
 // ---- the check order ----
-// kinds with a clearance: the hinge-on-SDF kinds (sdf_kind: they need a grid), HINGE_BOX, whose clearance is the margin to its limits,
-// and HINGE_HALFSPACE, whose clearance is the distance to the nearest active face
-static bool clearance_kind(int kind) { return sdf_kind(kind) || kind == KIND_HINGE_BOX || kind == KIND_HINGE_HALFSPACE; }
-
 static gvi_status scost_check_set(gvi_ctx* ctx, const FactorSet& s, bool clearance) {
-  if (s.kind == KIND_HOST_CALLBACK) return fail(ctx, GVI_ERR_UNSUPPORTED, "a PSI_HOST_CALLBACK set has no device psi");
-  if (clearance && !clearance_kind(s.kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "clearance needs a hinge-on-SDF set");   // text kept for its callers; HINGE_BOX and HINGE_HALFSPACE sets pass too
-  if (scost_sumsq(s.kind) && s.d > SCOST_DMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
-  if (s.kind == KIND_HINGE_SDF_3D_ARM && !s.arm.p)
+  if (psi_kind_is<PSI_NO_DEVICE>(s.kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "a PSI_HOST_CALLBACK set has no device psi");
+  if (clearance && !psi_kind_is<PSI_CLEARANCE>(s.kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "clearance needs a hinge-on-SDF set");   // text kept for its callers; HINGE_BOX and HINGE_HALFSPACE sets pass too
+  if (psi_kind_is<PSI_SUMSQ>(s.kind) && s.d > SCOST_DMAX) return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
+  if (psi_kind_is<PSI_ARM>(s.kind) && !s.arm.p)
     return fail(ctx, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");
-  if (sdf_kind(s.kind) && s.sdf_rows == 0)
+  if (psi_kind_is<PSI_SDF>(s.kind) && s.sdf_rows == 0)
     return fail(ctx, GVI_ERR_STATE, "HINGE_SDF set without a grid: call gvi_factors_set_sdf2d / gvi_factors_set_sdf3d");
   return GVI_OK;
 }
@@ -154,7 +150,7 @@ static gvi_status run_sample(gvi_ctx* c, const double* D, const double* U, const
   const int T = c->T, n = c->n;
   SampleFactorArgs fa;
   GVICK(run_sample_factor(c, D, U, fa));
-  if (!c->post.sample_sweep) return GVI_OK;
+  if (!c->opt.sample_sweep) return GVI_OK;
   const SweepPlan p = sweep_plan(S, T, n, true);
   SampleSweepArgs sa{};
   sa.T = T; sa.n = n; sa.L = fa.L; sa.S = S; sa.seed = seed; sa.first = first; sa.eps = eps;
@@ -260,8 +256,8 @@ static gvi_status run_solve(gvi_ctx* c, const double* D, const double* U, int R,
   const int T = c->T, n = c->n;
   SampleFactorArgs fa;
   GVICK(run_sample_factor(c, D, U, fa));
-  if (!c->post.sample_sweep) return GVI_OK;
-  const SweepPlan p = sweep_plan(R, T, n, c->post.solve_lds);
+  if (!c->opt.sample_sweep) return GVI_OK;
+  const SweepPlan p = sweep_plan(R, T, n, c->opt.solve_lds);
   SolveSweepArgs sa{};
   sa.T = T; sa.n = n; sa.L = fa.L; sa.R = R; sa.B = B; sa.nodes = nodes;
   sa.Rf = fa.R; sa.GA = fa.GA; sa.GB = fa.GB; sa.hld = fa.hld; sa.X = X; sa.tile = p.tile;
@@ -470,7 +466,7 @@ static gvi_status ngd_sample_interp(gvi_ctx* ctx, int S, uint64_t seed, uint64_t
   else if (!X) GVICK(carve(ctx, ctx->post.smp_io, {{&dX, SX}}));
   const Resident r = resident(ctx);
   GVICK(run_sample(ctx, r.D, r.U, r.mu, S, seed, first, nullptr, dX));
-  if (!ctx->post.sample_sweep) return host ? sync(ctx) : GVI_OK;
+  if (!ctx->opt.sample_sweep) return host ? sync(ctx) : GVI_OK;
   GVICK(run_interp_sweep(ctx, S, dX, noise_seed, first, nullptr, dXq));
   return host ? copy_out(ctx, {{X, dX, SX}, {Xq, dXq, SQ}}) : GVI_OK;
 }
@@ -509,7 +505,7 @@ static gvi_status run_sample_cost(gvi_ctx* c, int lo, int hi, int S, const doubl
     L.f[j] = s.dev(); L.start[j] = s.dstart.i();
     L.cost[j] = cp; L.clr[j] = kp; L.ld_cost[j] = ld; L.ld_clr[j] = ld_clr;
     L.boff[j] = (int)nb;
-    if (scost_sumsq(s.kind)) {
+    if (psi_kind_is<PSI_SUMSQ>(s.kind)) {
       // tiles of 4 G factors; the samples are cut into chunks only as far as the grid needs them (a block loads its rows of A once)
       const int F = SCOST_WAVES * (64 / scost_group(s.m));
       const int ft = (s.K + F - 1) / F;
@@ -635,7 +631,7 @@ static gvi_status ngd_sample_costs(gvi_ctx* ctx, int S, uint64_t seed, int64_t f
   double* dc = cs < 0 ? nullptr : host ? w.clr : clr_min;
   const Resident r = resident(ctx);
   GVICK(run_sample(ctx, r.D, r.U, r.mu, S, seed, first, nullptr, dX));
-  if (!ctx->post.sample_sweep) return host ? sync(ctx) : GVI_OK;
+  if (!ctx->opt.sample_sweep) return host ? sync(ctx) : GVI_OK;
   GVICK(run_sample_costs_total(ctx, S, dX, dJ, cs, dc, w));
   if (dl) GVICK(run_logpdf(ctx, r.D, r.U, r.mu, S, dX, w.Q, w.hld, dl));
   if (!host) return GVI_OK;

@@ -531,8 +531,9 @@ gvi_status gvi_debug_products(gvi_ctx* ctx, int set_id, double* S, double* Sinv,
 gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
 /* ---- A/B switches: the complete list ----
  * Environment variables are read ONCE, at gvi_ctx_create (GVI_SPGH_EXTENDED at table generation, GVI_RCCL_PATH when
- * librccl is loaded); everything else is a run-time option of gvi_set_option.  Every switch below is exercised by a test
- * or by an A/B leg of tools/gpu_legs.sh; results are identical in every setting unless the last column says otherwise.
+ * librccl is loaded); everything else is a run-time option of gvi_set_option.  The rows are those of the one table in
+ * gaussianvi_amd/csrc/options.hpp (tests/test_options_host.py compares the two lists); an environment name that is not
+ * below is not read.  Results are identical in every setting unless the last column says otherwise.
  *
  *   environment          option              default  what                                                   results
  *   GVI_ORBIT            orbit               1        sign-orbit psi kernel (0: lane-per-point kernels)      agree to 1e-10
@@ -569,7 +570,7 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  *                                                     the output buffer whatever the size)
  *   --                   trust_table_degree  0        gvi_factors_add_table: the table is the rule of degree p  --
  *   --                   jacobi_tol_exp      -34      stopping threshold of the symmetric-root solve         rounding
- *   --                   split_flush, target_waves, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, warm_start:
+ *   --                   split_flush, target_waves, orbit_waves, orbit_min_tiles, orbit_copies, warm_start:
  *                        launch geometry / summation order of individual kernels (tests/test_gpu_parity.py A/Bs)
  * Build-time only: GVI_FUSED_TIMING (phase stamps; GVI_FUSED_DBG=8 prints them), built beside the in-tree library by
  * tools/build_variant.py and selected with GVI_LIB_PATH (the in-tree library is always built without defines).
@@ -589,7 +590,7 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * "fused" (1: the full moments pass of the resident iteration is ONE launch per pass -- gather, per-pass products, psi walk, chunk
  * sum, cost and back-transform of a factor in one workgroup; 0: the three launches prep -> psi -> epilogue),
  * "jacobi_tol_exp" (stopping threshold 10^value of the symmetric-root solve, on SQUARED off-diagonal / diagonal mass; values
- * above -20 return GVI_ERR_ARG -- the environment form GVI_JACOBI_TOL_EXP clamps to -20 instead).
+ * above -20 return GVI_ERR_ARG).
  * chain_wave (default 1; process-wide, environment GVI_CHAIN_WAVE): chains of T <= 65 states of size n <= 2 run on the
  * lane-per-node kernel (one wave per chain operation) instead of the generic block-cyclic-reduction kernels.
  * asm_dense (default 1; process-wide, environment GVI_ASM_DENSE): an assemble-on-load over at most one binary (d = 2n) and one
@@ -612,7 +613,7 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * the A/B leg of the fused route).  The option selects it for the three-launch route's prep launch too (an instance of its own),
  * where it measured slower than v_readlane: there it is the bitwise A/B of the two forms inside one library.
  * Names: chol_rowb, split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, warm_start, no_scost, target_waves,
- * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_stack, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge, asm_dense, chain_pair,
+ * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge, asm_dense, chain_pair,
  * trust_table_degree, safe_publish, sample_sweep, solve_lds. */
 gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value);
 

@@ -254,8 +254,60 @@ def test_split_form_calls_equal_the_step(name):
     assert same_bits(want_grad, got_grad)
 
 
+GVI_ERR_STATE = 5
+
+
+def prior_set(name):
+    return next(i for i, spec in enumerate(graph(name)["specs"]) if spec["kind"] == api.PSI_QUAD_PRIOR)
+
+
+# setters that mark the costs and gradients of the resident iteration stale (the full list: DESIGN.md section 4.5)
+SETTERS = {
+    "temperature": lambda ctx: ctx.factors_set_temperature(prior_set("c2"), np.full(ctx.sets[prior_set("c2")][0], 2.0)),
+    "closed_form": lambda ctx: ctx.factors_set_closed_form(prior_set("c2"), False),
+    "option_mirror": lambda ctx: ctx.set_option("mirror", 1),
+}
+
+
+@pytest.mark.parametrize("setter", sorted(SETTERS))
+def test_a_setter_drops_the_speculative_gradients(setter):
+    """Gradients queued at the trial state were computed under the old setting: after a setter gvi_ngd_accept_spec refuses
+    them (GVI_ERR_STATE), gvi_ngd_accept still takes the trial, and the iteration goes on exactly as on a context that never
+    speculated and had the setter applied at the same point."""
+    first = 0.75 * 0.55
+    ctx = fresh_context("c2", mode=(1, 0))
+    c0 = ctx.ngd_cost()
+    ctx.ngd_gradients()
+    ctx.ngd_trial_local(first)
+    ctx.ngd_trial_publish()
+    ctx.ngd_spec_gradients_local()
+    ctx.ngd_spec_gradients_finish()
+    c1 = ctx.ngd_trial_wait()
+    assert c1 < c0
+    SETTERS[setter](ctx)
+    with pytest.raises(api.GviError, match="no speculative gradients at the trial state") as e:
+        ctx.ngd_accept_spec()
+    assert e.value.status == GVI_ERR_STATE
+    ctx.ngd_accept()
+    got, got_state = ctx.ngd_step(0.55), ctx.ngd_get_state()
+    ctx.close()
+
+    ctx = fresh_context("c2", mode=(1, 0))
+    assert ctx.ngd_cost() == c0
+    ctx.ngd_gradients()
+    assert ctx.ngd_trial(first) == c1
+    SETTERS[setter](ctx)
+    ctx.ngd_accept()
+    want, want_state = ctx.ngd_step(0.55), ctx.ngd_get_state()
+    ctx.close()
+    print(f"{setter}: step after the setter {got} / without speculation {want}")
+    assert got == want
+    assert same_bits(want_state, got_state)
+
+
 def test_the_retired_option_name_is_refused():
     ctx = api.Context(0)
-    with pytest.raises(api.GviError, match="unknown option"):
-        ctx.set_option("dual_chain", 0)
+    for name in ("dual_chain", "orbit_stack"):
+        with pytest.raises(api.GviError, match="unknown option"):
+            ctx.set_option(name, 0)
     ctx.close()
