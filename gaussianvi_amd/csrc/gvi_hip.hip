@@ -33,6 +33,7 @@
 #include "kernels_sample_cost.hpp"
 #include "options.hpp"
 #include "orbits.hpp"
+#include "routes.hpp"
 #include "spgh.hpp"
 
 using namespace gvi;
@@ -89,22 +90,13 @@ struct FactorSet {
   DevMem Vws;                         // eigenvectors of the last resident-NGD prep (Jacobi warm start)
   int warm_count = 0;                 // preps since the last cold start
   DevMem partial;
-  int nchunk = 1;
-  int64_t chunk = 0;
-  bool use_reg = false;
-  bool use_split = false;
-  bool use_orbit = false;
-  bool use_opsi = false;              // sign-orbit kernel for the non-polynomial psi kinds (kernels_orbit_psi.hpp)
+  PassRecord last;                    // the set's last moments / cost launch (routes.hpp; gvi_profile_geometry)
   int arm_ndof = 0;
   int seg_J = 0;                      // HINGE_SDF_*_SEG: check points per factor; HINGE_HALFSPACE: rows per factor
-  bool fused_pair = false;            // last resident launch went out fused with the other set
   bool closed_form = false;           // no sigma points: NGDFactorizedLinear route (sum-of-squares kinds), box_moments.hpp (HINGE_BOX, its default), halfspace_moments.hpp (HINGE_HALFSPACE, its default)
   bool chain_structured = false;      // start[k] == k (factor k on state k / states k, k + 1): assemble-on-load needs no CSR
   bool all_pos = false;               // every residual row has sgn = +1 (positive-definite weight)
-  double jtol = 1e-34;                // ctx->opt.jacobi_tol
-  bool use_chol = true;               // ctx->opt.chol_sqrt
   bool force_sym = false;             // set around passes whose caller sees the sigma points
-  bool use_mirror = true;             // evaluate +-pairs from the mirror-half table where the kernel supports it (ctx->opt.mirror)
   int prep_slot = -1;                 // NGD slot whose (mu_k, Sigma_k) the per-pass products belong to
   hipStream_t st = nullptr;           // the set's own stream: prep -> moments -> epilogue overlap across sets
   hipEvent_t done = nullptr;
@@ -118,22 +110,19 @@ struct FactorSet {
     if (done) (void)hipEventDestroy(done);
     if (st) (void)hipStreamDestroy(st);
   }
-  FactorDev dev() const {
+  FactorDev dev(const Options& opt) const {
     FactorDev f;
     f.K = K; f.d = d; f.m = m; f.kind = kind;
     f.N = table->N; f.Np = table->Np;
     f.Zt = table->Zt.d(); f.w = table->w.d();
     f.Zq = table->Zq.p ? table->Zq.d() : nullptr; f.all_pos = all_pos ? 1 : 0;
-    f.Zm = (table->Zm.p && use_mirror) ? table->Zm.d() : nullptr; f.Nm = table->Nm; f.Nmp = table->Nmp;
+    f.Zm = (table->Zm.p && opt.mirror) ? table->Zm.d() : nullptr; f.Nm = table->Nm; f.Nmp = table->Nmp;
     f.codes = table->coded ? (const uint32_t*)table->codes.p : nullptr; f.lut = table->coded ? table->lut.d() : nullptr;
     f.A = A.d(); f.b = b.d(); f.sgn = sgn.d(); f.raw = raw.d(); f.raw_stride = raw_stride;
     f.temperature = unit_temperature ? ones.d() : temperature.d();
     f.S = S.d(); f.Sinv = Sinv.d(); f.Lam = Lam.d(); f.H = H.d(); f.Hq = Hq.p ? Hq.d() : nullptr; f.u0 = u0.d();
-    f.Vws = nullptr; f.warm = 0; f.seg_J = seg_J; f.jko_h = 0.0; f.jtol = jtol;
-    // Cholesky factor instead of the symmetric root: sum-of-squares psi on a generated table of degree >= 3 (exact
-    // quadrature -- kernels_factor.hpp, prep_chol_body), the instantiated dimensions, and not when the caller is going
-    // to look at the sigma points themselves (force_sym: gvi_expand / gvi_moments_from_psi) or runs the JKO map
-    f.chol = (use_chol && !force_sym && psi_kind_is<PSI_SUMSQ>(kind) && table->p >= 3 && d <= 32) ? 1 : 0;
+    f.Vws = nullptr; f.warm = 0; f.seg_J = seg_J; f.jko_h = 0.0; f.jtol = opt.jacobi_tol;
+    f.chol = chol_products(kind, d, table->p, opt.chol_sqrt, force_sym) ? 1 : 0;
     f.sdf = sdf.d(); f.sdf_rows = sdf_rows; f.sdf_cols = sdf_cols; f.sdf_ox = sdf_ox; f.sdf_oy = sdf_oy; f.sdf_cell = sdf_cell; f.sdf_inv_cell = 1.0 / sdf_cell; f.sdf_nz = sdf_nz; f.sdf_oz = sdf_oz; f.arm = arm.p ? arm.d() : nullptr;
     return f;
   }
@@ -206,13 +195,11 @@ struct gvi_ctx {
   DevMem Wbuf, Ibuf, vbuf, scratch, hldtmp;
   std::string err;
   Options opt;                        // every switch of gvi_set_option / the environment (options.hpp)
-  int variant = 0;                    // gvi_set_variant
-  bool prefer_opsi = false;           // gvi_set_variant(7)
+  RouteForce force = RouteForce::Auto;   // gvi_set_variant
   bool speculate = true;              // gvi_ngd_step: queue the next gradients behind the first trial (gvi_ngd_set_mode)
   bool profile = false;
   bool profile_all = false;           // events around every moments / cost launch (else: set 0, full pass only)
   int profile_every = 1;              // on = 3: bracket only every 8th dominant launch (an event pair costs ~14 us of queue gaps)
-  static constexpr int cost_chunk_mult = 8;   // cost pass of the F-factor kernel: chunks per factor relative to the full pass
   int update_rule = 0;                // 0 natural gradient (NGD-GH), 1 proximal / JKO (ProxGVI-GH)
   DevMem Wbuf2, Ibuf2;                // second BCR workspace (the two chains are in flight together)
   // merged top + backward launch of the chain (chain_launch.hpp::ChainSync): a ring of word pairs, one pair per launch
@@ -469,176 +456,8 @@ void ngd_invalidate(gvi_ctx* c) {
 static_assert(Options{}.split_flush == SPLIT_FLUSH, "the default of option split_flush is the split kernel's own constant");
 
 // ---- the compiled instances of the factor kernels ----
-// Every kernel family has ONE list, with_<family>_instance: it hands f a tag that carries the template arguments of the
-// instance compiled for the shape and returns true, or returns false where there is none.  <family>_supported asks the list
-// with a no-op and the launch instantiates the kernel from the tag, so a new instance is registered by one line in its list.
-// These lists and the shape predicates (chain_pair_shape, planar_shape) choose KERNELS by kind; every FACT about a kind --
-// what it keeps, reads and offers -- is a row of psi_kinds.hpp.
-template <int D, typename Psi> struct RegInst {};
-template <int D, int M, bool PIPE> struct SregInst { static constexpr bool pipe = PIPE; };   // PIPE: the hand-pipelined body fits 256 registers
-template <int D, int M> struct ScostInst {};
-template <int D, int R> struct SplitInst {};
-template <int M, int SMAX, int WAVES, bool PAIR> struct OrbitInst { static constexpr int waves = WAVES; static constexpr bool pair = PAIR; };
-template <int KIND> struct OrbitPsiInst {};
-template <int M, int SMAX, int WAVES, int D0, int D1> struct FusedInst {};
-struct ClosedSumsq {};
-struct ClosedBox {};
-struct ClosedHalfspace {};
-constexpr auto any_instance = [](auto) {};
-template <class F, class Inst> bool hit(F& f, Inst inst) { f(inst); return true; }
-
-// moments_reg_kernel<D, Psi, full>: lane-per-point, psi operands in LDS
-template <class F>
-bool with_reg_instance(int kind, int d, int m, F&& f) {
-  switch (kind) {
-    case KIND_RANGE_1D:
-      if (d == 1) return hit(f, RegInst<1, PsiRange1D>{});
-      break;
-    case KIND_HINGE_SDF_2D:
-      if (d == 2) return hit(f, RegInst<2, PsiHingeSdf2D<2>>{});
-      if (d == 4) return hit(f, RegInst<4, PsiHingeSdf2D<4>>{});
-      if (d == 6) return hit(f, RegInst<6, PsiHingeSdf2D<6>>{});
-      break;
-    case KIND_HINGE_SDF_2D_BODY:
-      if (d == 3) return hit(f, RegInst<3, PsiHingeSdf<3, KIND_HINGE_SDF_2D_BODY>>{});
-      if (d == 6) return hit(f, RegInst<6, PsiHingeSdf<6, KIND_HINGE_SDF_2D_BODY>>{});
-      break;
-    case KIND_HINGE_SDF_3D:
-      if (d == 3) return hit(f, RegInst<3, PsiHingeSdf<3, KIND_HINGE_SDF_3D>>{});
-      if (d == 6) return hit(f, RegInst<6, PsiHingeSdf<6, KIND_HINGE_SDF_3D>>{});
-      break;
-    case KIND_HINGE_SDF_2D_SEG:
-      if (d == 4) return hit(f, RegInst<4, PsiHingeSeg<4, 2>>{});
-      if (d == 8) return hit(f, RegInst<8, PsiHingeSeg<8, 2>>{});
-      if (d == 12) return hit(f, RegInst<12, PsiHingeSeg<12, 2>>{});
-      break;
-    case KIND_HINGE_SDF_3D_SEG:   // d = 12: 256 VGPRs + 18 AGPR copies under launch_bounds(256) -> generic kernel
-      if (d == 6) return hit(f, RegInst<6, PsiHingeSeg<6, 3>>{});
-      break;
-    case KIND_HINGE_BOX:          // above d = 8 the accumulators leave no room: generic kernel, or the closed form
-      if (d == 2) return hit(f, RegInst<2, PsiBoxHinge<2>>{});
-      if (d == 4) return hit(f, RegInst<4, PsiBoxHinge<4>>{});
-      if (d == 6) return hit(f, RegInst<6, PsiBoxHinge<6>>{});
-      if (d == 8) return hit(f, RegInst<8, PsiBoxHinge<8>>{});
-      break;
-    case KIND_QUAD_PRIOR:
-      if (d != 2 * m) break;
-      if (d == 2) return hit(f, RegInst<2, PsiQuad<2, 1>>{});
-      if (d == 4) return hit(f, RegInst<4, PsiQuad<4, 2>>{});
-      if (d == 6) return hit(f, RegInst<6, PsiQuad<6, 3>>{});
-      if (d == 8) return hit(f, RegInst<8, PsiQuad<8, 4>>{});
-      if (d == 12) return hit(f, RegInst<12, PsiQuad<12, 6>>{});
-      break;
-    case KIND_FIXED_PRIOR:
-      if (d != m) break;
-      if (d == 1) return hit(f, RegInst<1, PsiQuad<1, 1>>{});
-      if (d == 2) return hit(f, RegInst<2, PsiQuad<2, 2>>{});
-      if (d == 3) return hit(f, RegInst<3, PsiQuad<3, 3>>{});
-      if (d == 4) return hit(f, RegInst<4, PsiQuad<4, 4>>{});
-      if (d == 6) return hit(f, RegInst<6, PsiQuad<6, 6>>{});
-      if (d == 8) return hit(f, RegInst<8, PsiQuad<8, 8>>{});
-      if (d == 12) return hit(f, RegInst<12, PsiQuad<12, 12>>{});
-      break;
-  }
-  return false;
-}
-
-// moments_sreg_kernel<D, M, full, pipelined>: lane-per-point, psi operands from SGPRs (variants 0 and 5)
-template <class F>
-bool with_sreg_instance(int kind, int d, int m, F&& f) {
-  if (kind == KIND_QUAD_PRIOR && d == 2 * m) {
-    if (d == 4) return hit(f, SregInst<4, 2, true>{});
-    if (d == 8) return hit(f, SregInst<8, 4, true>{});
-    if (d == 12) return hit(f, SregInst<12, 6, true>{});
-  }
-  if (kind == KIND_FIXED_PRIOR && d == m) {
-    if (d == 6) return hit(f, SregInst<6, 6, true>{});
-    if (d == 12) return hit(f, SregInst<12, 12, false>{});   // M = 12: the pipelined body does not fit 256 registers
-  }
-  return false;
-}
-
-// moments_scost_kernel<D, M, 2>: cost pass with two factors per wave (grid.x shrinks by 2); only the headline shapes
-template <class F>
-bool with_scost_instance(int kind, int d, int m, F&& f) {
-  if (kind == KIND_QUAD_PRIOR && d == 12 && m == 6) return hit(f, ScostInst<12, 6>{});
-  if (kind == KIND_FIXED_PRIOR && d == 6 && m == 6) return hit(f, ScostInst<6, 6>{});
-  return false;
-}
-
-// moments_split_kernel<D, R, full> (one block per factor and chunk), R = ceil(m / 4) row blocks: m = d and m = d / 2
-template <class F>
-bool with_split_instance(int d, int m, F&& f) {
-  if (d == 16 && m == 8) return hit(f, SplitInst<16, 2>{});
-  if (d == 16 && m == 16) return hit(f, SplitInst<16, 4>{});
-  if (d == 20 && m == 10) return hit(f, SplitInst<20, 3>{});
-  if (d == 20 && m == 20) return hit(f, SplitInst<20, 5>{});
-  if (d == 24 && m == 12) return hit(f, SplitInst<24, 3>{});
-  if (d == 24 && m == 24) return hit(f, SplitInst<24, 6>{});
-  return false;
-}
-
-// moments_orbit_kernel<M, SMAX, full, signed, WAVES>, and where PAIR moments_orbit_pair_kernel<M, SMAX, full, false, WAVES>:
-// smax is the largest support of the table's orbits (of both tables for the pair).  m = 2 is instantiated for supports <= 4
-// (every table of d <= 4, wider ones to degree 5), m = 14 (the d = 28 priors of the arm graph) likewise and on its own only.
-template <class F>
-bool with_orbit_instance(int m, int smax, F&& f) {
-  if (smax < 1 || smax > ORBIT_SMAX) return false;
-  if (m == 2 && smax <= 4) return hit(f, OrbitInst<2, 4, 4, true>{});
-  if (m == 14 && smax <= 4) return hit(f, OrbitInst<14, 4, 2, false>{});
-  if (m == 6) return smax <= 4 ? hit(f, OrbitInst<6, 4, 4, true>{}) : hit(f, OrbitInst<6, 6, 2, true>{});
-  if (m == 12) return smax <= 4 ? hit(f, OrbitInst<12, 4, 3, true>{}) : hit(f, OrbitInst<12, 6, 2, true>{});
-  return false;
-}
-
-// moments_orbit_psi_kernel<KIND, full>
-template <class F>
-bool with_orbit_psi_instance(int kind, F&& f) {
-  switch (kind) {
-    case KIND_RANGE_1D: return hit(f, OrbitPsiInst<KIND_RANGE_1D>{});
-    case KIND_HINGE_SDF_2D: return hit(f, OrbitPsiInst<KIND_HINGE_SDF_2D>{});
-    case KIND_HINGE_SDF_2D_BODY: return hit(f, OrbitPsiInst<KIND_HINGE_SDF_2D_BODY>{});
-    case KIND_HINGE_SDF_3D: return hit(f, OrbitPsiInst<KIND_HINGE_SDF_3D>{});
-    case KIND_HINGE_SDF_3D_ARM: return hit(f, OrbitPsiInst<KIND_HINGE_SDF_3D_ARM>{});
-  }
-  return false;
-}
-
-// factor_fused_kernel<M, SMAX, WAVES, D0, D1>: the chain patterns of BASELINE configs[1..3] (binary prior d = 2n + unary
-// factor d = n); smax over both tables
-template <class F>
-bool with_fused_instance(int m, int smax, int d0, int d1, F&& f) {
-  if (smax < 1 || smax > ORBIT_SMAX) return false;
-  if (m == 6 && d0 == 12 && d1 == 6) return smax <= 4 ? hit(f, FusedInst<6, 4, 4, 12, 6>{}) : hit(f, FusedInst<6, 6, 2, 12, 6>{});
-  if (m == 2 && d0 == 4 && d1 == 2 && smax <= 4) return hit(f, FusedInst<2, 4, 4, 4, 2>{});
-  return false;
-}
-
-// the quadrature-free kernels (PSI_CLOSED kinds): moments_closed_kernel, moments_box_closed_kernel, moments_halfspace_closed_kernel
-template <class F>
-bool with_closed_instance(int kind, F&& f) {
-  switch (kind) {
-    case KIND_QUAD_PRIOR:
-    case KIND_FIXED_PRIOR: return hit(f, ClosedSumsq{});
-    case KIND_HINGE_BOX: return hit(f, ClosedBox{});
-    case KIND_HINGE_HALFSPACE: return hit(f, ClosedHalfspace{});
-  }
-  return false;
-}
-
-bool reg_supported(int kind, int d, int m) { return with_reg_instance(kind, d, m, any_instance); }
-bool sreg_supported(const FactorSet& s) { return with_sreg_instance(s.kind, s.d, s.m, any_instance); }
-bool scost_supported(const FactorSet& s) { return with_scost_instance(s.kind, s.d, s.m, any_instance); }
-// sum-of-squares kinds on a coded table
-bool split_supported(const FactorSet& s) {
-  return psi_kind_is<PSI_SUMSQ>(s.kind) && s.table->coded && with_split_instance(s.d, s.m, any_instance);
-}
-bool orbit_pair_supported(int m, int smax) {
-  bool pair = false;
-  with_orbit_instance(m, smax, [&](auto inst) { pair = inst.pair; });
-  return pair;
-}
-
+// The lists with_<family>_instance, their tags and the *_supported helpers are in routes.hpp, with the decisions that ask
+// them; here the launches instantiate the kernels from the tags.
 template <int D, int R>
 gvi_status launch_split(gvi_ctx* c, const MomArgs& a, dim3 grid, hipStream_t st) {
   const size_t lds = (size_t)SPLIT_LDS_DOUBLES(D) * 8;
@@ -648,16 +467,6 @@ gvi_status launch_split(gvi_ctx* c, const MomArgs& a, dim3 grid, hipStream_t st)
   else hipLaunchKernelGGL((moments_split_kernel<D, R, false>), grid, dim3(256), lds, st, a);
   return GVI_OK;
 }
-
-// about nch chunks of whole 256-point tiles (Np is a multiple of 256: upload_table)
-void chunk_tiles(FactorSet& s, int64_t nch) {
-  const int64_t Np = s.table->Np, iters = Np / 256;
-  nch = std::min<int64_t>(std::max<int64_t>(1, nch), std::max<int64_t>(1, iters));
-  s.chunk = (iters + nch - 1) / nch * 256;
-  s.nchunk = (int)((Np + s.chunk - 1) / s.chunk);
-}
-// lane-per-point kernels: target_waves waves over the set; generic kernel: ~1024 blocks
-void plan_chunks(gvi_ctx* c, FactorSet& s, bool reg) { chunk_tiles(s, ((reg ? c->opt.target_waves : 1024) + s.K - 1) / s.K); }
 
 template <int D, typename Psi>
 void launch_reg(const MomArgs& a, dim3 grid, hipStream_t st) {
@@ -672,24 +481,31 @@ void launch_sreg(const MomArgs& a, dim3 grid, hipStream_t st, bool pipe) {
   else hipLaunchKernelGGL((moments_sreg_kernel<D, M, false>), grid, dim3(256), 0, st, a);
 }
 
-// ---- sign-orbit kernel (kernels_orbit.hpp) ----
-bool orbit_supported(const gvi_ctx* c, const FactorSet& s) {
-  if (!c->opt.orbit || !(c->variant == 0 || c->variant == 6)) return false;
-  if (!psi_kind_is<PSI_SUMSQ>(s.kind)) return false;
-  const OrbitHost& o = s.table->orb;
-  return s.d <= 32 && o.ok && !o.tile_s.empty() && with_orbit_instance(s.m, o.smax, any_instance);
+// ---- what the decisions of routes.hpp read of a set, its table and the context ----
+RouteFacts route_facts(const FactorSet& s, bool psi_ext) {
+  const Table& t = *s.table;
+  RouteFacts f;
+  f.kind = s.kind; f.d = s.d; f.m = s.m; f.K = s.K;
+  f.closed_form = s.closed_form; f.all_pos = s.all_pos; f.psi_ext = psi_ext;
+  f.has_arm = s.arm.p != nullptr; f.has_sdf = s.sdf_rows != 0;
+  f.arm_ndof = s.arm_ndof; f.seg_J = s.seg_J; f.opsi_rows = orbit_psi_rows(s.kind);
+  f.Np = t.Np; f.Nmp = t.Nmp; f.p = t.p; f.coded = t.coded; f.has_Zq = t.Zq.p != nullptr;
+  f.orb_ok = t.orb.ok; f.orb_smax = t.orb.smax; f.orb_tiles = (int64_t)t.orb.tile_s.size();
+  return f;
 }
+RouteRules rules_of(const gvi_ctx* c) { return route_rules(c->opt, c->force); }
 
-// the table's sign-orbit form as kernel arguments, for the set's current s.nchunk
-gvi_status orbit_dev(gvi_ctx* c, FactorSet& s, OrbitDev* out) {
+// ---- sign-orbit kernel (kernels_orbit.hpp) ----
+// the table's sign-orbit form as kernel arguments, for a pass of nchunk chunks
+gvi_status orbit_dev(gvi_ctx* c, FactorSet& s, int nchunk, OrbitDev* out) {
   Table& t = *s.table;
-  auto it = t.orb_bounds.find(s.nchunk);
+  auto it = t.orb_bounds.find(nchunk);
   if (it == t.orb_bounds.end()) {
-    const std::vector<int32_t> b = orbit_chunk_bounds(t.orb, s.nchunk);
+    const std::vector<int32_t> b = orbit_chunk_bounds(t.orb, nchunk);
     auto mem = std::make_unique<DevMem>();
     HIPCK(c, mem->ensure(b.size() * 4));
     HIPCK(c, hipMemcpy(mem->p, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-    it = t.orb_bounds.emplace(s.nchunk, std::move(mem)).first;
+    it = t.orb_bounds.emplace(nchunk, std::move(mem)).first;
   }
   OrbitDev& ob = *out;
   ob.cpk = (const uint64_t*)t.orb_cpk.p; ob.rpk = (const uint64_t*)t.orb_rpk.p; ob.mag = t.orb_mag.d(); ob.w = t.orb_w.d();
@@ -710,19 +526,19 @@ gvi_status orbit_dev(gvi_ctx* c, FactorSet& s, OrbitDev* out) {
   }
   ob.nb = 0;
   for (int i = 0; i < 5; ++i) ob.bnd[i] = 0;
-  if (s.nchunk <= 4) {
-    const std::vector<int32_t> b = orbit_chunk_bounds(t.orb, s.nchunk);
-    ob.nb = s.nchunk;
-    for (int i = 0; i <= s.nchunk; ++i) ob.bnd[i] = b[(size_t)i];
+  if (nchunk <= 4) {
+    const std::vector<int32_t> b = orbit_chunk_bounds(t.orb, nchunk);
+    ob.nb = nchunk;
+    for (int i = 0; i <= nchunk; ++i) ob.bnd[i] = b[(size_t)i];
   }
   return GVI_OK;
 }
 
-// arguments of moments_orbit_kernel for a set that orbit_supported accepts
-gvi_status orbit_args(gvi_ctx* c, FactorSet& s, OrbitArgs* out) {
+// arguments of moments_orbit_kernel for a set that orbit_supported accepts, in a pass of nchunk chunks
+gvi_status orbit_args(gvi_ctx* c, FactorSet& s, int nchunk, OrbitArgs* out) {
   OrbitArgs a;
   a.H = s.H.d(); a.u0 = s.u0.d(); a.sgn = s.sgn.d(); a.partial = s.partial.d();
-  a.K = s.K; a.d = s.d; a.nchunk = s.nchunk;
+  a.K = s.K; a.d = s.d; a.nchunk = nchunk;
   a.pred = c->pipe.pred; a.pred_val = c->pipe.pred_val;
   // private accumulator copies: as many as the occupancy of the set's own instance leaves LDS for (160 KB per CU, 64 KB per
   // block), capped by orbit_copies
@@ -732,7 +548,7 @@ gvi_status orbit_args(gvi_ctx* c, FactorSet& s, OrbitArgs* out) {
   const size_t lds_cap = std::min<size_t>(64 * 1024, 160 * 1024 / waves);
   a.copies = 1;
   while (a.copies * 2 <= c->opt.orbit_copies && (size_t)4 * orbit_lds_doubles(s.d, s.m, a.copies * 2) * 8 <= lds_cap) a.copies *= 2;
-  GVICK(orbit_dev(c, s, &a.ob));
+  GVICK(orbit_dev(c, s, nchunk, &a.ob));
   *out = a;
   return GVI_OK;
 }
@@ -845,28 +661,12 @@ gvi_status run_prep(gvi_ctx* c, FactorSet& s, const double* mu, const double* Si
   if (slot >= 0 && s.prep_slot == slot) return GVI_OK;     // products of this slot are still resident
   s.prep_slot = slot;
   if (s.K == 0) return GVI_OK;
-  GVICK(launch_prep(c, s.dev(), mu, Sigma, st));
+  GVICK(launch_prep(c, s.dev(c->opt), mu, Sigma, st));
   HIPCK(c, hipGetLastError());
   return GVI_OK;
 }
 
-// ---- sign-orbit kernel for the non-polynomial psi kinds (kernels_orbit_psi.hpp) ----
-// Selected by gvi_set_variant(7) only.  Measured (profiles/r04_*): with a non-polynomial psi the evaluations themselves
-// dominate and a lane that walks an orbit evaluates its 2^s points ONE AFTER THE OTHER -- planar hinge factors (d = 4, p = 7):
-// 30.8 us against 19.0 us of the lane-per-point register kernel; the arm graph's 129 factors x 421 points: 120 us slower per
-// pass than the generic kernel, which keeps 54 k points in flight.  It stays as the A/B leg and as the parity cross-check
-// (three independent kernels for these kinds); the arm graph's 0.27 ms launch was its d = 28 PRIOR set on the generic kernel,
-// which now takes the m = 14 instance of the sign-orbit kernel.
-bool orbit_psi_supported(const gvi_ctx* c, const FactorSet& s) {
-  if (!c->opt.orbit) return false;
-  if (!(c->variant == 0 && c->prefer_opsi)) return false;
-  if (!with_orbit_psi_instance(s.kind, any_instance)) return false;
-  const OrbitHost& o = s.table->orb;
-  if (!(o.ok && o.smax >= 1 && o.smax <= 4 && !o.tile_s.empty()) || s.d > 32) return false;
-  if (psi_kind_is<PSI_ARM>(s.kind) && (s.arm_ndof < 1 || s.arm_ndof > orbit_psi_rows(s.kind))) return false;
-  return orbit_psi_rows(s.kind) <= s.d;
-}
-
+// ---- sign-orbit kernel for the non-polynomial psi kinds (kernels_orbit_psi.hpp; selected by gvi_set_variant(7) only) ----
 template <int KIND>
 gvi_status launch_orbit_psi_t(gvi_ctx* c, const OrbitPsiArgs& a, bool full, dim3 grid, size_t lds, hipStream_t st) {
   if (full) {
@@ -881,10 +681,11 @@ gvi_status launch_orbit_psi_t(gvi_ctx* c, const OrbitPsiArgs& a, bool full, dim3
 // ---- the moments (full = 1) or cost (full = 0) pass of one set: plan, then launch ----
 // A plan is a value: the route, the chunking and the kernel arguments of the launch the set would issue on its own.  The
 // resident iteration plans every set once, then either fuses the launches of two or three plans or issues each one.
-enum class Route { Empty, Closed, Orbit, OrbitPsi, Split, Sreg, Scost, Reg, Generic };
 struct MomPlan {
   Route route = Route::Empty;
   int full = 0;
+  int nchunk = 1;            // chunks per factor: what the epilogue of this pass reduces
+  int64_t chunk = 0;
   MomArgs a;                 // every route but the two sign-orbit ones
   dim3 grid;                 // of the set's own launch
   OrbitArgs oa;              // Orbit
@@ -894,8 +695,12 @@ struct MomPlan {
   bool pipe = false;         // Sreg: the hand-pipelined body
   int block = 64;            // Closed (HINGE_HALFSPACE): lanes per block, 64 or 256
 };
-// lane-per-point register kernels: a block's four waves take four factors, grid ((K + 3) / 4, nchunk) but for Scost's own launch
-bool lane_per_point(const MomPlan& p) { return p.route == Route::Sreg || p.route == Route::Scost || p.route == Route::Reg; }
+// a pass of the resident iteration over all sets: what was read, what was decided, what was bound
+struct PassPlan {
+  RouteFacts F[MAX_SETS];
+  RouteDecision D[MAX_SETS];
+  MomPlan P[MAX_SETS];
+};
 
 // grid, block and LDS of a closed-form launch, and the launch itself, per kernel of with_closed_instance (p.grid = K blocks on entry)
 gvi_status plan_closed(gvi_ctx*, const FactorSet&, MomPlan&, ClosedSumsq) { return GVI_OK; }
@@ -904,9 +709,8 @@ gvi_status plan_closed(gvi_ctx* c, const FactorSet& s, MomPlan& p, ClosedBox) {
   if (p.lds > 64 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_BOX kernel LDS budget (d <= 89)");
   return GVI_OK;
 }
-gvi_status plan_closed(gvi_ctx* c, const FactorSet& s, MomPlan& p, ClosedHalfspace) {
-  if (s.d > 32) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_HALFSPACE kernel supports d <= 32");
-  // a wave holds G = 64 / Jp factors.  One wave per block while the launch has no more waves than the chip has SIMDs
+gvi_status plan_closed(gvi_ctx*, const FactorSet& s, MomPlan& p, ClosedHalfspace) {
+  // (d <= 32: decide_route)  a wave holds G = 64 / Jp factors.  One wave per block while the launch has no more waves than the chip has SIMDs
   // (256 CUs x 4): every wave can start at once wherever its block lands; above that four waves per block, a quarter
   // of the workgroups to dispatch
   const int64_t nwaves = (s.K + 64 / halfspace_group(s.seg_J) - 1) / (64 / halfspace_group(s.seg_J));
@@ -930,104 +734,50 @@ gvi_status launch_closed(gvi_ctx* c, const MomPlan& p, hipStream_t st, ClosedHal
   return GVI_OK;
 }
 
-// Everything before the launch: state checks, route under `variant` and the options, chunking (s.nchunk / chunk / use_*),
-// the partial buffer, the kernel arguments.  prep must have run for (mu, Sigma) before the plan is launched.
-gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double* psi_ext, int full, MomPlan* out) {
+// Binds a decision: the partial buffer, the kernel arguments, and the sizes and refusals that take the size functions of the
+// kernel headers.  Beyond its buffers it writes nothing into the set.  prep must have run for (mu, Sigma) before the plan is
+// launched.
+gvi_status bind_plan(gvi_ctx* c, FactorSet& s, const RouteDecision& r, const double* mu, const double* psi_ext, int full, MomPlan* out) {
   MomPlan& p = *out;
-  p.route = Route::Empty; p.full = full;
-  if (s.K == 0) { s.nchunk = 1; s.chunk = s.table->Np; s.use_reg = s.use_split = s.use_orbit = s.use_opsi = false; return GVI_OK; }   // empty shard
-  if (psi_kind_is<PSI_ARM>(s.kind) && !psi_ext && !s.arm.p)
-    return fail(c, GVI_ERR_STATE, "HINGE_SDF_3D_ARM set without an arm model: call gvi_factors_set_arm");
-  if (psi_kind_is<PSI_SDF>(s.kind) && !psi_ext && s.sdf_rows == 0)
-    return fail(c, GVI_ERR_STATE, "HINGE_SDF set without a grid: call gvi_factors_set_sdf2d / gvi_factors_set_sdf3d");
-  bool reg = reg_supported(s.kind, s.d, s.m) && !psi_ext && c->variant != 1;
-  if (c->variant == 2 && !reg && !psi_ext)
-    return fail(c, GVI_ERR_UNSUPPORTED, "register kernel not instantiated for this (kind, d)");
-  const bool closed = s.closed_form && !psi_ext;
-  const bool orbit = !closed && !psi_ext && orbit_supported(c, s);
-  const bool opsi = !closed && !orbit && !psi_ext && orbit_psi_supported(c, s);
-  const bool split = !closed && !orbit && !opsi && !reg && !psi_ext && c->variant != 1 && split_supported(s);
-  if (closed) { reg = false; s.chunk = s.table->Np; s.nchunk = 1; }
-  else if (orbit || opsi) {
-    reg = false;
-    const int64_t tiles = (int64_t)s.table->orb.tile_s.size();
-    // chunks: enough waves to fill the chip, but at least orbit_min_tiles tiles per wave -- a wave's prologue (H into LDS,
-    // zeroing the accumulator copies) and its reduction of the copies cost about as much as two tiles
-    const int64_t by_waves = std::max<int64_t>(1, (c->opt.orbit_waves + s.K - 1) / s.K);
-    const int64_t by_tiles = std::max<int64_t>(1, tiles / std::max(1, c->opt.orbit_min_tiles));
-    s.nchunk = (int)std::min<int64_t>(tiles, std::min(by_waves, by_tiles));
-    s.chunk = s.table->Np;
-  } else if (split) {
-    const int64_t tiles = s.table->Np / 64;                          // ~2 blocks per CU: K * nchunk >= 1024
-    int64_t nch = std::max<int64_t>(1, (1024 + s.K - 1) / s.K);
-    nch = std::max<int64_t>(nch, (tiles + 16383) / 16384);         // <= 16k points per lane: bounds the rounding of the
-    nch = std::min<int64_t>(nch, tiles);                           // sequential sums (|w|_1 ~ 2e7 at (24,7))
-    s.chunk = (tiles + nch - 1) / nch * 64;
-    s.nchunk = (int)((s.table->Np + s.chunk - 1) / s.chunk);
-  } else plan_chunks(c, s, reg);
-  // auto (variants 0 and 5): psi operands from SGPRs where instantiated (fastest for both passes); otherwise the operand-
-  // resident kernel for the cost pass and the LDS-operand kernel for the full pass
-  const bool sgpr = reg && (c->variant == 5 || c->variant == 0);
-  const bool scost = sgpr && !full && scost_supported(s) && !c->opt.no_scost;
-  if (scost) chunk_tiles(s, (int64_t)s.nchunk * c->cost_chunk_mult);   // two factors per wave: keep the wave count up with more, shorter chunks
-  s.use_reg = reg;
-  s.use_split = split;
-  s.use_orbit = orbit;
-  s.use_opsi = opsi;
-  const size_t need = (size_t)s.K * s.nchunk * npairs(s.d) * 8;
-  HIPCK(c, s.partial.ensure(need));
+  p.route = r.route; p.full = full; p.nchunk = r.nchunk; p.chunk = r.chunk; p.pipe = r.pipe;
+  if (r.route == Route::Empty) return GVI_OK;
+  HIPCK(c, s.partial.ensure((size_t)s.K * r.nchunk * npairs(s.d) * 8));
   MomArgs& a = p.a;
-  s.use_mirror = c->opt.mirror;
-  a.f = s.dev(); a.mu = mu; a.psi_ext = psi_ext; a.partial = s.partial.d();
-  a.chunk = s.chunk; a.nchunk = s.nchunk; a.full = full; a.flush = c->opt.split_flush;
-  a.mchunk = 0;
+  a.f = s.dev(c->opt); a.mu = mu; a.psi_ext = psi_ext; a.partial = s.partial.d();
+  a.chunk = r.chunk; a.nchunk = r.nchunk; a.full = full; a.flush = c->opt.split_flush;
+  a.mchunk = r.mchunk;
   a.pred = c->pipe.pred; a.pred_val = c->pipe.pred_val;
-  if (s.table->Nmp > 0) {                                   // same number of chunks over the mirror-half table
-    const int64_t tiles = s.table->Nmp / 64;
-    a.mchunk = (tiles + s.nchunk - 1) / s.nchunk * 64;
-  }
-  p.grid = dim3((s.K + 3) / 4, s.nchunk);
-  if (closed) {
-    p.route = Route::Closed;
-    p.grid = dim3(s.K);
+  p.grid = dim3(r.gx, r.gy);
+  if (r.route == Route::Closed) {
     gvi_status rc = GVI_OK;
     with_closed_instance(s.kind, [&](auto inst) { rc = plan_closed(c, s, p, inst); });
     GVICK(rc);
-  } else if (orbit) {
-    p.route = Route::Orbit;
-    GVICK(orbit_args(c, s, &p.oa));
+  } else if (r.route == Route::Orbit) {
+    GVICK(orbit_args(c, s, r.nchunk, &p.oa));
     p.smax = s.table->orb.smax;
     p.lds = (size_t)4 * orbit_lds_doubles(s.d, s.m, p.oa.copies) * 8;
-  } else if (opsi) {
-    p.route = Route::OrbitPsi;
+  } else if (r.route == Route::OrbitPsi) {
     OrbitPsiArgs& pa = p.pa;
-    pa.f = a.f; pa.mu = mu; pa.partial = s.partial.d(); pa.nchunk = s.nchunk;
+    pa.f = a.f; pa.mu = mu; pa.partial = s.partial.d(); pa.nchunk = r.nchunk;
     pa.pred = c->pipe.pred; pa.pred_val = c->pipe.pred_val;
-    GVICK(orbit_dev(c, s, &pa.ob));                         // table pointers, class layout, chunk bounds
+    GVICK(orbit_dev(c, s, r.nchunk, &pa.ob));               // table pointers, class layout, chunk bounds
     const int NR = orbit_psi_rows(s.kind);
     pa.copies = 1;
     while (pa.copies * 2 <= c->opt.orbit_copies && (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies * 2, true) * 8 <= 64 * 1024) pa.copies *= 2;
     p.lds = (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies, full != 0) * 8;
-  } else if (split) {
-    p.route = Route::Split;
-    p.grid = dim3(s.K, s.nchunk);
-  } else if (scost) {
-    p.route = Route::Scost;
-    p.grid = dim3((s.K + 7) / 8, s.nchunk);
-  } else if (sgpr && sreg_supported(s)) {
-    p.route = Route::Sreg;
-    with_sreg_instance(s.kind, s.d, s.m, [&](auto inst) { p.pipe = inst.pipe && c->opt.sreg_pipe && s.table->Zq.p; });
-  } else if (reg) {
-    p.route = Route::Reg;
-  } else {
-    p.route = Route::Generic;
-    if (s.d > 32) return fail(c, GVI_ERR_UNSUPPORTED, "generic kernel supports d <= 32");
+  } else if (r.route == Route::Generic) {
     const int d = s.d, m = s.m;
     p.lds = (size_t)(2 * GEN_BS * (d + 1) + GEN_BS + d * d + d + m * d + 2 * m) * 8;
     if (p.lds > 160 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "generic kernel LDS budget");
-    p.grid = dim3(s.K, s.nchunk);
   }
   return GVI_OK;
+}
+
+// plan = decide (a refusal becomes the context's error) + bind
+gvi_status plan_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double* psi_ext, int full, MomPlan* out) {
+  const RouteDecision r = decide_route(route_facts(s, psi_ext != nullptr), rules_of(c), full);
+  if (r.status != GVI_OK) return fail(c, r.status, r.why);
+  return bind_plan(c, s, r, mu, psi_ext, full, out);
 }
 
 // the launch a plan describes, on its own
@@ -1159,8 +909,12 @@ gvi_status prof_close(gvi_ctx* c, const ProfBracket& b) {
   return GVI_OK;
 }
 
+// what a launch owes gvi_profile_geometry: the plan it sent out for the set, and whether the other set went with it
+void record_plan(FactorSet& s, const MomPlan& p, bool fused_pair) { record_pass(s.last, p.route, fused_pair, p.nchunk, p.chunk); }
+
 // a plan's launch on its own, bracketed: every launch under profile_all, else the full pass of set 0
 gvi_status launch_single(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t st) {
+  record_plan(s, p, false);
   if (p.route == Route::Empty) return GVI_OK;
   ProfBracket b;
   GVICK(prof_open(c, s, p.full ? 0 : 1, c->profile_all || (p.full && &s == c->sets[0].get()), true, st, &b));
@@ -1168,19 +922,20 @@ gvi_status launch_single(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t
   return prof_close(c, b);
 }
 
-// moments (full=1) or cost (full=0) pass for one set; prep must have run for (mu, Sigma).
-gvi_status run_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double* psi_ext, int full) {
+// moments (full=1) or cost (full=0) pass for one set; prep must have run for (mu, Sigma).  *nchunk: what run_epilogue reduces
+gvi_status run_moments(gvi_ctx* c, FactorSet& s, const double* mu, const double* psi_ext, int full, int* nchunk) {
   MomPlan p;
   GVICK(plan_moments(c, s, mu, psi_ext, full, &p));
+  *nchunk = p.nchunk;
   return launch_single(c, s, p, c->stream);
 }
 
-gvi_status run_epilogue(gvi_ctx* c, FactorSet& s, int full, double* Ephi, double* cost, double* Vdmu,
+gvi_status run_epilogue(gvi_ctx* c, FactorSet& s, int full, int nchunk, double* Ephi, double* cost, double* Vdmu,
                         double* Vddmu, double* Ex, double* Exx, hipStream_t st = nullptr) {
   if (!st) st = c->stream;
   if (s.K == 0) return GVI_OK;
   EpiArgs e;
-  e.f = s.dev(); e.partial = s.partial.d(); e.nchunk = s.nchunk; e.full = full;
+  e.f = s.dev(c->opt); e.partial = s.partial.d(); e.nchunk = nchunk; e.full = full;
   e.Ephi = Ephi; e.cost = cost; e.Vdmu = Vdmu; e.Vddmu = Vddmu; e.E_xmuphi = Ex; e.E_xxphi = Exx;
   const size_t lds = epilogue_lds_doubles(s.d) * 8;
   hipLaunchKernelGGL(epilogue_kernel, dim3(s.K), dim3(64), lds, st, e);
@@ -1445,8 +1200,6 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   HIPCK(ctx, hipSetDevice(ctx->device));
 
   std::unique_ptr<FactorSet> s(new FactorSet);
-  s->jtol = ctx->opt.jacobi_tol;
-  s->use_chol = ctx->opt.chol_sqrt;
   s->unit_temperature = ctx->update_rule == GVI_RULE_PROX_JKO;    // the rule belongs to the context: a set takes it when it is added
   s->K = K; s->d = d; s->p = p; s->m = m; s->kind = psi_kind; s->seg_J = seg_J;
   s->closed_form = psi_kind_is<PSI_CLOSED_DEFAULT>(psi_kind);      // gvi_factors_set_closed_form(.., 0) for the quadrature
@@ -1541,7 +1294,7 @@ static gvi_status factors_add_impl(gvi_ctx* ctx, int K, int d, int p, const int3
   HIPCK(ctx, s->Sinv.ensure((size_t)K * d * d * 8));
   HIPCK(ctx, s->Lam.ensure((size_t)K * d * d * 8));
   HIPCK(ctx, s->H.ensure((size_t)K * std::max(m, 1) * d * 8));
-  if (split_supported(*s)) {            // per-wave row blocks of H for the split kernel (rows >= m stay 0)
+  if (split_supported(psi_kind, d, m, s->table->coded)) {           // per-wave row blocks of H for the split kernel (rows >= m stay 0)
     const size_t bytes = (size_t)K * 4 * d * ((m + 3) / 4) * 8;
     HIPCK(ctx, s->Hq.ensure(bytes));
     HIPCK(ctx, hipMemset(s->Hq.p, 0, bytes));
@@ -1685,8 +1438,9 @@ gvi_status gvi_moments_dev(gvi_ctx* ctx, int set_id, const double* mu, const dou
   if (psi_kind_is<PSI_NO_DEVICE>(s->kind)) return fail(ctx, GVI_ERR_ARG, "HOST_CALLBACK set: use gvi_expand + gvi_moments_from_psi");
   HIPCK(ctx, hipSetDevice(ctx->device));
   GVICK(run_prep(ctx, *s, mu, Sigma));
-  GVICK(run_moments(ctx, *s, mu, nullptr, 1));
-  return run_epilogue(ctx, *s, 1, Ephi, nullptr, Vdmu, Vddmu, nullptr, nullptr);
+  int nchunk = 1;
+  GVICK(run_moments(ctx, *s, mu, nullptr, 1, &nchunk));
+  return run_epilogue(ctx, *s, 1, nchunk, Ephi, nullptr, Vdmu, Vddmu, nullptr, nullptr);
 }
 
 gvi_status gvi_costs_dev(gvi_ctx* ctx, int set_id, const double* mu, const double* Sigma, double* cost) {
@@ -1695,8 +1449,9 @@ gvi_status gvi_costs_dev(gvi_ctx* ctx, int set_id, const double* mu, const doubl
   if (psi_kind_is<PSI_NO_DEVICE>(s->kind)) return fail(ctx, GVI_ERR_ARG, "HOST_CALLBACK set has no device psi");
   HIPCK(ctx, hipSetDevice(ctx->device));
   GVICK(run_prep(ctx, *s, mu, Sigma));
-  GVICK(run_moments(ctx, *s, mu, nullptr, 0));
-  return run_epilogue(ctx, *s, 0, nullptr, cost, nullptr, nullptr, nullptr, nullptr);
+  int nchunk = 1;
+  GVICK(run_moments(ctx, *s, mu, nullptr, 0, &nchunk));
+  return run_epilogue(ctx, *s, 0, nchunk, nullptr, cost, nullptr, nullptr, nullptr, nullptr);
 }
 
 static gvi_status upload_pass_inputs(gvi_ctx* ctx, FactorSet* s, const double* mu, const double* Sigma) {
@@ -1729,8 +1484,9 @@ gvi_status gvi_raw_moments(gvi_ctx* ctx, int set_id, const double* mu, const dou
   HIPCK(ctx, s->raw1.ensure((size_t)s->K * s->d * 8));
   HIPCK(ctx, s->raw2.ensure((size_t)s->K * s->d * s->d * 8));
   GVICK(run_prep(ctx, *s, s->in_mu.d(), s->in_Sigma.d()));
-  GVICK(run_moments(ctx, *s, s->in_mu.d(), nullptr, 1));
-  GVICK(run_epilogue(ctx, *s, 1, s->Ephi.d(), nullptr, nullptr, nullptr, s->raw1.d(), s->raw2.d()));
+  int nchunk = 1;
+  GVICK(run_moments(ctx, *s, s->in_mu.d(), nullptr, 1, &nchunk));
+  GVICK(run_epilogue(ctx, *s, 1, nchunk, s->Ephi.d(), nullptr, nullptr, nullptr, s->raw1.d(), s->raw2.d()));
   if (E_phi) GVICK(d2h(ctx, E_phi, s->Ephi.p, (size_t)s->K * 8));
   if (E_xmuphi) GVICK(d2h(ctx, E_xmuphi, s->raw1.p, (size_t)s->K * s->d * 8));
   if (E_xxphi) GVICK(d2h(ctx, E_xxphi, s->raw2.p, (size_t)s->K * s->d * s->d * 8));
@@ -1762,7 +1518,7 @@ gvi_status gvi_expand(gvi_ctx* ctx, int set_id, const double* mu, const double* 
   s->force_sym = false;
   GVICK(pst);
   hipLaunchKernelGGL(expand_kernel, dim3((unsigned)((s->table->N + 255) / 256), s->K), dim3(256), 0, ctx->stream,
-                     s->dev(), s->in_mu.d(), s->X.d());
+                     s->dev(ctx->opt), s->in_mu.d(), s->X.d());
   HIPCK(ctx, hipGetLastError());
   GVICK(d2h(ctx, X, s->X.p, bytes));
   return sync(ctx);
@@ -1780,8 +1536,9 @@ gvi_status gvi_moments_from_psi(gvi_ctx* ctx, int set_id, const double* mu, cons
   GVICK(h2d(ctx, s->psi_ext.p, psi, bytes));
   s->force_sym = true;                                       // psi was evaluated at the reference's nodes (gvi_expand)
   gvi_status pst = run_prep(ctx, *s, s->in_mu.d(), s->in_Sigma.d());
-  if (pst == GVI_OK) pst = run_moments(ctx, *s, s->in_mu.d(), s->psi_ext.d(), 1);
-  if (pst == GVI_OK) pst = run_epilogue(ctx, *s, 1, s->Ephi.d(), nullptr, s->Vdmu.d(), s->Vddmu.d(), nullptr, nullptr);
+  int nchunk = 1;
+  if (pst == GVI_OK) pst = run_moments(ctx, *s, s->in_mu.d(), s->psi_ext.d(), 1, &nchunk);
+  if (pst == GVI_OK) pst = run_epilogue(ctx, *s, 1, nchunk, s->Ephi.d(), nullptr, s->Vdmu.d(), s->Vddmu.d(), nullptr, nullptr);
   s->force_sym = false;
   GVICK(pst);
   if (Ephi) GVICK(d2h(ctx, Ephi, s->Ephi.p, (size_t)s->K * 8));
@@ -1952,7 +1709,7 @@ static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
   for (auto& s : ctx->sets) {
     if (s->prep_slot == i) continue;
     s->prep_slot = i;
-    L.f[L.nsets] = s->dev();
+    L.f[L.nsets] = s->dev(ctx->opt);
     GVICK(warm_start_of(ctx, *s, L.f[L.nsets]));
     L.mu[L.nsets] = s->mu_k[i].d();
     L.Sigma[L.nsets] = s->Sigma_k[i].d();
@@ -1984,7 +1741,8 @@ static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
 }
 
 // epilogue of every set -- one launch (full: Vdmu / Vddmu / Ephi / cost; else cost only)
-static EpiList make_epi_list(gvi_ctx* ctx, int full, int* dmax_out) {
+// P: the plans of the pass it reduces
+static EpiList make_epi_list(gvi_ctx* ctx, int full, const MomPlan* P, int* dmax_out) {
   EpiList L;
   L.nsets = (int)ctx->sets.size();
   L.koff[0] = 0;
@@ -1992,7 +1750,7 @@ static EpiList make_epi_list(gvi_ctx* ctx, int full, int* dmax_out) {
   for (int si = 0; si < L.nsets; ++si) {
     FactorSet& s = *ctx->sets[si];
     EpiArgs& e = L.e[si];
-    e.f = s.dev(); e.partial = s.partial.d(); e.nchunk = s.nchunk; e.full = full;
+    e.f = s.dev(ctx->opt); e.partial = s.partial.d(); e.nchunk = P[si].nchunk; e.full = full;
     e.Ephi = full ? s.Ephi.d() : nullptr; e.cost = s.cost.d();
     e.Vdmu = full ? s.Vdmu.d() : nullptr; e.Vddmu = full ? s.Vddmu.d() : nullptr;
     e.E_xmuphi = nullptr; e.E_xxphi = nullptr;
@@ -2004,9 +1762,9 @@ static EpiList make_epi_list(gvi_ctx* ctx, int full, int* dmax_out) {
 }
 
 // publish_slot >= 0: the launch also sums the factor costs and publishes the cost of NGD slot `publish_slot` (EpiTail)
-static gvi_status ngd_epilogue_all(gvi_ctx* ctx, int full, int publish_slot = -1) {
+static gvi_status ngd_epilogue_all(gvi_ctx* ctx, int full, const MomPlan* P, int publish_slot = -1) {
   int dmax = 0;
-  const EpiList L = make_epi_list(ctx, full, &dmax);
+  const EpiList L = make_epi_list(ctx, full, P, &dmax);
   const size_t lds = (epilogue_lds_doubles(dmax) + 256) * 8;       // + the tail's 256-leaf tree
   if (L.koff[L.nsets] == 0) return GVI_OK;
   EpiTail tail;
@@ -2074,7 +1832,8 @@ static gvi_status ngd_refresh(gvi_ctx* ctx, int i) {
 // sum over sets of sum_k E[psi]/T_k at slot i -> exch1[0].  Everything stays on ONE stream: side streams
 // share the hardware queue on this part and every cross-stream dependency costs a 6-30 us barrier
 // packet (profiles/r01_d_*); the small sets ride along inside the fused prep / epilogue launches.
-static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full, const MomPlan* P = nullptr);
+static gvi_status plan_sets(gvi_ctx* ctx, int slot, int full, PassPlan* pp);
+static gvi_status ngd_moments_launch(gvi_ctx* ctx, int full, const PassPlan& pp);
 
 // publish = true (single-process iteration): the same launch also writes {cost, half log-det, sequence} to the
 // host-mapped slot, so no separate publish_kernel follows
@@ -2091,7 +1850,9 @@ static gvi_status ngd_cost_local(gvi_ctx* ctx, int i, bool publish = false) {
   }
   if ((int)ctx->sets.size() > MAX_SETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
   GVICK(ngd_prep_all(ctx, i));
-  GVICK(ngd_moments_launch(ctx, i, 0));
+  PassPlan pp;
+  GVICK(plan_sets(ctx, i, 0, &pp));
+  GVICK(ngd_moments_launch(ctx, 0, pp));
   if (publish) ctx->seq += 1.0;
   if (!ctx->tail_counter.p) {
     HIPCK(ctx, ctx->tail_counter.ensure(8));
@@ -2100,7 +1861,7 @@ static gvi_status ngd_cost_local(gvi_ctx* ctx, int i, bool publish = false) {
   int64_t nfac = 0;
   for (auto& s : ctx->sets) nfac = std::max<int64_t>(nfac, s->K);
   const unsigned nblk = (unsigned)std::min<int64_t>(32, std::max<int64_t>(1, (nfac + 255) / 256));
-  hipLaunchKernelGGL(cost_tail_kernel, dim3(nblk), dim3(256), 0, ctx->stream, make_epi_list(ctx, 0, nullptr), g.exch1.d(),
+  hipLaunchKernelGGL(cost_tail_kernel, dim3(nblk), dim3(256), 0, ctx->stream, make_epi_list(ctx, 0, pp.P, nullptr), g.exch1.d(),
                      g.hld[i].d(), publish ? pub_slot(ctx) : nullptr, ctx->seq, (unsigned*)ctx->tail_counter.p);
   HIPCK(ctx, hipGetLastError());
   return GVI_OK;
@@ -2367,53 +2128,51 @@ gvi_status gvi_ngd_factor_costs(gvi_ctx* ctx, int set_id, double* costs) {
   return sync(ctx);
 }
 
-// the chain pattern of the two-set SGPR launches (moments_sreg_pair_kernel / moments_scost_pair_kernel <12, 6, 6, 6>): set 0
-// binary priors d = 12, set 1 unary factors d = 6
-static bool chain_pair_shape(const FactorSet& s0, const FactorSet& s1) {
-  return s0.kind == KIND_QUAD_PRIOR && s1.kind == KIND_FIXED_PRIOR && s0.d == 12 && s1.d == 6;
-}
-
-// the planning graph of the three-set launches (moments_planar3_kernel, factor_block3_kernel): d = 8 priors + d = 4
-// hinge-on-SDF obstacle factors + d = 4 anchors, registered in this order, none empty
-static bool planar_shape(const gvi_ctx* ctx) {
-  if (ctx->sets.size() != 3 || ctx->variant != 0 || ctx->prefer_opsi) return false;
-  const FactorSet &s0 = *ctx->sets[0], &s1 = *ctx->sets[1], &s2 = *ctx->sets[2];
-  return s0.kind == KIND_QUAD_PRIOR && s0.d == 8 && s0.m == 4 && s1.kind == KIND_HINGE_SDF_2D && s1.d == 4 &&
-         s2.kind == KIND_FIXED_PRIOR && s2.d == 4 && !s0.closed_form && !s2.closed_form && s0.K > 0 && s1.K > 0 && s2.K > 0;
-}
-
-// P: [MAX_SETS]
-static gvi_status plan_sets(gvi_ctx* ctx, int slot, int full, MomPlan* P) {
+// every set's decision for a pass of the resident iteration
+static gvi_status decide_sets(gvi_ctx* ctx, int full, PassPlan* pp) {
   if ((int)ctx->sets.size() > MAX_SETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
-  for (size_t i = 0; i < ctx->sets.size(); ++i)
-    GVICK(plan_moments(ctx, *ctx->sets[i], ctx->sets[i]->mu_k[slot].d(), nullptr, full, &P[i]));
+  const RouteRules r = rules_of(ctx);
+  for (size_t i = 0; i < ctx->sets.size(); ++i) {
+    pp->F[i] = route_facts(*ctx->sets[i], false);
+    pp->D[i] = decide_route(pp->F[i], r, full);
+    if (pp->D[i].status != GVI_OK) return fail(ctx, pp->D[i].status, pp->D[i].why);
+  }
   return GVI_OK;
 }
 
-// All sets' moments (full = 1) or cost (full = 0) launches at NGD slot `slot`: every set is planned once (P non-null: by the
-// caller already), then the plans decide.  Two sign-orbit sets of one instance with sgn = +1, the chain pattern on the
-// SGPR-operand kernels (Sreg / Sreg in the full pass, Scost / Scost in the cost pass) and the planning graph on three
-// lane-per-point kernels go out as ONE launch; every other combination as one launch per set.
-static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full, const MomPlan* P) {
+// ... bound at NGD slot `slot`: the sets' launches exactly as they would go out on their own (chunking, table pointers,
+// partial buffers)
+static gvi_status bind_sets(gvi_ctx* ctx, int slot, int full, PassPlan* pp) {
+  for (size_t i = 0; i < ctx->sets.size(); ++i)
+    GVICK(bind_plan(ctx, *ctx->sets[i], pp->D[i], ctx->sets[i]->mu_k[slot].d(), nullptr, full, &pp->P[i]));
+  return GVI_OK;
+}
+
+static gvi_status plan_sets(gvi_ctx* ctx, int slot, int full, PassPlan* pp) {
+  GVICK(decide_sets(ctx, full, pp));
+  return bind_sets(ctx, slot, full, pp);
+}
+
+// All sets' moments (full = 1) or cost (full = 0) launches of a planned pass: decide_fuse (routes.hpp) says which plans go out
+// as ONE launch; every other combination is one launch per set.
+static gvi_status ngd_moments_launch(gvi_ctx* ctx, int full, const PassPlan& pp) {
   if (full) ++ctx->ngd.n_full_pass; else ++ctx->ngd.n_cost_pass;
-  MomPlan own[MAX_SETS];
-  if (!P) { GVICK(plan_sets(ctx, slot, full, own)); P = own; }
-  const size_t ns = ctx->sets.size();
-  const bool fuse = ctx->opt.pair_fuse && !ctx->profile_all;
-  if (fuse && ns == 2) {
-    FactorSet &s0 = *ctx->sets[0], &s1 = *ctx->sets[1];
-    const int smax = std::max(P[0].smax, P[1].smax);
-    ProfBracket b;
-    if (P[0].route == Route::Orbit && P[1].route == Route::Orbit && s0.m == s1.m && s0.all_pos && s1.all_pos &&
-        orbit_pair_supported(s0.m, smax)) {
+  const MomPlan* P = pp.P;
+  const int ns = (int)ctx->sets.size();
+  ProfBracket b;
+  switch (decide_fuse(ns, pp.F, pp.D, rules_of(ctx), ctx->profile_all, full)) {
+    case Fuse::OrbitPair: {
+      FactorSet &s0 = *ctx->sets[0], &s1 = *ctx->sets[1];
       GVICK(prof_open(ctx, s0, 0, full != 0, false, ctx->stream, &b));
-      launch_orbit_pair(P[0].oa, P[1].oa, s0.m, smax, full != 0, ctx->stream, b.e0, b.e1);
+      launch_orbit_pair(P[0].oa, P[1].oa, s0.m, std::max(P[0].smax, P[1].smax), full != 0, ctx->stream, b.e0, b.e1);
       HIPCK(ctx, hipGetLastError());
-      s0.fused_pair = s1.fused_pair = true;
+      record_plan(s0, P[0], true);
+      record_plan(s1, P[1], true);
       return prof_close(ctx, b);
     }
-    const Route want = full ? Route::Sreg : Route::Scost;
-    if (chain_pair_shape(s0, s1) && P[0].route == want && P[1].route == want) {
+    case Fuse::SregPair:
+    case Fuse::ScostPair: {
+      FactorSet &s0 = *ctx->sets[0], &s1 = *ctx->sets[1];
       const MomArgs &a0 = P[0].a, &a1 = P[1].a;
       const int nbx0 = (int)P[0].grid.x, nbx1 = (int)P[1].grid.x;
       const int nb0 = nbx0 * (int)P[0].grid.y, nb1 = nbx1 * (int)P[1].grid.y;
@@ -2426,84 +2185,51 @@ static gvi_status ngd_moments_launch(gvi_ctx* ctx, int slot, int full, const Mom
       else
         hipLaunchKernelGGL((moments_scost_pair_kernel<12, 6, 6, 6, 2>), dim3(nb0 + nb1), dim3(256), 0, ctx->stream, a0, a1, nbx0, nb0, nbx1);
       HIPCK(ctx, hipGetLastError());
-      s0.fused_pair = s1.fused_pair = true;
+      record_plan(s0, P[0], true);
+      record_plan(s1, P[1], true);
       return prof_close(ctx, b);
     }
-  }
-  if (fuse && planar_shape(ctx) && lane_per_point(P[0]) && lane_per_point(P[1]) && lane_per_point(P[2])) {
-    int nbx[3], nb[3];
-    for (int q = 0; q < 3; ++q) {
-      ctx->sets[q]->fused_pair = false;
-      nbx[q] = (ctx->sets[q]->K + 3) / 4;
-      nb[q] = nbx[q] * P[q].a.nchunk;
+    case Fuse::Planar3: {
+      int nbx[3], nb[3];
+      for (int q = 0; q < 3; ++q) {
+        nbx[q] = (ctx->sets[q]->K + 3) / 4;
+        nb[q] = nbx[q] * P[q].nchunk;
+      }
+      GVICK(prof_open(ctx, *ctx->sets[1], 0, full != 0, true, ctx->stream, &b));   // booked on the obstacle set (the dominant one)
+      if (full)
+        hipLaunchKernelGGL((moments_planar3_kernel<true>), dim3(nb[0] + nb[1] + nb[2]), dim3(256), 0, ctx->stream, P[0].a, P[1].a, P[2].a,
+                           nbx[0], nb[0], nbx[1], nb[1], nbx[2], P[0].pipe ? 1 : 0);
+      else
+        hipLaunchKernelGGL((moments_planar3_kernel<false>), dim3(nb[0] + nb[1] + nb[2]), dim3(256), 0, ctx->stream, P[0].a, P[1].a, P[2].a,
+                           nbx[0], nb[0], nbx[1], nb[1], nbx[2], 0);
+      HIPCK(ctx, hipGetLastError());
+      for (int q = 0; q < 3; ++q) record_plan(*ctx->sets[q], P[q], false);
+      return prof_close(ctx, b);
     }
-    ProfBracket b;                                           // the bracket is booked on the obstacle set (the dominant one)
-    GVICK(prof_open(ctx, *ctx->sets[1], 0, full != 0, true, ctx->stream, &b));
-    if (full)
-      hipLaunchKernelGGL((moments_planar3_kernel<true>), dim3(nb[0] + nb[1] + nb[2]), dim3(256), 0, ctx->stream, P[0].a, P[1].a, P[2].a,
-                         nbx[0], nb[0], nbx[1], nb[1], nbx[2], P[0].pipe ? 1 : 0);
-    else
-      hipLaunchKernelGGL((moments_planar3_kernel<false>), dim3(nb[0] + nb[1] + nb[2]), dim3(256), 0, ctx->stream, P[0].a, P[1].a, P[2].a,
-                         nbx[0], nb[0], nbx[1], nb[1], nbx[2], 0);
-    HIPCK(ctx, hipGetLastError());
-    return prof_close(ctx, b);
+    case Fuse::None:
+      break;
   }
-  for (size_t i = 0; i < ns; ++i) {
-    ctx->sets[i]->fused_pair = false;
-    GVICK(launch_single(ctx, *ctx->sets[i], P[i], ctx->stream));
-  }
+  for (int i = 0; i < ns; ++i) GVICK(launch_single(ctx, *ctx->sets[i], P[i], ctx->stream));
   return GVI_OK;
 }
 
-// ---- the full pass as ONE launch (kernels_fused.hpp) ----
-// Blocks that own items: one per factor of the first (heavy) set; a longer second set wraps around (block b also takes its
-// items b + nblk, ...).  0: more than FUSED_MAX_ITEMS items per block would be needed.
-static int fused_nblk(const gvi_ctx* ctx) {
-  const int K0 = ctx->sets[0]->K, K1 = ctx->sets.size() > 1 ? ctx->sets[1]->K : 0;
-  const int nblk = K0;
-  const int per = 1 + (K1 + nblk - 1) / nblk;
-  return per <= FUSED_MAX_ITEMS ? nblk : 0;
-}
-
-// key of the fused instance (with_fused_instance): m and the second dimension of a one-set problem as the chain pattern has them
-struct FusedKey { int m, smax, d0, d1; };
-static FusedKey fused_key(const gvi_ctx* ctx) {
-  FusedKey k{ctx->sets[0]->m, 0, ctx->sets[0]->d, ctx->sets.size() > 1 ? ctx->sets[1]->d : ctx->sets[0]->d / 2};
-  for (auto& sp : ctx->sets) k.smax = std::max(k.smax, sp->table->orb.smax);
-  return k;
-}
-
-static bool fused_ok(const gvi_ctx* ctx, int slot) {
-  if (!ctx->opt.fused || !ctx->opt.pair_fuse || ctx->profile_all || ctx->sets.empty() || ctx->sets.size() > 2) return false;
-  if (ctx->update_rule != GVI_RULE_NGD) return false;     // the JKO map reads the sets' Sigma^-1 after the pass
-  const FusedKey k = fused_key(ctx);
-  for (auto& sp : ctx->sets) {
-    const FactorSet& s = *sp;
-    if (!orbit_supported(ctx, s) || !s.all_pos || s.closed_form || s.K <= 0 || s.m != k.m) return false;
-    if (s.prep_slot == slot) return false;          // products already resident: the plain route skips the prep
-  }
-  if (!with_fused_instance(k.m, k.smax, k.d0, k.d1, any_instance)) return false;
-  for (auto& sp : ctx->sets)
-    if (!sp->dev().chol) return false;              // the instances are compiled for the Cholesky route
-  return fused_nblk(ctx) > 0;
-}
-
-static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot) {
+// ---- the full pass as ONE launch (kernels_fused.hpp), where decide_full says Fused ----
+// It chunks by its own rule: four chunks per factor, one per wave.
+static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot, const PassPlan& pp) {
+  constexpr int fused_chunks = 4;
   FusedArgs A{};
   A.nsets = (int)ctx->sets.size();
   A.koff[0] = 0;
   int dmax = 0, copies = 1;
-  const FusedKey key = fused_key(ctx);
-  A.nblk = fused_nblk(ctx);
+  const FusedKey key = fused_key(A.nsets, pp.F);
+  A.nblk = fused_nblk(pp.F[0].K, A.nsets > 1 ? pp.F[1].K : 0, FUSED_MAX_ITEMS);
   for (int si = 0; si < A.nsets; ++si) {
     FactorSet& s = *ctx->sets[si];
     FusedSet& F = A.s[si];
     s.prep_slot = -1;                      // the fused pass keeps its products in LDS: nothing resident for a later pass
-    s.nchunk = 4; s.chunk = s.table->Np;
-    s.use_reg = s.use_split = false; s.use_orbit = true; s.fused_pair = true;
-    F.f = s.dev();
+    F.f = s.dev(ctx->opt);
     GVICK(warm_start_of(ctx, s, F.f));     // (symmetric-root sets only; the Cholesky route ignores it)
-    GVICK(orbit_args(ctx, s, &F.oa));
+    GVICK(orbit_args(ctx, s, fused_chunks, &F.oa));
     F.oa.partial = nullptr;
     F.mu = s.mu_k[slot].d(); F.Sigma = s.Sigma_k[slot].d();
     F.start = s.chain_structured ? nullptr : (const int32_t*)s.dstart.p;      // null: start[k] == k, one dependent load less
@@ -2533,33 +2259,21 @@ static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot) {
     return fail(ctx, GVI_ERR_UNSUPPORTED, "fused pass: shape not instantiated");
   GVICK(rc);
   HIPCK(ctx, hipGetLastError());
+  for (auto& s : ctx->sets) record_pass(s->last, Route::Orbit, true, fused_chunks, s->table->Np);
   return prof_close(ctx, b);
 }
 
-// ---- the planning graph's full pass as ONE launch (kernels_block.hpp) ----
-// The shape of moments_planar3_kernel (planar_shape, all three on their lane-per-point kernels), at most four chunks per
-// factor (a workgroup's four waves take them), products of this state not resident yet.  *done = false: not this shape -- the
-// caller takes the three launches, with the plans made here where *planned.
-static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, MomPlan* P, bool* planned, bool* done) {
-  *done = *planned = false;
-  if (!ctx->opt.fused || !ctx->opt.pair_fuse || ctx->profile_all || !planar_shape(ctx)) return GVI_OK;
-  if (ctx->update_rule != GVI_RULE_NGD) return GVI_OK;     // the JKO map reads the sets' Sigma^-1 after the pass
-  FactorSet* ss[3] = {ctx->sets[0].get(), ctx->sets[1].get(), ctx->sets[2].get()};
-  for (auto* q : ss)
-    if (q->prep_slot == slot) return GVI_OK;                 // products already resident: the plain route skips the prep
-  if (!ss[0]->dev().chol || ss[1]->dev().chol || !ss[2]->dev().chol) return GVI_OK;     // the products the kernel is compiled for (kernels_block.hpp)
-  // the sets' moments launches exactly as they would go out on their own (chunking, table pointers, partial buffers)
-  GVICK(plan_sets(ctx, slot, 1, P));
-  *planned = true;
-  for (int q = 0; q < 3; ++q)
-    if (!lane_per_point(P[q]) || P[q].a.nchunk > 4) return GVI_OK;
+// ---- the planning graph's full pass as ONE launch (kernels_block.hpp), where decide_full says Block3 ----
+// The sets' moments launches exactly as they would go out on their own (pp), taken by one kernel with prep and epilogue.
+static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, const PassPlan& pp) {
+  const MomPlan* P = pp.P;
   ++ctx->ngd.n_full_pass;
   Block3Args A{};
-  A.nitems = ss[0]->K + ss[1]->K + ss[2]->K;
+  A.nitems = ctx->sets[0]->K + ctx->sets[1]->K + ctx->sets[2]->K;
   A.pipe = P[0].pipe ? 1 : 0;
   unsigned nblk = 0;
   for (int q = 0; q < 3; ++q) {
-    FactorSet& s = *ss[q];
+    FactorSet& s = *ctx->sets[q];
     BlockSet& B = A.s[q];
     B.a = P[q].a;
     GVICK(warm_start_of(ctx, s, B.a.f));       // warm-started Jacobi of the symmetric-root sets, as ngd_prep_all
@@ -2567,36 +2281,44 @@ static gvi_status ngd_block3_full(gvi_ctx* ctx, int slot, int publish_slot, MomP
     B.mu_k = s.mu_k[slot].d(); B.Sigma_k = s.Sigma_k[slot].d();
     B.Ephi = s.Ephi.d(); B.cost = s.cost.d(); B.Vdmu = s.Vdmu.d(); B.Vddmu = s.Vddmu.d();
     A.cl.cost[q] = s.cost.d(); A.cl.K[q] = s.K;
-    nblk += (unsigned)block3_blocks(s.K, B.a.nchunk);
+    nblk += (unsigned)block3_blocks(s.K, P[q].nchunk);
     s.prep_slot = slot;                        // the products go to memory as prep_all_kernel leaves them
-    s.fused_pair = false;
   }
   A.cl.nsets = 3;
   const unsigned extra = take_gather(ctx, slot, A, 256);
   GVICK(fill_epi_tail(ctx, A.nitems, publish_slot, &A.tail));
   ProfBracket b;                               // the bracket is booked on the obstacle set (the dominant one)
-  GVICK(prof_open(ctx, *ss[1], 0, true, true, ctx->stream, &b));
+  GVICK(prof_open(ctx, *ctx->sets[1], 0, true, true, ctx->stream, &b));
   hipLaunchKernelGGL(factor_block3_kernel, dim3(nblk + extra), dim3(256), 4 * block3_lds_doubles() * 8, ctx->stream, A);
   ++block3_launches();
   HIPCK(ctx, hipGetLastError());
-  GVICK(prof_close(ctx, b));
-  *done = true;
-  return GVI_OK;
+  for (int q = 0; q < 3; ++q) record_plan(*ctx->sets[q], P[q], false);
+  return prof_close(ctx, b);
 }
 
+// the full pass at NGD slot `slot`: decide every set, decide_full, then one switch that launches
 static gvi_status ngd_moments_full(gvi_ctx* ctx, int slot, int publish_slot = -1) {
-  if ((int)ctx->sets.size() > MAX_SETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
   for (auto& s : ctx->sets)
     if (psi_kind_is<PSI_NO_DEVICE>(s->kind)) return fail(ctx, GVI_ERR_UNSUPPORTED, "resident NGD needs device psi kinds");
   StageScope scope(ctx, STAGE_FACTORS);
-  if (fused_ok(ctx, slot)) return ngd_fused_full(ctx, slot, publish_slot);
-  MomPlan plans[MAX_SETS];
-  bool planned = false, done = false;
-  GVICK(ngd_block3_full(ctx, slot, publish_slot, plans, &planned, &done));
-  if (done) return GVI_OK;
+  PassPlan pp;
+  GVICK(decide_sets(ctx, 1, &pp));
+  const int ns = (int)ctx->sets.size();
+  bool resident[MAX_SETS];                     // products of this state already there: the plain route skips the prep
+  for (int i = 0; i < ns; ++i) resident[i] = ctx->sets[i]->prep_slot == slot;
+  switch (decide_full(ns, pp.F, pp.D, resident, rules_of(ctx), ctx->profile_all, ctx->update_rule == GVI_RULE_NGD, FUSED_MAX_ITEMS)) {
+    case FullFuse::Fused:
+      return ngd_fused_full(ctx, slot, publish_slot, pp);
+    case FullFuse::Block3:
+      GVICK(bind_sets(ctx, slot, 1, &pp));
+      return ngd_block3_full(ctx, slot, publish_slot, pp);
+    case FullFuse::Separate:
+      break;
+  }
   GVICK(ngd_prep_all(ctx, slot));
-  GVICK(ngd_moments_launch(ctx, slot, 1, planned ? plans : nullptr));
-  return ngd_epilogue_all(ctx, 1, publish_slot);
+  GVICK(bind_sets(ctx, slot, 1, &pp));
+  GVICK(ngd_moments_launch(ctx, 1, pp));
+  return ngd_epilogue_all(ctx, 1, pp.P, publish_slot);
 }
 
 // the gradient solve is parked and goes out beside the next trial factorisation, as the dual launch (ngd_trial_state);
@@ -3161,7 +2883,7 @@ gvi_status gvi_prox_gradients(gvi_ctx* ctx, double h) {
     a.K = s.K; a.d = s.d; a.h = h; a.Vdmu = s.Vdmu.d(); a.Vddmu = s.Vddmu.d(); a.Sigma = s.Sigma_k[g.cur].d();
     a.Lam = s.Lam.d(); a.Shalf = s.jko_half.d(); a.LamNew = s.jko_Lam.d();
     hipLaunchKernelGGL(jko_half_kernel, dim3(s.K), dim3(64), 3 * dd * 8, ctx->stream, a);
-    FactorDev f = s.dev();                                 // spectral map of Sig_half into scratch (no psi operands)
+    FactorDev f = s.dev(ctx->opt);                         // spectral map of Sig_half into scratch (no psi operands)
     f.m = 0; f.S = s.jko_S.d(); f.Sinv = s.jko_Sinv.d(); f.Lam = s.jko_Lam.d(); f.H = nullptr; f.Hq = nullptr; f.u0 = nullptr;
     f.jko_h = h;
     f.chol = 0;                                            // the JKO map is a function of the eigenvalues
@@ -3432,9 +3154,9 @@ gvi_status gvi_profile_stages(gvi_ctx* ctx, int on, float* mean_us, int* counts)
 gvi_status gvi_profile_geometry(gvi_ctx* ctx, int set_id, int* variant, int* nchunk, int64_t* chunk) {
   FactorSet* s = get_set(ctx, set_id);
   if (!s) return GVI_ERR_ARG;
-  if (variant) *variant = s->closed_form ? 0 : (s->use_opsi ? 7 : s->use_orbit ? 6 : (s->fused_pair ? 5 : (s->use_reg ? 2 : (s->use_split ? 3 : 1))));
-  if (nchunk) *nchunk = s->nchunk;
-  if (chunk) *chunk = s->chunk;
+  if (variant) *variant = geometry_code(s->last.route, s->last.fused_pair, s->closed_form);
+  if (nchunk) *nchunk = s->last.nchunk;
+  if (chunk) *chunk = s->last.chunk;
   return GVI_OK;
 }
 
@@ -3448,7 +3170,7 @@ gvi_status gvi_set_option(gvi_ctx* ctx, const char* name, int value) {
   // what a switch owes the context beyond its field
   if (n == "safe_publish") for (int q = 0; q < 16; ++q) ctx->host_slot[q] = 0.0;       // the two forms lay the slot out differently
   if (n == "chain_merge") ctx->opt.chain_merge_fault = value == 2;
-  for (auto& s : ctx->sets) { s->use_chol = ctx->opt.chol_sqrt; s->jtol = ctx->opt.jacobi_tol; s->prep_slot = -1; }
+  for (auto& s : ctx->sets) s->prep_slot = -1;
   ngd_invalidate(ctx);
   return GVI_OK;
 }
@@ -3499,11 +3221,7 @@ gvi_status gvi_debug_products(gvi_ctx* ctx, int set_id, double* S, double* Sinv,
 }
 
 gvi_status gvi_set_variant(gvi_ctx* ctx, int variant) {
-  if (!ctx || variant < 0 || variant > 7 || variant == 3 || variant == 4) return GVI_ERR_ARG;
-  // 7 = auto, but the non-polynomial psi kinds take the sign-orbit kernel also where a register kernel exists
-  ctx->prefer_opsi = variant == 7;
-  ctx->variant = variant == 7 ? 0 : variant;
-  return GVI_OK;
+  return ctx && route_force_of_variant(variant, &ctx->force) ? GVI_OK : GVI_ERR_ARG;
 }
 
 }  // extern "C"

@@ -125,11 +125,11 @@ constexpr OptionRow OPTION_ROWS[] = {
   opt_flag("mirror", "GVI_MIRROR", &Options::mirror),
   opt_flag("safe_publish", "GVI_SAFE_PUBLISH", &Options::safe_publish),    // (option: gvi_set_option drains the stream and resets the slot)
   opt_min(nullptr, "GVI_SPIN_MS", &Options::spin_ms, 0),
-  opt_flag("chol_sqrt", nullptr, &Options::chol_sqrt),                     // (gvi_set_option copies it into the sets)
+  opt_flag("chol_sqrt", nullptr, &Options::chol_sqrt),
   opt_flag("sample_sweep", nullptr, &Options::sample_sweep),
   opt_flag("solve_lds", nullptr, &Options::solve_lds),
   opt_flag("trust_table_degree", nullptr, &Options::trust_table_degree),
-  opt_pow10("jacobi_tol_exp", &Options::jacobi_tol, -20),                  // (gvi_set_option copies it into the sets)
+  opt_pow10("jacobi_tol_exp", &Options::jacobi_tol, -20),
   opt_min("split_flush", nullptr, &Options::split_flush, 0),
   opt_min("target_waves", nullptr, &Options::target_waves, 1),
   opt_min("orbit_waves", nullptr, &Options::orbit_waves, 1),

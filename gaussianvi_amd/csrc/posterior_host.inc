@@ -502,7 +502,7 @@ static gvi_status run_sample_cost(gvi_ctx* c, int lo, int hi, int S, const doubl
     koff += s.K;
     if (s.K == 0 || (!cp && !kp)) continue;
     const int j = L.nsets++;
-    L.f[j] = s.dev(); L.start[j] = s.dstart.i();
+    L.f[j] = s.dev(c->opt); L.start[j] = s.dstart.i();
     L.cost[j] = cp; L.clr[j] = kp; L.ld_cost[j] = ld; L.ld_clr[j] = ld_clr;
     L.boff[j] = (int)nb;
     if (psi_kind_is<PSI_SUMSQ>(s.kind)) {

@@ -2,7 +2,7 @@
 // about a kind -- its operand rows m, the size of its parameter block, the condition on the factor dimension and what it
 // keeps, reads and offers.  gvi_factors_add lays a set out with psi_kind_layout and checks the values of its parameter
 // blocks with psi_kind_check_params; every other site asks psi_kind_is.  A new kind is one row here, its psi_* function in
-// kernels_factor.hpp (psi_point) and, where it has compiled instances, a line in the with_*_instance lists of gvi_hip.hip.
+// kernels_factor.hpp (psi_point) and, where it has compiled instances, a line in the with_*_instance lists of routes.hpp.
 // Plain C++17 that also compiles without HIP (tests/stubs/psi_kinds_check.cpp runs it under AddressSanitizer / UBSan).
 #pragma once
 #include <math.h>
