@@ -14,6 +14,7 @@ PSI_HINGE_SDF_2D_BODY, PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM = 5, 6, 7
 PSI_HINGE_SDF_2D_SEG, PSI_HINGE_SDF_3D_SEG = 8, 9
 PSI_HINGE_BOX = 10
 PSI_HINGE_HALFSPACE = 11
+PSI_HINGE_BALLS_2D, PSI_HINGE_BALLS_3D = 13, 14       # 12 is not a kind
 RULE_NGD, RULE_PROX_JKO = 0, 1
 GVI_F64, GVI_F32 = 0, 1
 
@@ -206,6 +207,13 @@ class Context:
 
     def factors_set_temperature(self, sid, temperature):
         self._ck(self.lib.gvi_factors_set_temperature(self.h, sid, _p(_f64(temperature))))
+
+    def factors_set_params(self, sid, params):
+        """Replace the parameter blocks [K][params_per_factor] of a set that keeps them (gvi_factors_set_params): the layout --
+        block size and J -- stays the one of factors_add."""
+        K = self.sets[sid][0]
+        params = _f64(params).reshape(K, -1) if K else np.zeros((0, 1))
+        self._ck(self.lib.gvi_factors_set_params(self.h, sid, _p(params), params.shape[1]))
 
     # ---- per-pass factor operators (host buffers) ----
     def moments(self, sid, mu, Sigma):

@@ -74,7 +74,7 @@ def build_examples(force: bool = False) -> str:
     os.makedirs(out_dir, exist_ok=True)
     first = None
     for name in ("1d_example", "1d_example_prox", "planar_example", "factorwise_example", "ltv_chain_example", "planar_limits_example",
-                 "planar_corridor_example"):
+                 "planar_corridor_example", "planar_moving_example"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         exe = os.path.join(out_dir, name)
         deps = [src, os.path.join(ROOT, "include", "gvi", "gvi_host.hpp"), os.path.join(ROOT, "include", "gvi", "factorized_opts_LTV.hpp"),

@@ -1420,6 +1420,30 @@ gvi_status gvi_factors_set_temperature(gvi_ctx* ctx, int set_id, const double* t
   return GVI_OK;
 }
 
+// The PSI_RAW kinds keep their blocks as gvi_factors_add uploaded them and nothing derived from the VALUES is cached (seg_J and
+// raw_stride are layout), so new blocks are one copy; the sum-of-squares kinds build (A, b, sgn) from theirs at gvi_factors_add.
+gvi_status gvi_factors_set_params(gvi_ctx* ctx, int set_id, const double* psi_params, int64_t params_per_factor) {
+  FactorSet* s = get_set(ctx, set_id);
+  if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
+  if (!psi_kind_is<PSI_RAW>(s->kind)) return fail(ctx, GVI_ERR_ARG, "gvi_factors_set_params: only the kinds that keep their parameter block");
+  int m = 0, J = 0;
+  int64_t need = 0;
+  const char* why = nullptr;
+  // a block size the kind itself refuses is another layout too; the values' own refusals keep their texts below
+  if (psi_kind_layout(s->kind, s->d, params_per_factor, &m, &J, &need, &why) != GVI_OK || J != s->seg_J || need != s->raw_stride)
+    return fail(ctx, GVI_ERR_ARG, "gvi_factors_set_params: the layout of a set is fixed at gvi_factors_add");
+  if (gvi_status rc = psi_kind_check_params(s->kind, s->d, J, params_per_factor, s->K, psi_params, &why)) return fail(ctx, rc, why);
+  if (s->K == 0) return GVI_OK;
+  const int np = s->raw_stride;
+  std::vector<double> raw((size_t)s->K * np);
+  for (int k = 0; k < s->K; ++k) memcpy(&raw[(size_t)k * np], psi_params + (size_t)k * params_per_factor, (size_t)np * 8);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  GVICK(sync(ctx));
+  HIPCK(ctx, hipMemcpy(s->raw.p, raw.data(), raw.size() * 8, hipMemcpyHostToDevice));
+  ngd_invalidate(ctx);
+  return GVI_OK;
+}
+
 gvi_status gvi_factors_info(const gvi_ctx* ctx, int set_id, int* K, int* d, int* p, int64_t* N) {
   FactorSet* s = get_set(const_cast<gvi_ctx*>(ctx), set_id);
   if (!s) return GVI_ERR_ARG;

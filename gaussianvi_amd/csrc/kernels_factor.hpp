@@ -34,6 +34,7 @@
 
 #include <utility>
 
+#include "balls_psi.hpp"
 #include "box_moments.hpp"
 #include "device_common.hpp"
 #include "dpp_rowb.hpp"
@@ -1033,6 +1034,8 @@ __device__ __forceinline__ double psi_point(const FactorDev& f, int k, const dou
   if (f.kind == KIND_HINGE_SDF_3D_SEG) return psi_hinge_sdf3d_seg(f, p, x, f.d);
   if (f.kind == KIND_HINGE_BOX) return psi_hinge_box(p, x, f.d);
   if (f.kind == KIND_HINGE_HALFSPACE) return psi_hinge_halfspace(p, x, f.d, f.seg_J);
+  if (f.kind == KIND_HINGE_BALLS_2D) return psi_hinge_balls<2>(p, x, f.d, f.seg_J);
+  if (f.kind == KIND_HINGE_BALLS_3D) return psi_hinge_balls<3>(p, x, f.d, f.seg_J);
   return __builtin_nan("");
 }
 
@@ -1053,6 +1056,8 @@ __device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, c
   else if (f.kind == KIND_HINGE_SDF_3D_SEG) hinge_sdf3d_seg_points(f, p, x, f.d, keep);
   else if (f.kind == KIND_HINGE_BOX) c = box_margin(p, x, f.d);                        // limits on the slice itself (box_moments.hpp): the margin
   else if (f.kind == KIND_HINGE_HALFSPACE) c = halfspace_margin(p, x, f.d, f.seg_J);   // rows a_j^T x <= b_j (halfspace_moments.hpp): distance to the nearest active face
+  else if (f.kind == KIND_HINGE_BALLS_2D) hinge_balls_points<2>(p, x, f.d, f.seg_J, keep);   // analytic balls (balls_psi.hpp): no grid
+  else if (f.kind == KIND_HINGE_BALLS_3D) hinge_balls_points<3>(p, x, f.d, f.seg_J, keep);
   else c = __builtin_nan("");   // no clearance for this kind: the host refuses such a set before any launch
   clr = c;
 }
@@ -1481,6 +1486,112 @@ struct PsiHingeSeg {
     return cost;
   }
 };
+
+// Moving balls (hinge_balls_points, balls_psi.hpp).  As for PsiHingeSeg, load forms G_j = W_j S and
+// g_j = W_j mu + c_j once per (factor, chunk), so eval pays P D FMAs per check point and never forms x.  load also COMPACTS the
+// slots: the M non-empty ones come first, M is wave-uniform, and eval's loop over balls runs M times.  The centres
+// o_m + tau_j v_m are formed in load per (check point, active ball) -- 64 P doubles of LDS at most instead of P FMAs per
+// (sigma point, check point, ball) in eval.  Per active ball eval forms the squared distance and compares it with
+// (eps + r + R_m)^2; only inside that branch is the fp64 square root taken, and the value is hinge_sq's own clamp of
+// eps + r - (sqrt(dist^2) - R_m): the pretest skips work, it decides nothing.  No grid pointer is touched.
+// hs: [SEG_MAX_J][P (D + 1)] = (G_j [P][D] | g_j [P]) | sigma, eps + r, M, - | [BALLS_SLOTS] (R_m, (eps + r + R_m)^2) |
+//     [SEG_MAX_J][BALLS_SLOTS][P] centres.
+template <int D, int P>
+struct PsiHingeBalls {
+  static constexpr int STRIDE = P * (D + 1);
+  static constexpr int HEAD = SEG_MAX_J * STRIDE;
+  static constexpr int RB = HEAD + 4;
+  static constexpr int CEN = RB + 2 * BALLS_SLOTS;
+  static constexpr int LDS = CEN + SEG_MAX_J * BALLS_SLOTS * P;
+  static constexpr bool GUARD = false;
+  static_assert(SEG_MAX_J * BALLS_SLOTS <= 64, "load places one (check point, slot) pair per lane");
+  static_assert((4 * LDS + 4 * 16 * 65) * 8 < 64 * 1024, "static LDS of a block of moments_reg_kernel");
+  __device__ static void load(const MomArgs& a, int k, double* hs, int lane) {
+    const double* raw = a.f.raw + (size_t)k * a.f.raw_stride;
+    const double* S = a.f.S + (size_t)k * D * D;
+    const double* mu = a.mu + (size_t)k * D;
+    const int J = a.f.seg_J < SEG_MAX_J ? a.f.seg_J : SEG_MAX_J;      // the host admits 1 .. SEG_MAX_J; keeps the LDS slice
+    for (int e = lane; e < J * STRIDE; e += 64) {
+      const int j = e / STRIDE, rem = e - j * STRIDE;
+      const double* Wj = raw + 3 + j * (STRIDE + 1);
+      double v;
+      if (rem < P * D) {                                              // G_j[r][c] = sum_e W_j[r][e] S[e][c]
+        const int r = rem / D, c = rem - r * D;
+        v = 0.0;
+#pragma unroll
+        for (int q = 0; q < D; ++q) v = fma(Wj[r * D + q], S[q * D + c], v);
+      } else {                                                        // g_j[r] = c_j[r] + W_j[r] mu
+        const int r = rem - P * D;
+        v = Wj[P * D + r];
+#pragma unroll
+        for (int q = 0; q < D; ++q) v = fma(Wj[r * D + q], mu[q], v);
+      }
+      hs[e] = v;
+    }
+    const double* balls = raw + 3 + J * (STRIDE + 1);
+    const double thr = raw[1] + raw[2];
+    if (lane < J * BALLS_SLOTS) {                                     // lane = (check point j, slot m)
+      const int j = lane / BALLS_SLOTS, m = lane - j * BALLS_SLOTS;
+      const double* b = balls + m * (2 * P + 1);
+      const double R = b[2 * P];
+      if (!balls_slot_empty(R)) {
+        int rank = 0;                                                 // non-empty slots before m
+        for (int q = 0; q < m; ++q) rank += balls_slot_empty(balls[q * (2 * P + 1) + 2 * P]) ? 0 : 1;
+        const double tau = raw[3 + j * (STRIDE + 1) + STRIDE];
+#pragma unroll
+        for (int r = 0; r < P; ++r) hs[CEN + (j * BALLS_SLOTS + rank) * P + r] = fma(tau, b[P + r], b[r]);
+        if (j == 0) {
+          const double t = thr + R;                                   // t <= 0: no distance is below it
+          hs[RB + 2 * rank] = R;
+          hs[RB + 2 * rank + 1] = t > 0.0 ? t * t : -1.0;
+        }
+      }
+    }
+    if (lane == 0) {
+      int M = 0;
+      for (int q = 0; q < BALLS_SLOTS; ++q) M += balls_slot_empty(balls[q * (2 * P + 1) + 2 * P]) ? 0 : 1;
+      hs[HEAD] = raw[0];
+      hs[HEAD + 1] = thr;
+      hs[HEAD + 2] = (double)M;
+    }
+  }
+  __device__ static double eval(const double (&z)[D], const double* hs, const MomArgs& a) {
+    const double sigma = hs[HEAD], thr = hs[HEAD + 1];
+    const int M = __builtin_amdgcn_readfirstlane((int)hs[HEAD + 2]);
+    const int J = a.f.seg_J < SEG_MAX_J ? a.f.seg_J : SEG_MAX_J;
+    double cost = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < J; ++j) {
+      const double* G = hs + j * STRIDE;
+      double q[P];
+#pragma unroll
+      for (int r = 0; r < P; ++r) {
+        double v = G[P * D + r];
+#pragma unroll
+        for (int c = 0; c < D; ++c) v = fma(G[r * D + c], z[c], v);
+        q[r] = v;
+      }
+      const double* cen = hs + CEN + j * BALLS_SLOTS * P;
+      double sd = INFINITY;
+#pragma unroll 1
+      for (int m = 0; m < M; ++m) {
+        double d2 = 0.0;
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+          const double e = q[r] - cen[m * P + r];
+          d2 = fma(e, e, d2);
+        }
+        if (d2 < hs[RB + 2 * m + 1]) sd = fmin(sd, sqrt(d2) - hs[RB + 2 * m]);
+      }
+      cost += hinge_sq(sd, thr, 1.0, sigma);
+    }
+    return cost;
+  }
+};
+// The tag the instance lists hand out for a hinge on a signed distance is PsiHingeSdf<D, KIND> (routes.hpp); for the two
+// analytic kinds it IS the policy above.
+template <int D> struct PsiHingeSdf<D, KIND_HINGE_BALLS_2D> : PsiHingeBalls<D, 2> {};
+template <int D> struct PsiHingeSdf<D, KIND_HINGE_BALLS_3D> : PsiHingeBalls<D, 3> {};
 
 // Limits on the slice itself (HINGE_BOX, box_moments.hpp).  hs: S [D][D] | mu [D] | sigma [D] | upper threshold hi - eps [D] |
 // lower threshold lo + eps [D], an infinite threshold for a side that is off.  eval forms x_i = mu_i + s_i z only for a

@@ -23,11 +23,15 @@ enum { KIND_RANGE_1D = GVI_PSI_RANGE_1D, KIND_QUAD_PRIOR = GVI_PSI_QUAD_PRIOR, K
        KIND_HINGE_SDF_2D_BODY = GVI_PSI_HINGE_SDF_2D_BODY, KIND_HINGE_SDF_3D = GVI_PSI_HINGE_SDF_3D,
        KIND_HINGE_SDF_3D_ARM = GVI_PSI_HINGE_SDF_3D_ARM, KIND_HINGE_SDF_2D_SEG = GVI_PSI_HINGE_SDF_2D_SEG,
        KIND_HINGE_SDF_3D_SEG = GVI_PSI_HINGE_SDF_3D_SEG, KIND_HINGE_BOX = GVI_PSI_HINGE_BOX,
-       KIND_HINGE_HALFSPACE = GVI_PSI_HINGE_HALFSPACE, KIND_COUNT = 12 };
+       KIND_HINGE_HALFSPACE = GVI_PSI_HINGE_HALFSPACE, KIND_HINGE_BALLS_2D = GVI_PSI_HINGE_BALLS_2D,
+       KIND_HINGE_BALLS_3D = GVI_PSI_HINGE_BALLS_3D, KIND_COUNT = 15 };
+// 12 is a hole: the host tests of this table and of routes.hpp pin it as the first number that is NO kind, so it stays unassigned
+constexpr int KIND_HOLE = 12;
 
 constexpr int SEG_MAX_J = GVI_SEG_MAX_J;               // check points of one HINGE_SDF_*_SEG factor
 constexpr int HALFSPACE_MAX_J = GVI_HALFSPACE_MAX_J;   // rows of one HINGE_HALFSPACE factor
-static_assert(SEG_MAX_J == 8 && HALFSPACE_MAX_J == 16, "the refusal texts of psi_kind_layout spell the limits out");
+constexpr int BALLS_MAX_M = GVI_BALLS_MAX_M;           // ball slots of one HINGE_BALLS_* factor (its check points: SEG_MAX_J)
+static_assert(SEG_MAX_J == 8 && HALFSPACE_MAX_J == 16 && BALLS_MAX_M == 8, "the refusal texts of psi_kind_layout spell the limits out");
 
 // what a kind keeps, reads and offers
 enum : unsigned {
@@ -51,7 +55,8 @@ enum PsiNeed {
   NEED_MEAN_QUAD,   // [mu0 (d) | Qinv (d x d)]: d + d^2
   NEED_SEG,         // exactly 3 + J P (d + 1), P = `arg`, 1 <= J <= SEG_MAX_J: J is a property of the set
   NEED_BOX,         // exactly 4 d: [sigma | eps | lo | hi]
-  NEED_HALFSPACE    // exactly J (d + 3), 1 <= J <= HALFSPACE_MAX_J: J is a property of the set
+  NEED_HALFSPACE,   // exactly J (d + 3), 1 <= J <= HALFSPACE_MAX_J: J is a property of the set
+  NEED_BALLS        // exactly 3 + J (P (d + 1) + 1) + BALLS_MAX_M (2 P + 1), P = `arg`, 1 <= J <= SEG_MAX_J: J is a property of the set
 };
 enum PsiDim { D_ANY, D_ONE, D_EVEN, D_MIN };   // D_MIN: d >= `dmin`
 
@@ -79,7 +84,11 @@ constexpr PsiKindRow PSI_KINDS[KIND_COUNT] = {
   {KIND_HINGE_SDF_3D_SEG, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE, M_NONE, NEED_SEG, 3, D_ANY, 0, nullptr},
   {KIND_HINGE_BOX, PSI_RAW | PSI_CLEARANCE | PSI_CLOSED | PSI_CLOSED_DEFAULT, M_NONE, NEED_BOX, 0, D_ANY, 0, nullptr},
   {KIND_HINGE_HALFSPACE, PSI_RAW | PSI_CLEARANCE | PSI_CLOSED | PSI_CLOSED_DEFAULT, M_NONE, NEED_HALFSPACE, 0, D_ANY, 0, nullptr},
+  {KIND_HOLE, 0, M_NONE, NEED_FIXED, 0, D_ANY, 0, nullptr},
+  {KIND_HINGE_BALLS_2D, PSI_RAW | PSI_CLEARANCE, M_NONE, NEED_BALLS, 2, D_ANY, 0, nullptr},
+  {KIND_HINGE_BALLS_3D, PSI_RAW | PSI_CLEARANCE, M_NONE, NEED_BALLS, 3, D_ANY, 0, nullptr},
 };
+constexpr bool psi_kind_known(int kind) { return kind >= 0 && kind < KIND_COUNT && kind != KIND_HOLE; }
 
 constexpr bool psi_kinds_in_order() {
   for (int i = 0; i < KIND_COUNT; ++i)
@@ -109,7 +118,7 @@ GVI_KIND_HD constexpr bool psi_kind_is(int kind) {
 // in *msg where the kind, d or the block size is refused.
 inline gvi_status psi_kind_layout(int kind, int d, int64_t params_per_factor, int* m, int* J, int64_t* need, const char** msg) {
   *m = 0; *J = 0; *need = 0; *msg = nullptr;
-  if (kind < 0 || kind >= KIND_COUNT) { *msg = "unknown psi kind"; return GVI_ERR_ARG; }
+  if (!psi_kind_known(kind)) { *msg = "unknown psi kind"; return GVI_ERR_ARG; }
   const PsiKindRow& r = PSI_KINDS[kind];
   if ((r.dim == D_ONE && d != 1) || (r.dim == D_EVEN && d % 2 != 0) || (r.dim == D_MIN && d < r.dmin)) { *msg = r.dim_msg; return GVI_ERR_ARG; }
   *m = r.rows == M_HALF_D ? d / 2 : r.rows == M_D ? d : 0;
@@ -142,6 +151,17 @@ inline gvi_status psi_kind_layout(int kind, int d, int64_t params_per_factor, in
       *need = params_per_factor;
       break;
     }
+    case NEED_BALLS: {
+      const int64_t per = (int64_t)r.arg * (d + 1) + 1, body = params_per_factor - 3 - BALLS_MAX_M * (2 * (int64_t)r.arg + 1);
+      if (body < per || body % per != 0 || body / per > SEG_MAX_J) {
+        *msg = "HINGE_BALLS_* needs params_per_factor = 3 + J (P (d + 1) + 1) + 8 (2 P + 1) with 1 <= J <= 8 check points "
+               "(P = 2 for _2D, 3 for _3D)";
+        return GVI_ERR_ARG;
+      }
+      *J = (int)(body / per);
+      *need = params_per_factor;
+      break;
+    }
   }
   if (params_per_factor < *need) { *msg = "psi_params missing or params_per_factor too small for this kind"; return GVI_ERR_ARG; }
   return GVI_OK;
@@ -152,7 +172,7 @@ inline gvi_status psi_kind_layout(int kind, int d, int64_t params_per_factor, in
 inline gvi_status psi_kind_check_params(int kind, int d, int J, int64_t params_per_factor, int64_t K, const double* params, const char** msg) {
   *msg = nullptr;
   auto refuse = [&](const char* text) -> gvi_status { *msg = text; return GVI_ERR_ARG; };
-  if (kind < 0 || kind >= KIND_COUNT) return refuse("unknown psi kind");
+  if (!psi_kind_known(kind)) return refuse("unknown psi kind");
   const PsiNeed need = PSI_KINDS[kind].need;
   if (!params && !(need == NEED_FIXED && PSI_KINDS[kind].arg == 0)) return refuse("psi_params missing or params_per_factor too small for this kind");
   if (need == NEED_BOX) {
@@ -183,6 +203,27 @@ inline gvi_status psi_kind_check_params(int kind, int d, int J, int64_t params_p
           zero = zero && v == 0.0;
         }
         if (zero && P[j] > 0.0) return refuse("HINGE_HALFSPACE: an active row (sigma > 0) needs a non-zero normal a_j");
+      }
+    }
+  }
+  if (need == NEED_BALLS) {
+    const int P = PSI_KINDS[kind].arg;
+    const int64_t per = (int64_t)P * (d + 1) + 1, slot = 2 * (int64_t)P + 1;
+    for (int64_t k = 0; k < K; ++k) {
+      const double* B = params + k * params_per_factor;
+      for (int64_t e = 0; e < params_per_factor; ++e)
+        if (isnan(B[e])) return refuse("HINGE_BALLS: NaN in the parameter block");
+      if (!isfinite(B[0]) || B[0] < 0.0) return refuse("HINGE_BALLS: sigma must be finite and >= 0");
+      if (!isfinite(B[1]) || !isfinite(B[2])) return refuse("HINGE_BALLS: eps and r must be finite");
+      for (int64_t e = 3; e < 3 + J * per; ++e)
+        if (!isfinite(B[e])) return refuse("HINGE_BALLS: W, c and tau must be finite");
+      const double* ball = B + 3 + J * per;
+      for (int m = 0; m < BALLS_MAX_M; ++m, ball += slot) {
+        const double R = ball[2 * P];
+        if (R == -INFINITY) continue;             // an empty slot: never evaluated
+        if (!isfinite(R) || R < 0.0) return refuse("HINGE_BALLS: a radius is finite and >= 0, or -inf for an empty slot");
+        for (int e = 0; e < 2 * P; ++e)
+          if (!isfinite(ball[e])) return refuse("HINGE_BALLS: a ball needs a finite centre and velocity");
       }
     }
   }

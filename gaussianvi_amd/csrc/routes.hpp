@@ -68,6 +68,19 @@ bool with_reg_instance(int kind, int d, int m, F&& f) {
     case KIND_HINGE_SDF_3D_SEG:   // d = 12: 256 VGPRs + 18 AGPR copies under launch_bounds(256) -> generic kernel
       if (d == 6) return hit(f, RegInst<6, PsiHingeSeg<6, 3>>{});
       break;
+    // analytic balls: the policy is PsiHingeBalls<D, P> (kernels_factor.hpp), handed out under the tag of every hinge on a
+    // signed distance, PsiHingeSdf<D, KIND>.  Every listed instance compiles without scratch or spills
+    case KIND_HINGE_BALLS_2D:
+      if (d == 2) return hit(f, RegInst<2, PsiHingeSdf<2, KIND_HINGE_BALLS_2D>>{});
+      if (d == 4) return hit(f, RegInst<4, PsiHingeSdf<4, KIND_HINGE_BALLS_2D>>{});
+      if (d == 8) return hit(f, RegInst<8, PsiHingeSdf<8, KIND_HINGE_BALLS_2D>>{});
+      if (d == 12) return hit(f, RegInst<12, PsiHingeSdf<12, KIND_HINGE_BALLS_2D>>{});
+      break;
+    case KIND_HINGE_BALLS_3D:
+      if (d == 3) return hit(f, RegInst<3, PsiHingeSdf<3, KIND_HINGE_BALLS_3D>>{});
+      if (d == 6) return hit(f, RegInst<6, PsiHingeSdf<6, KIND_HINGE_BALLS_3D>>{});
+      if (d == 12) return hit(f, RegInst<12, PsiHingeSdf<12, KIND_HINGE_BALLS_3D>>{});
+      break;
     case KIND_HINGE_BOX:          // above d = 8 the accumulators leave no room: generic kernel, or the closed form
       if (d == 2) return hit(f, RegInst<2, PsiBoxHinge<2>>{});
       if (d == 4) return hit(f, RegInst<4, PsiBoxHinge<4>>{});

@@ -10,6 +10,7 @@ the C-ABI works on.  psi parameter blocks use the C-ABI layouts of include/gvi_h
   HINGE_SDF_2D_SEG / _3D_SEG  [sigma, eps, r | W_0 (P x d) | c_0 (P) | ... ]   d = n or 2n   (segment_params)
   HINGE_BOX   [sigma (d) | eps (d) | lo (d) | hi (d)]          d = n or 2n   (box_params)
   HINGE_HALFSPACE  [sigma (J) | eps (J) | b (J) | A (J x d)]   d = n or 2n   (halfspace_params)
+  HINGE_BALLS_2D / _3D  [sigma, eps, r | J x (W_j | c_j | tau_j) | 8 x (o_m | v_m | R_m)]   d = n or 2n   (balls_params)
 """
 from __future__ import annotations
 
@@ -20,6 +21,8 @@ PSI_HINGE_SDF_2D_BODY, PSI_HINGE_SDF_3D, PSI_HINGE_SDF_3D_ARM = 5, 6, 7
 PSI_HINGE_SDF_2D_SEG, PSI_HINGE_SDF_3D_SEG = 8, 9
 PSI_HINGE_BOX = 10
 PSI_HINGE_HALFSPACE = 11
+PSI_HINGE_BALLS_2D, PSI_HINGE_BALLS_3D = 13, 14       # 12 is not a kind
+BALLS_MAX_M = 8           # ball slots of one HINGE_BALLS_* factor
 
 CONFIGS = {
     # name: (cfg#, T, n, p, prior kind)
@@ -206,6 +209,64 @@ def add_corridor_set(chain, normals, offsets, sigma=10.0, eps=0.05, p=3, pair=Fa
         A[:, :, :npos] = N
         b = B
     spec = dict(kind=PSI_HINGE_HALFSPACE, d=d, p=p, start=np.arange(K, dtype=np.int32), params=halfspace_params(sigma, eps, b, A),
+                temperature=np.full(K, float(temperature)))
+    return dict(chain, specs=list(chain["specs"]) + [spec])
+
+
+def balls_params(sigma, eps, r, W, c, tau, centres, velocities, radii):
+    """Parameter blocks [K][3 + J (P (d + 1) + 1) + 8 (2 P + 1)] of a HINGE_BALLS_2D / _3D set:
+    [sigma, eps, r | J x (W_j | c_j | tau_j) | 8 x (o_m | v_m | R_m)].  W [J][P][d], c [J][P] and tau [J] shared by the set, or
+    [K][J][P][d], [K][J][P], [K][J] per factor; centres [M][P], velocities [M][P] and radii [M] one scene for every factor, or
+    [K][M][P], [K][M][P], [K][M] per factor, M <= 8: the remaining slots are empty (radius -inf, centre and velocity 0).
+    sigma, eps, r scalars or [K]."""
+    W, c, tau = (np.asarray(v, dtype=np.float64) for v in (W, c, tau))
+    o, v, R = (np.asarray(x, dtype=np.float64) for x in (centres, velocities, radii))
+    sig, eps, r = (np.atleast_1d(np.asarray(x, dtype=np.float64)) for x in (sigma, eps, r))
+    K = max(sig.size, eps.size, r.size, W.shape[0] if W.ndim == 4 else 1, o.shape[0] if o.ndim == 3 else 1,
+            v.shape[0] if v.ndim == 3 else 1, R.shape[0] if R.ndim == 2 else 1)
+    J, P = W.shape[-3], W.shape[-2]
+    W = np.broadcast_to(W, (K,) + W.shape[-3:])
+    c = np.broadcast_to(c, (K, J, P))
+    tau = np.broadcast_to(tau, (K, J))
+    M = R.shape[-1] if R.ndim else 0
+    assert M <= BALLS_MAX_M, "a factor has 8 ball slots"
+    slots = np.zeros((K, BALLS_MAX_M, 2 * P + 1))
+    slots[:, :, 2 * P] = -np.inf
+    if M:
+        slots[:, :M, :P] = np.broadcast_to(o, (K, M, P))
+        slots[:, :M, P:2 * P] = np.broadcast_to(v, (K, M, P))
+        slots[:, :M, 2 * P] = np.broadcast_to(R, (K, M))
+    head = np.stack([np.broadcast_to(x, (K,)) for x in (sig, eps, r)], axis=1)
+    body = np.concatenate([W.reshape(K, J, -1), c, tau[:, :, None]], axis=2).reshape(K, -1)
+    return np.ascontiguousarray(np.concatenate([head, body, slots.reshape(K, -1)], axis=1))
+
+
+def add_moving_obstacle_set(chain, centres0, velocities, radii, sigma=15.0, eps=0.2, r=0.1, p=3, taus=None, dt=0.25, qc=QC,
+                            temperature=1.0):
+    """A copy of `chain` (the arrays are shared) with a HINGE_BALLS_2D / _3D set appended behind its sets: balls m with centres
+    centres0 [M][P] at time 0, constant velocities [M][P] and radii [M] (M <= 8; P = 2 or 3 picks the kind).  State i has the
+    time t_i = i dt, and factor i of the set carries ball m at centres0_m + t_i v_m with velocity v_m.
+    taus = None: one factor per state (K = T, d = n) on the state's position, J = 1, tau = 0.
+    taus given: one factor per pair of neighbouring states (K = T - 1, d = 2n) on the GP-interpolated positions at the times
+    taus inside the segment (minacc_segment_readout for the chain's constant-velocity prior with step dt and spectral density
+    qc), tau_j = taus[j]: check point j meets the balls where they are at t_i + taus[j]."""
+    T, n = chain["T"], chain["n"]
+    o0, v = np.atleast_2d(np.asarray(centres0, dtype=np.float64)), np.atleast_2d(np.asarray(velocities, dtype=np.float64))
+    P = o0.shape[1]
+    assert P in (2, 3) and v.shape == o0.shape
+    if taus is None:
+        K, d = T, n
+        W = np.zeros((1, P, n))
+        W[0, :, :P] = np.eye(P)
+        c, tau = np.zeros((1, P)), np.zeros(1)
+    else:
+        K, d = T - 1, 2 * n
+        W, c = minacc_segment_readout(n // 2, qc, dt, list(taus), P)
+        tau = np.asarray(taus, dtype=np.float64)
+    t = dt * np.arange(K)
+    centres = o0[None, :, :] + t[:, None, None] * v[None, :, :]
+    params = balls_params(sigma, eps, r, W, c, tau, centres, np.broadcast_to(v, centres.shape), np.broadcast_to(radii, (K, o0.shape[0])))
+    spec = dict(kind=PSI_HINGE_BALLS_2D if P == 2 else PSI_HINGE_BALLS_3D, d=d, p=p, start=np.arange(K, dtype=np.int32), params=params,
                 temperature=np.full(K, float(temperature)))
     return dict(chain, specs=list(chain["specs"]) + [spec])
 

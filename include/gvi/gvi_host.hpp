@@ -41,6 +41,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -395,9 +396,49 @@ struct DevicePsi {
     }
     return p;
   }
-  // a set is homogeneous in its block size too: segment factors, and half-space factors, with different J stay apart
+  // Moving obstacles as analytic balls (GVI_PSI_HINGE_BALLS_2D / _3D; no reference counterpart): J = W.size() check points
+  // W[j] x + c[j] as for the segment kinds, check point j taken tau[j] after the factor's own time stamp; ball m stands at
+  // centres.row(m) + tau[j] velocities.row(m) then, radius radii(m).  psi = sigma sum_j max(0, epsilon + radius - sd_j)^2 with sd_j
+  // the exact distance to the nearest ball.  centres and velocities are M x P (P = 2 / 3), M <= GVI_BALLS_MAX_M: the remaining
+  // slots of the block are empty.  Needs no field; sample_clearance of such a set returns min_j sd_j - radius.  A predicted scene
+  // is refreshed with set_device_psi on the factors and update_device_psi_params on the optimizer.
+  static DevicePsi hinge_balls2d(double sigma, double epsilon, double radius, const std::vector<MatrixXd>& W, const std::vector<VectorXd>& c,
+                                 const std::vector<double>& tau, const MatrixXd& centres, const MatrixXd& velocities, const VectorXd& radii) {
+    return {GVI_PSI_HINGE_BALLS_2D, balls_block(2, sigma, epsilon, radius, W, c, tau, centres, velocities, radii)};
+  }
+  static DevicePsi hinge_balls3d(double sigma, double epsilon, double radius, const std::vector<MatrixXd>& W, const std::vector<VectorXd>& c,
+                                 const std::vector<double>& tau, const MatrixXd& centres, const MatrixXd& velocities, const VectorXd& radii) {
+    return {GVI_PSI_HINGE_BALLS_3D, balls_block(3, sigma, epsilon, radius, W, c, tau, centres, velocities, radii)};
+  }
+  // [sigma, epsilon, radius | J x (W_j | c_j | tau_j) | GVI_BALLS_MAX_M x (o_m | v_m | R_m)], empty slots: R = -infinity
+  static std::vector<double> balls_block(int P, double sigma, double epsilon, double radius, const std::vector<MatrixXd>& W,
+                                         const std::vector<VectorXd>& c, const std::vector<double>& tau, const MatrixXd& centres,
+                                         const MatrixXd& velocities, const VectorXd& radii) {
+    if (W.empty() || W.size() > (size_t)GVI_SEG_MAX_J || c.size() != W.size() || tau.size() != W.size())
+      throw std::invalid_argument("ball factor: 1 .. GVI_SEG_MAX_J (8) check points, one offset c and one time tau per read-out W");
+    const int M = (int)radii.size();
+    if (M > (int)GVI_BALLS_MAX_M || centres.rows() != M || velocities.rows() != M || (M > 0 && (centres.cols() != P || velocities.cols() != P)))
+      throw std::invalid_argument("ball factor: at most GVI_BALLS_MAX_M (8) balls; centres and velocities are M x P, radii has M entries");
+    std::vector<double> blk{sigma, epsilon, radius};
+    for (size_t j = 0; j < W.size(); ++j) {
+      if (W[j].rows() != P || W[j].cols() != W[0].cols() || c[j].size() != P)
+        throw std::invalid_argument("ball factor: every W must be P x d and every c of size P");
+      for (int r = 0; r < P; ++r)
+        for (int q = 0; q < W[j].cols(); ++q) blk.push_back(W[j](r, q));
+      for (int r = 0; r < P; ++r) blk.push_back(c[j](r));
+      blk.push_back(tau[j]);
+    }
+    for (int m = 0; m < (int)GVI_BALLS_MAX_M; ++m) {
+      for (int r = 0; r < P; ++r) blk.push_back(m < M ? centres(m, r) : 0.0);
+      for (int r = 0; r < P; ++r) blk.push_back(m < M ? velocities(m, r) : 0.0);
+      blk.push_back(m < M ? radii(m) : -std::numeric_limits<double>::infinity());
+    }
+    return blk;
+  }
+  // a set is homogeneous in its block size too: segment, ball and half-space factors with different J stay apart
   bool same_group(const DevicePsi& o) const {
-    const bool seg = kind == GVI_PSI_HINGE_SDF_2D_SEG || kind == GVI_PSI_HINGE_SDF_3D_SEG || kind == GVI_PSI_HINGE_HALFSPACE;
+    const bool seg = kind == GVI_PSI_HINGE_SDF_2D_SEG || kind == GVI_PSI_HINGE_SDF_3D_SEG || kind == GVI_PSI_HINGE_HALFSPACE ||
+                     kind == GVI_PSI_HINGE_BALLS_2D || kind == GVI_PSI_HINGE_BALLS_3D;
     return kind == o.kind && sdf2d == o.sdf2d && sdf3d == o.sdf3d && arm == o.arm && (!seg || params.size() == o.params.size());
   }
   // [sigma, epsilon, radius | W_0 (P x d, row-major) | c_0 (P) | ...]: the kinds' parameter block (DevicePsi stays an aggregate)
@@ -955,6 +996,8 @@ class FactorBatch {
   const std::shared_ptr<Device>& device() const { return _dev; }
   int set_id() const { return _set; }
   void forget(GVIFactorizedBase* f) { std::lock_guard<std::mutex> g(_mx); for (auto& m : _members) if (m == f) m = nullptr; }
+  // the set's psi changed on the device (gvi_factors_set_params): cached moments and costs are stale
+  void invalidate() { std::lock_guard<std::mutex> g(_mx); _mom_valid = _cost_valid = false; }
 
   // calculate_partial_V of member k at its current (mu, covariance)
   void moments(int k, double& Ephi, VectorXd& Vdmu, MatrixXd& Vddmu) {
@@ -1190,6 +1233,13 @@ class NGDFactorizedBaseGH : public NGDFactorDeviceOps {
   double psi(const VectorXd& x) const override { return _function(x, _cost_class); }
   int gh_degree() const override { return _gh_degree; }
   const DevicePsi& device_psi() const override { return _psi; }
+  // New parameters for the device psi -- a predicted scene refreshed at a replanning cycle: same kind, shared field and block
+  // size, so the factor stays in its set.  The optimizer's update_device_psi_params() sends them to the device.
+  void set_device_psi(const DevicePsi& psi) {
+    if (!_psi.same_group(psi) || psi.params.size() != _psi.params.size())
+      throw std::invalid_argument("set_device_psi: the kind, the shared field and the size of the parameter block of a factor are fixed");
+    _psi = psi;
+  }
   // (x - mu) psi(x), (x - mu)(x - mu)^T psi(x): the closures of :46-48, for callers that integrate on the host
   inline MatrixXd negative_log_probability(const VectorXd& x) const { return MatrixXd::Constant(1, 1, psi(x)); }
   inline MatrixXd xMu_negative_log_probability(const VectorXd& x) const {
@@ -1709,6 +1759,21 @@ class GVIGH {
     for (auto& f : _vec_factors) f->factor_switch_to_high_temperature();
     _temperature = _high_temperature;
     push_temperatures();
+  }
+  // After set_device_psi on factors: the parameter blocks of every set that keeps them go to the device again
+  // (gvi_factors_set_params; the priors build their operands when the set is added and are left alone).  The state stays.
+  void update_device_psi_params() {
+    for (size_t s = 0; s < _sets.size(); ++s) {
+      const DevicePsi& dp = _vec_factors[_sets[s].members[0]]->device_psi();
+      if (dp.kind == GVI_PSI_QUAD_PRIOR || dp.kind == GVI_PSI_FIXED_PRIOR || dp.kind == GVI_PSI_HOST_CALLBACK) continue;
+      std::vector<double> params;
+      for (int i : _sets[s].members) {
+        const std::vector<double>& q = _vec_factors[i]->device_psi().params;
+        params.insert(params.end(), q.begin(), q.end());
+      }
+      _dev->check(gvi_factors_set_params(_dev->get(), (int)s, params.data(), (int64_t)dp.params.size()));
+      _batches[s]->invalidate();
+    }
   }
 
   // cost_value(mean, Precision) (gvibase/GVI-GH-impl.h:176-197): sum_k fact_cost_value + 1/2 log det, operator level

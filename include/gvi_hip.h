@@ -97,13 +97,28 @@ enum { GVI_F64 = 0, GVI_F32 = 1 };
  *       gvi_factors_set_closed_form(set, 0) selects the Gauss-Hermite quadrature of the same psi, (set, 1) returns.
  *       margin(x) = min over the rows with sigma_j > 0 of (b_j - a_j^T x) / |a_j|, the signed Euclidean distance to the nearest
  *       active face (+inf when every row is off; eps plays no part), is what the clearance calls return for such a set
+ *   GVI_PSI_HINGE_BALLS_2D / GVI_PSI_HINGE_BALLS_3D                         d = n or 2n, P = 2 / P = 3 (no reference counterpart)
+ *       [sigma, epsilon, radius | J x ( W_j (P x d, row-major) | c_j (P) | tau_j ) | 8 x ( o_m (P) | v_m (P) | R_m )]
+ *       params_per_factor = 3 + J (P (d + 1) + 1) + 8 (2 P + 1) exactly
+ *       Moving obstacles as analytic balls, no grid: check point j is the read-out q_j = W_j x + c_j of the factor's slice (as
+ *       for the _SEG kinds), ball m stands at o_m + tau_j v_m when check point j is taken, and
+ *       sd_j(x) = min_m |q_j - (o_m + tau_j v_m)| - R_m,  psi(x) = sigma * sum_j max(0, epsilon + radius - sd_j(x))^2.
+ *       tau_j is the time of check point j relative to the factor's own time stamp; the obstacle's parameters are part of the
+ *       factor's block, so factor k sees the scene at its own time (v = 0 or tau = 0: a static scene).  Every factor carries
+ *       GVI_BALLS_MAX_M = 8 ball slots; a slot with R_m = -inf is EMPTY: it is never evaluated and may hold anything but NaN.
+ *       With every slot empty sd_j = +inf and psi = 0.  J is a property of the set, 1 <= J <= 8 (GVI_SEG_MAX_J), derived from
+ *       params_per_factor; else GVI_ERR_ARG.  GVI_ERR_ARG also for: a NaN anywhere, sigma < 0 or not finite, epsilon, radius, W,
+ *       c or tau not finite, R_m neither finite and >= 0 nor -inf, a non-finite o_m or v_m in a slot that is not empty.
+ *       Needs no grid and no arm model (those setters refuse it) and has no closed form.  The clearance calls return
+ *       min_j sd_j - radius (+inf with every slot empty).  gvi_factors_set_params replaces the blocks
  *   GVI_PSI_HOST_CALLBACK no parameters: psi is an opaque host function (the reference's
  *       std::function, ngd/NGDFactorizedBaseGH.h:30,46-48); use gvi_expand + gvi_moments_from_psi. */
 enum { GVI_PSI_RANGE_1D = 0, GVI_PSI_QUAD_PRIOR = 1, GVI_PSI_FIXED_PRIOR = 2, GVI_PSI_HOST_CALLBACK = 3,
        GVI_PSI_HINGE_SDF_2D = 4, GVI_PSI_HINGE_SDF_2D_BODY = 5, GVI_PSI_HINGE_SDF_3D = 6, GVI_PSI_HINGE_SDF_3D_ARM = 7,
        GVI_PSI_HINGE_SDF_2D_SEG = 8, GVI_PSI_HINGE_SDF_3D_SEG = 9, GVI_PSI_HINGE_BOX = 10,
-       GVI_PSI_HINGE_HALFSPACE = 11 };
-enum { GVI_SEG_MAX_J = 8 };   /* check points of one HINGE_SDF_*_SEG factor */
+       GVI_PSI_HINGE_HALFSPACE = 11, /* 12 is not a kind */ GVI_PSI_HINGE_BALLS_2D = 13, GVI_PSI_HINGE_BALLS_3D = 14 };
+enum { GVI_SEG_MAX_J = 8 };   /* check points of one HINGE_SDF_*_SEG / HINGE_BALLS_* factor */
+enum { GVI_BALLS_MAX_M = 8 };   /* ball slots of one HINGE_BALLS_* factor */
 enum { GVI_HALFSPACE_MAX_J = 16 };   /* rows of one HINGE_HALFSPACE factor */
 
 const char* gvi_version(void);
@@ -186,6 +201,14 @@ gvi_status gvi_factors_set_arm(gvi_ctx* ctx, int set_id, int ndof, const double*
 gvi_status gvi_factors_set_closed_form(gvi_ctx* ctx, int set_id, int on);
 /* factor_switch_to_high_temperature (gvibase/GVIFactorizedBase.h:212-214), batched. */
 gvi_status gvi_factors_set_temperature(gvi_ctx* ctx, int set_id, const double* temperature);
+/* Replace the K parameter blocks of a set (a predicted scene refreshed at every replanning cycle, new limits, ...):
+ * psi_params [K][params_per_factor] as for gvi_factors_add.  For the kinds whose block is uploaded as it is -- RANGE_1D, the
+ * hinge kinds on a grid, HINGE_BOX, HINGE_HALFSPACE, HINGE_BALLS_*; the priors (operands built from the block at
+ * gvi_factors_add) and HOST_CALLBACK: GVI_ERR_ARG.  The layout of a set is fixed when it is added: the same
+ * params_per_factor (hence the same J) is required, and the values pass the checks of gvi_factors_add; after a refusal
+ * the set keeps its old blocks.  Cost and gradients of the resident iteration are stale afterwards, as after
+ * gvi_factors_set_temperature. */
+gvi_status gvi_factors_set_params(gvi_ctx* ctx, int set_id, const double* psi_params, int64_t params_per_factor);
 gvi_status gvi_factors_info(const gvi_ctx* ctx, int set_id, int* K, int* d, int* p, int64_t* N);
 
 /* ---- per-pass factor operators (one call = all K factors of the set) ---- */
@@ -450,7 +473,9 @@ gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_
  *      psi, in the same arithmetic: the one ball of HINGE_SDF_2D / _3D, the n_balls body points of _2D_BODY, the first
  *      min(d, nspheres) spheres with their own radii of _3D_ARM, the J read-outs W_j x + c_j of _2D_SEG / _3D_SEG.  epsilon and slope play no part in it.
  *      For a HINGE_BOX set the clearance is margin(x) = min_i min(hi_i - x_i, x_i - lo_i), +inf when no limit is finite; for a
- *      HINGE_HALFSPACE set min_j (b_j - a_j^T x) / |a_j| over the rows with sigma_j > 0, +inf when every row is off.  It is the continuous
+ *      HINGE_HALFSPACE set min_j (b_j - a_j^T x) / |a_j| over the rows with sigma_j > 0, +inf when every row is off; for a
+ *      HINGE_BALLS_* set min_j sd_j - radius, the exact distance to the nearest ball at each check point's time, +inf when
+ *      every slot is empty (it needs no grid).  It is the continuous
  *      quantity; the library returns no collided / not-collided indicator.
  *      S = 0 is a no-op; S < 0, a required NULL buffer, first < 0 or a set id outside the context's sets: GVI_ERR_ARG; before
  *      gvi_chain_set (gvi_ngd_*: before gvi_ngd_init): GVI_ERR_STATE, as is a hinge set whose grid (arm model) was never set; a
@@ -466,7 +491,7 @@ gvi_status gvi_ngd_sample_interp_dev(gvi_ctx* ctx, int S, uint64_t seed, uint64_
  *      64, ... 1).  The order depends on the sets only. ---- */
 /* cost [S][K] of one set at X [S][T][n]; host buffers, a pure operator. */
 gvi_status gvi_sample_factor_costs(gvi_ctx* ctx, int set_id, int S, const double* X, double* cost);
-/* clr [S][K]: hinge-on-SDF, HINGE_BOX and HINGE_HALFSPACE sets only, every other kind: GVI_ERR_UNSUPPORTED.  The _dev twin takes device buffers and is
+/* clr [S][K]: hinge-on-SDF, HINGE_BOX, HINGE_HALFSPACE and HINGE_BALLS_* sets only, every other kind: GVI_ERR_UNSUPPORTED.  The _dev twin takes device buffers and is
  * asynchronous on the context stream. */
 gvi_status gvi_sample_clearance(gvi_ctx* ctx, int set_id, int S, const double* X, double* clr);
 gvi_status gvi_sample_clearance_dev(gvi_ctx* ctx, int set_id, int S, const double* X_dev, double* clr_dev);
