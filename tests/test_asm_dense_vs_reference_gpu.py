@@ -42,6 +42,7 @@ import numpy as np
 import pytest
 
 import gvi_oracle as o
+from asm_closed_form import closed_form
 from chains import make_chain
 from gaussianvi_amd import api
 from test_gpu_parity import TIGHT, rel
@@ -108,19 +109,13 @@ def _closed_form(P, mu):
     """g, V_D, V_U as the sums of the factor gradients at the mean and of the factor Hessians; the binary set's share of
     V_D; dmu from the dense system (None where V is singular: no unary set)"""
     T, n = P["T"], P["n"]
-    g, VD, VU, VDb = np.zeros((T, n)), np.zeros((T, n, n)), np.zeros((T - 1, n, n)), np.zeros((T, n, n))
-    for k in range(P["Kb"]):
-        J = np.hstack([P["Phi"][k], -np.eye(n)])
-        H = J.T @ P["Q"][k] @ J                                   # psi = (J x)^T Q (J x) / 2
-        gr = H @ np.concatenate([mu[k], mu[k + 1]])
-        g[k] += gr[:n]; g[k + 1] += gr[n:]
-        VDb[k] += H[:n, :n]; VDb[k + 1] += H[n:, n:]; VU[k] += H[:n, n:]
-    VD += VDb
-    for k in range(P["Ku"]):
-        H = 2.0 * P["Kinv"][k]                                    # psi = (x - mu_k)^T Kinv (x - mu_k)
-        g[k] += H @ (mu[k] - P["mu_u"][k]); VD[k] += H
-    dmu = np.linalg.solve(o.bt_to_dense(VD, VU), -g.reshape(-1)).reshape(T, n) if P["Ku"] else None
-    return dict(g=g, VD=VD, VU=VU, VDb=VDb, dmu=dmu)
+    sets = []                                                     # (binary set first: the order these sums always had)
+    if P["Kb"]:
+        sets.append(dict(kind="b", start=np.arange(P["Kb"]), Phi=P["Phi"], Q=P["Q"]))
+    if P["Ku"]:
+        sets.append(dict(kind="u", start=np.arange(P["Ku"]), mu_u=P["mu_u"], Kinv=P["Kinv"]))
+    cf = closed_form(T, n, sets, mu, solve=bool(P["Ku"]))
+    return dict(g=cf["g"], VD=cf["VD"], VU=cf["VU"], VDb=cf["parts"][0] if P["Kb"] else np.zeros((T, n, n)), dmu=cf["dmu"])
 
 
 def _oracle_sets(P):
