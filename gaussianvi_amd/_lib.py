@@ -55,6 +55,9 @@ SIGNATURES = {
                             C.c_void_p, C.c_void_p],
     "gvi_factors_set_temperature": [C.c_void_p, C.c_int, C.c_void_p],
     "gvi_factors_set_params": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64],
+    "gvi_factors_set_readout_rule": [C.c_void_p, C.c_int, C.c_int],
+    "gvi_factors_readout_info": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                 C.POINTER(C.c_int64)],
     "gvi_factors_info": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                          C.POINTER(C.c_int64)],
     "gvi_moments": [C.c_void_p, C.c_int] + [C.c_void_p] * 5,

@@ -215,6 +215,17 @@ class Context:
         params = _f64(params).reshape(K, -1) if K else np.zeros((0, 1))
         self._ck(self.lib.gvi_factors_set_params(self.h, sid, _p(params), params.shape[1]))
 
+    def factors_set_readout_rule(self, sid, order):
+        """Moments of a set on linear read-outs (HINGE_SDF_2D / _3D, the _SEG and BALLS kinds) by a dense tensor Gauss-Hermite
+        rule of `order` nodes per read-out coordinate instead of the sparse rule in d dimensions (gvi_factors_set_readout_rule);
+        0 switches it off."""
+        self._ck(self.lib.gvi_factors_set_readout_rule(self.h, sid, int(order)))
+
+    def factors_readout_info(self, sid):
+        order, P, J, pts = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        self._ck(self.lib.gvi_factors_readout_info(self.h, sid, C.byref(order), C.byref(P), C.byref(J), C.byref(pts)))
+        return dict(order=order.value, P=P.value, J=J.value, points_per_check_point=pts.value)
+
     # ---- per-pass factor operators (host buffers) ----
     def moments(self, sid, mu, Sigma):
         K, d, _, _ = self.sets[sid]
@@ -693,4 +704,6 @@ def context_for_chain(chain, device=0, specs=None, tables=None):
             ctx.factors_set_sdf3d(ids[-1], spec["sdf_origin"], spec["sdf_cell"], spec["sdf_field"])
         if spec["kind"] == PSI_HINGE_SDF_3D_ARM:
             ctx.factors_set_arm(ids[-1], spec["arm"])
+        if spec.get("readout_order"):                     # the builders' readout_order= (synthetic.py): the read-out-space rule
+            ctx.factors_set_readout_rule(ids[-1], spec["readout_order"])
     return ctx, ids

@@ -33,6 +33,26 @@ GVI_BALLS_HD double balls_hinge_sq(double sd, double thr, double sigma) {
   return err * err * sigma;
 }
 
+// Signed distance from the read-out point q [P] to the union of the slots that are not empty, the balls taken at time tau
+// (+inf when every slot is empty).  balls: the BALLS_SLOTS slots of the factor's block.  The one distance code of the kind: psi
+// and the clearance at a sample (hinge_balls_points) and f_j at a quadrature point of the read-out rule (readout_moments.hpp).
+template <int P>
+GVI_BALLS_HD double balls_signed_distance(const double* balls, double tau, const double* q) {
+  double sd = INFINITY;
+  const double* b = balls;
+  for (int m = 0; m < BALLS_SLOTS; ++m, b += balls_slot_stride(P)) {
+    const double R = b[2 * P];
+    if (balls_slot_empty(R)) continue;
+    double d2 = 0.0;
+    for (int r = 0; r < P; ++r) {
+      const double e = q[r] - fma(tau, b[P + r], b[r]);
+      d2 = fma(e, e, d2);
+    }
+    sd = fmin(sd, sqrt(d2) - R);
+  }
+  return sd;
+}
+
 // Walks the J check points of one factor at the slice x and calls visit(sd_j, r), as the *_points functions of
 // kernels_factor.hpp do: psi and the clearance are two visitors of this walk.
 template <int P, typename V>
@@ -47,20 +67,7 @@ GVI_BALLS_HD void hinge_balls_points(const double* p, const double* x, int d, in
       for (int c = 0; c < d; ++c) v = fma(wc[r * d + c], x[c], v);
       q[r] = v;
     }
-    const double tau = wc[P * (d + 1)];
-    double sd = INFINITY;
-    const double* b = balls;
-    for (int m = 0; m < BALLS_SLOTS; ++m, b += balls_slot_stride(P)) {
-      const double R = b[2 * P];
-      if (balls_slot_empty(R)) continue;
-      double d2 = 0.0;
-      for (int r = 0; r < P; ++r) {
-        const double e = q[r] - fma(tau, b[P + r], b[r]);
-        d2 = fma(e, e, d2);
-      }
-      sd = fmin(sd, sqrt(d2) - R);
-    }
-    visit(sd, p[2]);
+    visit(balls_signed_distance<P>(balls, wc[P * (d + 1)], q), p[2]);
   }
 }
 

@@ -27,6 +27,7 @@
 #include "kernels_fused.hpp"
 #include "kernels_block.hpp"
 #include "kernels_orbit_psi.hpp"
+#include "kernels_readout.hpp"
 #include "kernels_sample.hpp"
 #include "kernels_solve.hpp"
 #include "kernels_interp.hpp"
@@ -94,6 +95,8 @@ struct FactorSet {
   int arm_ndof = 0;
   int seg_J = 0;                      // HINGE_SDF_*_SEG: check points per factor; HINGE_HALFSPACE: rows per factor
   bool closed_form = false;           // no sigma points: NGDFactorizedLinear route (sum-of-squares kinds), box_moments.hpp (HINGE_BOX, its default), halfspace_moments.hpp (HINGE_HALFSPACE, its default)
+  int readout_order = 0;              // > 0: moments by the read-out-space rule of this order (gvi_factors_set_readout_rule; PSI_READOUT kinds)
+  DevMem readout_rule;                // its 1-D rule [nodes (order) | weights (order)]
   bool chain_structured = false;      // start[k] == k (factor k on state k / states k, k + 1): assemble-on-load needs no CSR
   bool all_pos = false;               // every residual row has sgn = +1 (positive-definite weight)
   bool force_sym = false;             // set around passes whose caller sees the sigma points
@@ -487,6 +490,7 @@ RouteFacts route_facts(const FactorSet& s, bool psi_ext) {
   RouteFacts f;
   f.kind = s.kind; f.d = s.d; f.m = s.m; f.K = s.K;
   f.closed_form = s.closed_form; f.all_pos = s.all_pos; f.psi_ext = psi_ext;
+  f.readout_order = s.readout_order;
   f.has_arm = s.arm.p != nullptr; f.has_sdf = s.sdf_rows != 0;
   f.arm_ndof = s.arm_ndof; f.seg_J = s.seg_J; f.opsi_rows = orbit_psi_rows(s.kind);
   f.Np = t.Np; f.Nmp = t.Nmp; f.p = t.p; f.coded = t.coded; f.has_Zq = t.Zq.p != nullptr;
@@ -693,7 +697,9 @@ struct MomPlan {
   OrbitPsiArgs pa;           // OrbitPsi
   size_t lds = 0;            // Orbit, OrbitPsi, Generic, Closed (HINGE_BOX, HINGE_HALFSPACE): dynamic LDS
   bool pipe = false;         // Sreg: the hand-pipelined body
-  int block = 64;            // Closed (HINGE_HALFSPACE): lanes per block, 64 or 256
+  int block = 64;            // Closed (HINGE_HALFSPACE), Readout: lanes per block, 64 or 256
+  const double* ro_rule = nullptr;   // Readout: the set's 1-D rule on the device and its order
+  int ro_order = 0;
 };
 // a pass of the resident iteration over all sets: what was read, what was decided, what was bound
 struct PassPlan {
@@ -734,6 +740,27 @@ gvi_status launch_closed(gvi_ctx* c, const MomPlan& p, hipStream_t st, ClosedHal
   return GVI_OK;
 }
 
+// ---- the read-out-space rule (kernels_readout.hpp; gvi_factors_set_readout_rule) ----
+// One wave per factor.  As for the closed-form HINGE_HALFSPACE kernel: one wave per block while the launch has no more waves
+// than the chip has SIMDs (256 CUs x 4), above that four waves per block, a quarter of the workgroups to dispatch.
+constexpr int READOUT_WPB_SWITCH = 1024;
+template <int P, int CLS>
+gvi_status plan_readout(gvi_ctx* c, const FactorSet& s, MomPlan& p, ReadoutInst<P, CLS>) {
+  const int wpb = s.K <= READOUT_WPB_SWITCH ? 1 : 4;
+  p.block = 64 * wpb;
+  p.grid = dim3((unsigned)((s.K + wpb - 1) / wpb));
+  p.lds = (size_t)wpb * readout_lds_doubles(P, s.d, CLS == READOUT_LEAD ? 1 : s.seg_J) * 8;
+  p.ro_rule = s.readout_rule.d(); p.ro_order = s.readout_order;
+  if (p.lds > 64 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "read-out rule kernel LDS budget");
+  return GVI_OK;
+}
+template <int P, int CLS>
+void launch_readout(const MomPlan& p, hipStream_t st, ReadoutInst<P, CLS>) {
+  ReadoutArgs ra;
+  ra.a = p.a; ra.rule = p.ro_rule; ra.order = p.ro_order;
+  hipLaunchKernelGGL((moments_readout_kernel<P, CLS>), p.grid, dim3(p.block), p.lds, st, ra);
+}
+
 // Binds a decision: the partial buffer, the kernel arguments, and the sizes and refusals that take the size functions of the
 // kernel headers.  Beyond its buffers it writes nothing into the set.  prep must have run for (mu, Sigma) before the plan is
 // launched.
@@ -751,6 +778,10 @@ gvi_status bind_plan(gvi_ctx* c, FactorSet& s, const RouteDecision& r, const dou
   if (r.route == Route::Closed) {
     gvi_status rc = GVI_OK;
     with_closed_instance(s.kind, [&](auto inst) { rc = plan_closed(c, s, p, inst); });
+    GVICK(rc);
+  } else if (r.route == Route::Readout) {
+    gvi_status rc = GVI_OK;
+    with_readout_instance(s.kind, [&](auto inst) { rc = plan_readout(c, s, p, inst); });
     GVICK(rc);
   } else if (r.route == Route::Orbit) {
     GVICK(orbit_args(c, s, r.nchunk, &p.oa));
@@ -817,6 +848,9 @@ gvi_status launch_plan(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t s
     case Route::Generic:
       GVICK(allow_lds(c, (const void*)moments_generic_kernel, 160 * 1024));
       hipLaunchKernelGGL(moments_generic_kernel, p.grid, dim3(GEN_BS), p.lds, st, a);
+      break;
+    case Route::Readout:
+      hit = with_readout_instance(s.kind, [&](auto inst) { launch_readout(p, st, inst); });
       break;
   }
   if (!hit) return fail(c, GVI_ERR_UNSUPPORTED, "planned route without a kernel instance");
@@ -1441,6 +1475,42 @@ gvi_status gvi_factors_set_params(gvi_ctx* ctx, int set_id, const double* psi_pa
   GVICK(sync(ctx));
   HIPCK(ctx, hipMemcpy(s->raw.p, raw.data(), raw.size() * 8, hipMemcpyHostToDevice));
   ngd_invalidate(ctx);
+  return GVI_OK;
+}
+
+// The rule is a property of the set beside its table: nothing derived from the blocks' VALUES is kept (the drop rule of a
+// read-out is decided on the device per pass), so gvi_factors_set_params and gvi_set_variant leave it alone.
+gvi_status gvi_factors_set_readout_rule(gvi_ctx* ctx, int set_id, int order) {
+  FactorSet* s = get_set(ctx, set_id);
+  if (!s) return fail(ctx, GVI_ERR_ARG, "bad set id");
+  const int P = psi_kind_readout_P(s->kind);
+  if (P == 0)
+    return fail(ctx, GVI_ERR_ARG, "gvi_factors_set_readout_rule: only the kinds on linear read-outs (HINGE_SDF_2D / _3D, HINGE_SDF_*_SEG, HINGE_BALLS_*)");
+  if (order != 0 && !readout_order_ok(order, P))
+    return fail(ctx, GVI_ERR_ARG, "gvi_factors_set_readout_rule: order is 0 (off) or 2 <= order <= 16 with order^P <= 1024 (P = 3: order <= 10)");
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  GVICK(sync(ctx));
+  if (order > 0) {
+    SparseGrid g;
+    if (spgh_generate(1, order, g) || g.N != order) return fail(ctx, GVI_ERR_NOTABLE, "gvi_factors_set_readout_rule: no 1-D rule of this order");
+    std::vector<double> rule(2 * (size_t)order);
+    for (int a = 0; a < order; ++a) { rule[a] = g.Z[a]; rule[order + a] = g.w[a]; }
+    HIPCK(ctx, s->readout_rule.ensure(2 * (size_t)READOUT_MAX_ORDER * 8));
+    HIPCK(ctx, hipMemcpy(s->readout_rule.p, rule.data(), rule.size() * 8, hipMemcpyHostToDevice));
+  }
+  s->readout_order = order;
+  ngd_invalidate(ctx);
+  return GVI_OK;
+}
+
+gvi_status gvi_factors_readout_info(const gvi_ctx* ctx, int set_id, int* order, int* P, int* J, int64_t* points_per_check_point) {
+  FactorSet* s = get_set(const_cast<gvi_ctx*>(ctx), set_id);
+  if (!s) return GVI_ERR_ARG;
+  const int rp = psi_kind_readout_P(s->kind);
+  if (order) *order = s->readout_order;
+  if (P) *P = rp;
+  if (J) *J = rp == 0 ? 0 : (s->seg_J > 0 ? s->seg_J : 1);
+  if (points_per_check_point) *points_per_check_point = s->readout_order > 0 ? readout_points(s->readout_order, rp) : 0;
   return GVI_OK;
 }
 

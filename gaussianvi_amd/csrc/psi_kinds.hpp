@@ -44,6 +44,8 @@ enum : unsigned {
   PSI_CLOSED_DEFAULT = 1u << 6,   // ... and takes them by default: exact and cheaper than any rule on the kink
   PSI_SUMSQ = 1u << 7,            // sum of squares of m linear forms: operands (A, b, sgn) built at gvi_factors_add
   PSI_NO_DEVICE = 1u << 8,        // the host evaluates psi (gvi_expand + gvi_moments_from_psi)
+  PSI_READOUT = 1u << 9,          // psi = sum_j f_j(W_j x + c_j) on P-dimensional linear read-outs (psi_kind_readout_P): offers the
+                                  // read-out-space rule (gvi_factors_set_readout_rule; readout_moments.hpp)
   PSI_SDF = PSI_SDF_2D | PSI_SDF_3D
 };
 
@@ -76,17 +78,17 @@ constexpr PsiKindRow PSI_KINDS[KIND_COUNT] = {
   {KIND_QUAD_PRIOR, PSI_SUMSQ | PSI_CLOSED, M_HALF_D, NEED_QUAD, 0, D_EVEN, 0, "QUAD_PRIOR needs even d"},
   {KIND_FIXED_PRIOR, PSI_SUMSQ | PSI_CLOSED, M_D, NEED_MEAN_QUAD, 0, D_ANY, 0, nullptr},
   {KIND_HOST_CALLBACK, PSI_NO_DEVICE, M_NONE, NEED_FIXED, 0, D_ANY, 0, nullptr},
-  {KIND_HINGE_SDF_2D, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE, M_NONE, NEED_FIXED, 3, D_MIN, 2, "HINGE_SDF_2D needs d >= 2"},
+  {KIND_HINGE_SDF_2D, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_FIXED, 3, D_MIN, 2, "HINGE_SDF_2D needs d >= 2"},
   {KIND_HINGE_SDF_2D_BODY, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE, M_NONE, NEED_FIXED, 6, D_MIN, 3, "HINGE_SDF_2D_BODY needs d >= 3"},
-  {KIND_HINGE_SDF_3D, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE, M_NONE, NEED_FIXED, 3, D_MIN, 3, "HINGE_SDF_3D needs d >= 3"},
+  {KIND_HINGE_SDF_3D, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_FIXED, 3, D_MIN, 3, "HINGE_SDF_3D needs d >= 3"},
   {KIND_HINGE_SDF_3D_ARM, PSI_RAW | PSI_SDF_3D | PSI_ARM | PSI_CLEARANCE, M_NONE, NEED_FIXED, 2, D_ANY, 0, nullptr},
-  {KIND_HINGE_SDF_2D_SEG, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE, M_NONE, NEED_SEG, 2, D_ANY, 0, nullptr},
-  {KIND_HINGE_SDF_3D_SEG, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE, M_NONE, NEED_SEG, 3, D_ANY, 0, nullptr},
+  {KIND_HINGE_SDF_2D_SEG, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_SEG, 2, D_ANY, 0, nullptr},
+  {KIND_HINGE_SDF_3D_SEG, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_SEG, 3, D_ANY, 0, nullptr},
   {KIND_HINGE_BOX, PSI_RAW | PSI_CLEARANCE | PSI_CLOSED | PSI_CLOSED_DEFAULT, M_NONE, NEED_BOX, 0, D_ANY, 0, nullptr},
   {KIND_HINGE_HALFSPACE, PSI_RAW | PSI_CLEARANCE | PSI_CLOSED | PSI_CLOSED_DEFAULT, M_NONE, NEED_HALFSPACE, 0, D_ANY, 0, nullptr},
   {KIND_HOLE, 0, M_NONE, NEED_FIXED, 0, D_ANY, 0, nullptr},
-  {KIND_HINGE_BALLS_2D, PSI_RAW | PSI_CLEARANCE, M_NONE, NEED_BALLS, 2, D_ANY, 0, nullptr},
-  {KIND_HINGE_BALLS_3D, PSI_RAW | PSI_CLEARANCE, M_NONE, NEED_BALLS, 3, D_ANY, 0, nullptr},
+  {KIND_HINGE_BALLS_2D, PSI_RAW | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_BALLS, 2, D_ANY, 0, nullptr},
+  {KIND_HINGE_BALLS_3D, PSI_RAW | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_BALLS, 3, D_ANY, 0, nullptr},
 };
 constexpr bool psi_kind_known(int kind) { return kind >= 0 && kind < KIND_COUNT && kind != KIND_HOLE; }
 
@@ -111,6 +113,13 @@ template <unsigned FLAGS>
 GVI_KIND_HD constexpr bool psi_kind_is(int kind) {
   constexpr unsigned mask = psi_kind_mask(FLAGS);
   return kind >= 0 && kind < KIND_COUNT && ((mask >> kind) & 1u) != 0;
+}
+
+// P of a PSI_READOUT kind: the dimension of its read-outs (2: the planar grid / planar balls, 3: the 3-D field / balls); 0 for
+// every other kind
+GVI_KIND_HD constexpr int psi_kind_readout_P(int kind) {
+  if (!psi_kind_is<PSI_READOUT>(kind)) return 0;
+  return kind == KIND_HINGE_SDF_2D || kind == KIND_HINGE_SDF_2D_SEG || kind == KIND_HINGE_BALLS_2D ? 2 : 3;
 }
 
 // Layout of a set of `kind` on factors of dimension d whose parameter blocks are params_per_factor doubles apart: operand

@@ -37,6 +37,7 @@ template <int M, int SMAX, int WAVES, int D0, int D1> struct FusedInst {};
 struct ClosedSumsq {};
 struct ClosedBox {};
 struct ClosedHalfspace {};
+template <int P, int CLS> struct ReadoutInst {};   // CLS: how the kind lays its read-outs out (0 the leading coordinates, 1 _SEG blocks, 2 BALLS blocks)
 constexpr auto any_instance = [](auto) {};
 template <class F, class Inst> bool hit(F& f, Inst inst) { f(inst); return true; }
 
@@ -192,6 +193,20 @@ bool with_closed_instance(int kind, F&& f) {
   return false;
 }
 
+// moments_readout_kernel<P, CLS> (kernels_readout.hpp): the PSI_READOUT kinds, any d <= 32
+template <class F>
+bool with_readout_instance(int kind, F&& f) {
+  switch (kind) {
+    case KIND_HINGE_SDF_2D: return hit(f, ReadoutInst<2, 0>{});
+    case KIND_HINGE_SDF_3D: return hit(f, ReadoutInst<3, 0>{});
+    case KIND_HINGE_SDF_2D_SEG: return hit(f, ReadoutInst<2, 1>{});
+    case KIND_HINGE_SDF_3D_SEG: return hit(f, ReadoutInst<3, 1>{});
+    case KIND_HINGE_BALLS_2D: return hit(f, ReadoutInst<2, 2>{});
+    case KIND_HINGE_BALLS_3D: return hit(f, ReadoutInst<3, 2>{});
+  }
+  return false;
+}
+
 inline bool reg_supported(int kind, int d, int m) { return with_reg_instance(kind, d, m, any_instance); }
 inline bool sreg_supported(int kind, int d, int m) { return with_sreg_instance(kind, d, m, any_instance); }
 inline bool scost_supported(int kind, int d, int m) { return with_scost_instance(kind, d, m, any_instance); }
@@ -239,7 +254,8 @@ struct RouteFacts {
   // of the set
   int kind = 0, d = 0, m = 0, K = 0;
   bool closed_form = false, all_pos = false;
-  bool psi_ext = false;               // the caller supplies psi at the sigma points (gvi_moments_from_psi)
+  int readout_order = 0;              // > 0: the read-out-space rule is on (gvi_factors_set_readout_rule; PSI_READOUT kinds only)
+  bool psi_ext = false;              // the caller supplies psi at the sigma points (gvi_moments_from_psi)
   bool has_arm = false, has_sdf = false;
   int arm_ndof = 0, seg_J = 0;
   int opsi_rows = 0;                  // leading coordinates the kind's register psi reads (orbit_psi_rows, kernels_orbit_psi.hpp)
@@ -267,7 +283,7 @@ inline RouteRules route_rules(const Options& o, RouteForce force) {
   return r;
 }
 
-enum class Route { Empty, Closed, Orbit, OrbitPsi, Split, Sreg, Scost, Reg, Generic };
+enum class Route { Empty, Closed, Orbit, OrbitPsi, Split, Sreg, Scost, Reg, Generic, Readout };
 // lane-per-point register kernels: a block's four waves take four factors, grid ((K + 3) / 4, nchunk) but for Scost's own launch
 constexpr bool lane_per_point(Route r) { return r == Route::Sreg || r == Route::Scost || r == Route::Reg; }
 
@@ -342,6 +358,14 @@ inline RouteDecision decide_route(const RouteFacts& s, const RouteRules& r, int 
   if (psi_kind_is<PSI_SDF>(s.kind) && !s.psi_ext && !s.has_sdf)
     return refuse(GVI_ERR_STATE, "HINGE_SDF set without a grid: call gvi_factors_set_sdf2d / gvi_factors_set_sdf3d");
   const bool closed = s.closed_form && !s.psi_ext;
+  // the read-out-space rule is the set's own choice of quadrature, not a kernel variant: it holds under every force, before
+  // the sparse routes and their refusals; a pass on the caller's psi values walks the caller's sigma points
+  if (s.readout_order > 0 && !closed && !s.psi_ext && with_readout_instance(s.kind, any_instance)) {
+    if (s.d > 32) return refuse(GVI_ERR_UNSUPPORTED, "read-out rule kernel supports d <= 32");
+    o.route = Route::Readout;
+    o.gx = (unsigned)s.K; o.gy = 1;   // one wave per factor, re-shaped by the bind step
+    return o;
+  }
   const bool reg_inst = reg_supported(s.kind, s.d, s.m) && !s.psi_ext && may_take_reg(r.force);
   if (must_take_reg(r.force) && !reg_inst && !s.psi_ext)
     return refuse(GVI_ERR_UNSUPPORTED, "register kernel not instantiated for this (kind, d)");
@@ -397,6 +421,7 @@ inline bool chain_pair_shape(const RouteFacts& s0, const RouteFacts& s1) {
 // hinge-on-SDF obstacle factors + d = 4 anchors, registered in this order, none empty
 inline bool planar_shape(int nsets, const RouteFacts* s, RouteForce force) {
   if (nsets != 3 || force != RouteForce::Auto) return false;
+  if (s[1].readout_order > 0) return false;   // moments_planar3_kernel / factor_block3_kernel are compiled for the sparse route
   return s[0].kind == KIND_QUAD_PRIOR && s[0].d == 8 && s[0].m == 4 && s[1].kind == KIND_HINGE_SDF_2D && s[1].d == 4 &&
          s[2].kind == KIND_FIXED_PRIOR && s[2].d == 4 && !s[0].closed_form && !s[2].closed_form && s[0].K > 0 && s[1].K > 0 && s[2].K > 0;
 }
@@ -481,8 +506,9 @@ inline void record_pass(PassRecord& last, Route route, bool fused_pair, int nchu
 }
 
 // the integers gvi_profile_geometry reports: 0 closed form, 7 / 6 sign-orbit kernels, 5 SGPR pair launch, 2 lane-per-point,
-// 3 split, 1 generic
+// 3 split, 1 generic, 8 read-out-space rule
 inline int geometry_code(Route route, bool fused_pair, bool closed_form) {
+  if (route == Route::Readout) return 8;
   if (closed_form) return 0;
   if (route == Route::OrbitPsi) return 7;
   if (route == Route::Orbit) return 6;

@@ -117,15 +117,19 @@ def segment_params(sigma, eps, radius, W, c):
     return np.ascontiguousarray(np.concatenate([head, body], axis=1))
 
 
-def _segment_spec(obstacle, kind, T, n, nd, dt, taus, npos, p=None):
+def _segment_spec(obstacle, kind, T, n, nd, dt, taus, npos, p=None, readout_order=0):
     """The segment set beside the obstacle set `obstacle`: one factor per pair of neighbouring states (K = T - 1, start =
     arange, d = 2n), check points at the times taus inside the segment, the obstacle set's sigma, eps, r and field; GH degree p
-    (default: the obstacle set's)."""
+    (default: the obstacle set's).  readout_order > 0: the set takes the read-out-space rule of that order
+    (gvi_factors_set_readout_rule; api.context_for_chain sets it)."""
     W, c = minacc_segment_readout(nd, QC, dt, taus, npos)
     P = obstacle["params"]
-    return dict(kind=kind, d=2 * n, p=obstacle["p"] if p is None else p, start=np.arange(T - 1, dtype=np.int32),
+    spec = dict(kind=kind, d=2 * n, p=obstacle["p"] if p is None else p, start=np.arange(T - 1, dtype=np.int32),
                 params=segment_params(P[:T - 1, 0], P[:T - 1, 1], P[:T - 1, 2], W, c), temperature=np.ones(T - 1),
                 seg_W=W, seg_c=c, sdf_origin=obstacle["sdf_origin"], sdf_cell=obstacle["sdf_cell"], sdf_field=obstacle["sdf_field"])
+    if readout_order:
+        spec["readout_order"] = int(readout_order)
+    return spec
 
 
 def box_params(sigma, eps, lo, hi):
@@ -242,7 +246,7 @@ def balls_params(sigma, eps, r, W, c, tau, centres, velocities, radii):
 
 
 def add_moving_obstacle_set(chain, centres0, velocities, radii, sigma=15.0, eps=0.2, r=0.1, p=3, taus=None, dt=0.25, qc=QC,
-                            temperature=1.0):
+                            temperature=1.0, readout_order=0):
     """A copy of `chain` (the arrays are shared) with a HINGE_BALLS_2D / _3D set appended behind its sets: balls m with centres
     centres0 [M][P] at time 0, constant velocities [M][P] and radii [M] (M <= 8; P = 2 or 3 picks the kind).  State i has the
     time t_i = i dt, and factor i of the set carries ball m at centres0_m + t_i v_m with velocity v_m.
@@ -268,6 +272,8 @@ def add_moving_obstacle_set(chain, centres0, velocities, radii, sigma=15.0, eps=
     params = balls_params(sigma, eps, r, W, c, tau, centres, np.broadcast_to(v, centres.shape), np.broadcast_to(radii, (K, o0.shape[0])))
     spec = dict(kind=PSI_HINGE_BALLS_2D if P == 2 else PSI_HINGE_BALLS_3D, d=d, p=p, start=np.arange(K, dtype=np.int32), params=params,
                 temperature=np.full(K, float(temperature)))
+    if readout_order:                   # the read-out-space rule of that order (gvi_factors_set_readout_rule; api.context_for_chain sets it)
+        spec["readout_order"] = int(readout_order)
     return dict(chain, specs=list(chain["specs"]) + [spec])
 
 
@@ -456,13 +462,15 @@ def circle_sdf(origin, cell, rows, cols, centers, radii):
     return f
 
 
-def make_planar_chain(T=17, p=3, seed=0x5EED + 40, jitter=0.02, p_obstacle=None, horizon=None, segment_taus=None, segment_p=None):
+def make_planar_chain(T=17, p=3, seed=0x5EED + 40, jitter=0.02, p_obstacle=None, horizon=None, segment_taus=None, segment_p=None,
+                      readout_order=0):
     """Planar point-robot planning graph of the reference's own GPU workload: states
     [x, y, vx, vy] (n = 4), T-1 minimum-acceleration priors (d = 8), T hinge-on-SDF obstacle factors on
     every state (d = 4, helpers/CudaOperation.h:491-523) and two fixed-prior end anchors.  p_obstacle: GH degree of the
     obstacle factors (default p + 1); horizon: total time (default (T - 1) / 4, i.e. dt = 0.25).  segment_taus: times in [0, dt]
     of the check points of an additional HINGE_SDF_2D_SEG set on every pair of neighbouring states (d = 8), inserted behind the
-    obstacle set (specs = priors, obstacles, segments, anchors), at GH degree segment_p (default: the obstacle factors')."""
+    obstacle set (specs = priors, obstacles, segments, anchors), at GH degree segment_p (default: the obstacle factors');
+    readout_order > 0 puts that segment set on the read-out-space rule of that order."""
     rng = np.random.default_rng(seed)
     n, nd, K = 4, 2, T - 1
     dt = 0.25 if horizon is None else horizon / (T - 1)
@@ -495,7 +503,7 @@ def make_planar_chain(T=17, p=3, seed=0x5EED + 40, jitter=0.02, p_obstacle=None,
              params=np.concatenate([anchors, Kinv.reshape(2, -1)], axis=1), temperature=np.ones(2), mu0=anchors, Kinv=Kinv),
     ]
     if segment_taus is not None:
-        specs.insert(2, _segment_spec(specs[1], PSI_HINGE_SDF_2D_SEG, T, n, nd, dt, segment_taus, 2, segment_p))
+        specs.insert(2, _segment_spec(specs[1], PSI_HINGE_SDF_2D_SEG, T, n, nd, dt, segment_taus, 2, segment_p, readout_order))
     return dict(name="planar", T=T, n=n, specs=specs, mu0=mu0, D0=D0, U0=U0)
 
 
@@ -511,12 +519,12 @@ def sphere_sdf3d(origin, cell, rows, cols, nz, centers, radii):
     return f
 
 
-def make_obstacle_chain(kind: str, T=9, p=3, seed=0x5EED + 41, segment_taus=None, segment_p=None):
+def make_obstacle_chain(kind: str, T=9, p=3, seed=0x5EED + 41, segment_taus=None, segment_p=None, readout_order=0):
     """n = 6 planning graphs of the reference's other two obstacle workloads: "quad2d" (planar quadrotor,
     state [x, z, phi, vx, vz, w], body of 5 check points, helpers/CudaOperation.h:565-606) and "pr3d" (3-D point
     robot, state [x, y, z, v], trilinear field, :650-683): minimum-acceleration priors (d = 12), one obstacle
     factor per state (d = 6) and two end anchors.  segment_taus ("pr3d" only): as for make_planar_chain, a HINGE_SDF_3D_SEG set
-    (d = 12) behind the obstacle set."""
+    (d = 12) behind the obstacle set, on the read-out-space rule where readout_order > 0."""
     rng = np.random.default_rng(seed + {"quad2d": 0, "pr3d": 1, "arm7": 2}[kind])
     nd = 7 if kind == "arm7" else 3
     n, K = 2 * nd, T - 1
@@ -565,7 +573,7 @@ def make_obstacle_chain(kind: str, T=9, p=3, seed=0x5EED + 41, segment_taus=None
     ]
     if segment_taus is not None:
         assert kind == "pr3d", "segment factors are built for the point robots"
-        specs.insert(2, _segment_spec(specs[1], PSI_HINGE_SDF_3D_SEG, T, n, nd, dt, segment_taus, 3, segment_p))
+        specs.insert(2, _segment_spec(specs[1], PSI_HINGE_SDF_3D_SEG, T, n, nd, dt, segment_taus, 3, segment_p, readout_order))
     return dict(name=kind, T=T, n=n, specs=specs, mu0=mu0, D0=D0, U0=U0)
 
 

@@ -297,6 +297,21 @@ struct DevicePsi {
   std::shared_ptr<const PlanarSDF> sdf2d;
   std::shared_ptr<const SignedDistanceField> sdf3d;
   std::shared_ptr<const ArmModel> arm;
+  // Read-out-space rule (gvi_factors_set_readout_rule): 0 = the sparse Gauss-Hermite rule of the factor's GH
+  // degree, else the order of a dense tensor rule in the space of the kind's linear read-outs.  Factors of one set share it.
+  int readout_order = 0;
+  static bool has_linear_readout(int kind) {
+    return kind == GVI_PSI_HINGE_SDF_2D || kind == GVI_PSI_HINGE_SDF_3D || kind == GVI_PSI_HINGE_SDF_2D_SEG || kind == GVI_PSI_HINGE_SDF_3D_SEG ||
+           kind == GVI_PSI_HINGE_BALLS_2D || kind == GVI_PSI_HINGE_BALLS_3D;
+  }
+  // 0 switches it off; 2 <= order <= 16 with order^P <= 1024 (P = 3, the _3D kinds: order <= 10)
+  DevicePsi& set_readout_rule(int order) {
+    if (!has_linear_readout(kind)) throw std::invalid_argument("read-out rule: only the obstacle kinds on linear read-outs (HINGE_SDF_2D / _3D, the _SEG and BALLS kinds)");
+    const bool three = kind == GVI_PSI_HINGE_SDF_3D || kind == GVI_PSI_HINGE_SDF_3D_SEG || kind == GVI_PSI_HINGE_BALLS_3D;
+    if (order != 0 && (order < 2 || order > (three ? 10 : 16))) throw std::invalid_argument("read-out rule: order is 0 (off) or 2 .. 16 with order^P <= 1024");
+    readout_order = order;
+    return *this;
+  }
   // CudaOperation_PlanarPR / _Quad / _3dpR / _3dArm cost_obstacle* (helpers/CudaOperation.h:491-523, 565-606, 650-683, 752-771)
   static DevicePsi HingeSdf2D(double sigma, double epsilon, double radius, std::shared_ptr<const PlanarSDF> sdf) {
     DevicePsi p{GVI_PSI_HINGE_SDF_2D, {sigma, epsilon, radius}};
@@ -439,7 +454,8 @@ struct DevicePsi {
   bool same_group(const DevicePsi& o) const {
     const bool seg = kind == GVI_PSI_HINGE_SDF_2D_SEG || kind == GVI_PSI_HINGE_SDF_3D_SEG || kind == GVI_PSI_HINGE_HALFSPACE ||
                      kind == GVI_PSI_HINGE_BALLS_2D || kind == GVI_PSI_HINGE_BALLS_3D;
-    return kind == o.kind && sdf2d == o.sdf2d && sdf3d == o.sdf3d && arm == o.arm && (!seg || params.size() == o.params.size());
+    return kind == o.kind && sdf2d == o.sdf2d && sdf3d == o.sdf3d && arm == o.arm && (!seg || params.size() == o.params.size()) &&
+           readout_order == o.readout_order;
   }
   // [sigma, epsilon, radius | W_0 (P x d, row-major) | c_0 (P) | ...]: the kinds' parameter block (DevicePsi stays an aggregate)
   static std::vector<double> segment_block(int P, double sigma, double epsilon, double radius, const std::vector<MatrixXd>& W,
@@ -1157,6 +1173,7 @@ inline std::shared_ptr<FactorBatch> make_factor_batch(const std::shared_ptr<Devi
   }
   upload_psi_shared(*dev, id, dp);
   if (f0.closed_form()) dev->check(gvi_factors_set_closed_form(dev->get(), id, 1));
+  if (dp.readout_order != 0) dev->check(gvi_factors_set_readout_rule(dev->get(), id, dp.readout_order));
   return std::make_shared<FactorBatch>(dev, id, f0._dim, dp.kind, members);
 }
 inline FactorBatch& GVIFactorizedBase::batch() {
@@ -1236,9 +1253,21 @@ class NGDFactorizedBaseGH : public NGDFactorDeviceOps {
   // New parameters for the device psi -- a predicted scene refreshed at a replanning cycle: same kind, shared field and block
   // size, so the factor stays in its set.  The optimizer's update_device_psi_params() sends them to the device.
   void set_device_psi(const DevicePsi& psi) {
-    if (!_psi.same_group(psi) || psi.params.size() != _psi.params.size())
+    DevicePsi q = psi;
+    q.readout_order = _psi.readout_order;             // the rule is the set's: new parameters keep it
+    if (!_psi.same_group(q) || q.params.size() != _psi.params.size())
       throw std::invalid_argument("set_device_psi: the kind, the shared field and the size of the parameter block of a factor are fixed");
-    _psi = psi;
+    _psi = q;
+  }
+  // The read-out-space rule for this factor's psi (DevicePsi::set_readout_rule): call it BEFORE the factor joins an optimizer, so
+  // that the set it lands in is created with the rule; a factor used on its own may change it at any time.  Inside an
+  // optimizer the rule belongs to the whole set: GVIGH::set_readout_rule.
+  void set_readout_rule(int order) {
+    _psi.set_readout_rule(order);
+    if (_batch) {
+      _batch->device()->check(gvi_factors_set_readout_rule(_batch->device()->get(), _batch->set_id(), order));
+      _batch->invalidate();
+    }
   }
   // (x - mu) psi(x), (x - mu)(x - mu)^T psi(x): the closures of :46-48, for callers that integrate on the host
   inline MatrixXd negative_log_probability(const VectorXd& x) const { return MatrixXd::Constant(1, 1, psi(x)); }
@@ -1774,6 +1803,19 @@ class GVIGH {
       _dev->check(gvi_factors_set_params(_dev->get(), (int)s, params.data(), (int64_t)dp.params.size()));
       _batches[s]->invalidate();
     }
+  }
+  // The read-out-space rule (gvi_factors_set_readout_rule) for the device set that holds factor `factor_index` -- the sets are
+  // the groups of factors with the same dimension, GH degree, psi kind and shared field, in first-appearance order; order = 0
+  // returns the set to its sparse rule.  The state stays; a kind without linear read-outs or a bad order throws (GVI_ERR_ARG).
+  void set_readout_rule(int factor_index, int order) {
+    for (size_t s = 0; s < _sets.size(); ++s)
+      for (int i : _sets[s].members)
+        if (i == factor_index) {
+          _dev->check(gvi_factors_set_readout_rule(_dev->get(), (int)s, order));
+          _batches[s]->invalidate();
+          return;
+        }
+    throw std::invalid_argument("set_readout_rule: no such factor");
   }
 
   // cost_value(mean, Precision) (gvibase/GVI-GH-impl.h:176-197): sum_k fact_cost_value + 1/2 log det, operator level

@@ -209,6 +209,27 @@ gvi_status gvi_factors_set_temperature(gvi_ctx* ctx, int set_id, const double* t
  * the set keeps its old blocks.  Cost and gradients of the resident iteration are stale afterwards, as after
  * gvi_factors_set_temperature. */
 gvi_status gvi_factors_set_params(gvi_ctx* ctx, int set_id, const double* psi_params, int64_t params_per_factor);
+/* Read-out-space quadrature for the obstacle kinds whose psi depends on the slice only through P-dimensional linear read-outs
+ * q_j = W_j x + c_j, psi = sum_j f_j(q_j): HINGE_SDF_2D / _3D (q = the first P coordinates, J = 1), HINGE_SDF_2D_SEG / _3D_SEG and
+ * HINGE_BALLS_2D / _3D (P = 2 / 3).  q_j is a P-dimensional Gaussian N(W_j mu + c_j, W_j Sigma W_j^T), and E[psi], E[(x - mu) psi],
+ * E[(x - mu)(x - mu)^T psi] follow exactly from P-dimensional integrals of f_j; with the rule on they are taken by a dense tensor
+ * Gauss-Hermite rule of `order` nodes per read-out coordinate (positive weights, order^P points per check point) instead of the
+ * set's sparse rule in d dimensions, which is off by 10-60 % on a kink.
+ *   order = 0: off (the default): the sparse-grid routes.  Else 2 <= order <= 16 and order^P <= 1024 (P = 3: order <= 10);
+ *   anything else, and a set of any other kind (the priors, RANGE_1D, HOST_CALLBACK, _2D_BODY, _3D_ARM, HINGE_BOX,
+ *   HINGE_HALFSPACE): GVI_ERR_ARG, and the set is unchanged.  Factor dimension d <= 32, above that the passes return
+ *   GVI_ERR_UNSUPPORTED.  A read-out coordinate without variance given the ones before it (a zero row of W: the time stamp as
+ *   third coordinate of a _3D_SEG read-out; two parallel rows) takes the single node 0; a covariance W_j Sigma W_j^T that is
+ *   not positive semidefinite makes every output of that factor NaN.
+ * The rule is the set's own: it holds under every gvi_set_variant (gvi_profile_geometry reports variant 8) and survives
+ * gvi_factors_set_params.  gvi_expand / gvi_moments_from_psi ignore it -- their sigma points are the set's table --, and so do
+ * the clearance and sample-cost calls, which evaluate psi at samples.  In the planning graph a rule on the obstacle set sends the
+ * factor stage out as one launch per set.  Cost and gradients of the resident iteration are stale afterwards, as after
+ * gvi_factors_set_temperature. */
+gvi_status gvi_factors_set_readout_rule(gvi_ctx* ctx, int set_id, int order);
+/* The set's rule: order (0: off), P and J of its kind (0 and 0 for a kind without linear read-outs) and order^P (0 when off).
+ * Any output may be NULL. */
+gvi_status gvi_factors_readout_info(const gvi_ctx* ctx, int set_id, int* order, int* P, int* J, int64_t* points_per_check_point);
 gvi_status gvi_factors_info(const gvi_ctx* ctx, int set_id, int* K, int* d, int* p, int64_t* N);
 
 /* ---- per-pass factor operators (one call = all K factors of the set) ---- */
@@ -522,7 +543,8 @@ gvi_status gvi_profile_last(gvi_ctx* ctx, int set_id, int what /*0 moments kerne
  * call; the records are then cleared and the mode set to `on`.  A pair costs ~14 us of queue gaps: keep it out of timed runs. */
 gvi_status gvi_profile_stages(gvi_ctx* ctx, int on, float* mean_us, int* counts);
 /* Launch geometry of the set's last moments/cost launch: variant (0 closed form, 1 generic, 2 register, 3 split = four waves per factor, d = 16/20/24,
- * 5 register kernel fused with the chain's other set in one launch, 6 sign-orbit kernel, 7 sign-orbit kernel for a non-polynomial psi), chunks. */
+ * 5 register kernel fused with the chain's other set in one launch, 6 sign-orbit kernel, 7 sign-orbit kernel for a non-polynomial psi,
+ * 8 read-out-space rule of gvi_factors_set_readout_rule), chunks. */
 gvi_status gvi_profile_geometry(gvi_ctx* ctx, int set_id, int* variant, int* nchunk, int64_t* chunk);
 /* Stress-test hook of the fence-free hand-over between the epilogue tail and the host (publish_to_host, option
  * "safe_publish"): entries > 0 (a power of two) starts recording the cost every tail publishes at log[(int)sequence & (entries - 1)]
