@@ -19,11 +19,7 @@
 #pragma once
 #include <math.h>
 
-#if defined(__HIPCC__)
-#define GVI_BOX_HD __host__ __device__
-#else
-#define GVI_BOX_HD
-#endif
+#include "hd.hpp"
 
 namespace gvi {
 
@@ -34,7 +30,7 @@ struct BoxSide { double e0, e1, e2; };
 
 // gap = sgn (m - a): how far the mean is inside the hinge (negative: outside).  The caller skips an infinite side: t phi(t) at
 // t = +-inf is 0 * inf.
-GVI_BOX_HD inline BoxSide box_side(double sigma, double sd, double gap, double sgn) {
+GVI_HD inline BoxSide box_side(double sigma, double sd, double gap, double sgn) {
   BoxSide r;
   if (!(sd > 0.0)) {
     const double g = gap > 0.0 ? gap : 0.0;
@@ -72,7 +68,7 @@ GVI_BOX_HD inline BoxSide box_side(double sigma, double sd, double gap, double s
 
 // The two sides of coordinate i of a factor: p = [sigma (d) | eps (d) | lo (d) | hi (d)], mean m, standard deviation sd.
 // An infinite limit switches its side off.
-GVI_BOX_HD inline BoxSide box_coordinate(const double* p, int d, int i, double m, double sd) {
+GVI_HD inline BoxSide box_coordinate(const double* p, int d, int i, double m, double sd) {
   const double sigma = p[i], eps = p[d + i], lo = p[2 * d + i], hi = p[3 * d + i];
   BoxSide s = {0.0, 0.0, 0.0};
   if (hi < INFINITY) {
@@ -88,7 +84,7 @@ GVI_BOX_HD inline BoxSide box_coordinate(const double* p, int d, int i, double m
 
 // psi(x) = sum_i sigma_i [max(0, x_i - (hi_i - eps_i))^2 + max(0, (lo_i + eps_i) - x_i)^2]; an infinite side adds nothing and
 // a coordinate without a finite side is not read
-GVI_BOX_HD inline double psi_hinge_box(const double* p, const double* x, int d) {
+GVI_HD inline double psi_hinge_box(const double* p, const double* x, int d) {
   double cost = 0.0;
   for (int i = 0; i < d; ++i) {
     const double sigma = p[i], eps = p[d + i], lo = p[2 * d + i], hi = p[3 * d + i];
@@ -105,7 +101,7 @@ GVI_BOX_HD inline double psi_hinge_box(const double* p, const double* x, int d) 
 }
 
 // margin(x) = min_i min(hi_i - x_i, x_i - lo_i): negative where a limit itself (not its eps band) is passed; +inf without limits
-GVI_BOX_HD inline double box_margin(const double* p, const double* x, int d) {
+GVI_HD inline double box_margin(const double* p, const double* x, int d) {
   double mg = INFINITY;
   for (int i = 0; i < d; ++i) {
     const double lo = p[2 * d + i], hi = p[3 * d + i];

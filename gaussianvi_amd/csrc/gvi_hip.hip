@@ -492,7 +492,7 @@ RouteFacts route_facts(const FactorSet& s, bool psi_ext) {
   f.closed_form = s.closed_form; f.all_pos = s.all_pos; f.psi_ext = psi_ext;
   f.readout_order = s.readout_order;
   f.has_arm = s.arm.p != nullptr; f.has_sdf = s.sdf_rows != 0;
-  f.arm_ndof = s.arm_ndof; f.seg_J = s.seg_J; f.opsi_rows = orbit_psi_rows(s.kind);
+  f.arm_ndof = s.arm_ndof; f.seg_J = s.seg_J; f.opsi_rows = psi_kind_lead(s.kind);
   f.Np = t.Np; f.Nmp = t.Nmp; f.p = t.p; f.coded = t.coded; f.has_Zq = t.Zq.p != nullptr;
   f.orb_ok = t.orb.ok; f.orb_smax = t.orb.smax; f.orb_tiles = (int64_t)t.orb.tile_s.size();
   return f;
@@ -749,7 +749,7 @@ gvi_status plan_readout(gvi_ctx* c, const FactorSet& s, MomPlan& p, ReadoutInst<
   const int wpb = s.K <= READOUT_WPB_SWITCH ? 1 : 4;
   p.block = 64 * wpb;
   p.grid = dim3((unsigned)((s.K + wpb - 1) / wpb));
-  p.lds = (size_t)wpb * readout_lds_doubles(P, s.d, CLS == READOUT_LEAD ? 1 : s.seg_J) * 8;
+  p.lds = (size_t)wpb * readout_lds_doubles(P, s.d, readout_check_points(CLS, s.seg_J)) * 8;
   p.ro_rule = s.readout_rule.d(); p.ro_order = s.readout_order;
   if (p.lds > 64 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "read-out rule kernel LDS budget");
   return GVI_OK;

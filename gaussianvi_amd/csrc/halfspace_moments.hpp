@@ -20,7 +20,7 @@
 namespace gvi {
 
 // psi at the slice x [d]
-GVI_BOX_HD inline double psi_hinge_halfspace(const double* p, const double* x, int d, int J) {
+GVI_HD inline double psi_hinge_halfspace(const double* p, const double* x, int d, int J) {
   const double* A = p + 3 * J;
   double cost = 0.0;
   for (int j = 0; j < J; ++j) {
@@ -35,7 +35,7 @@ GVI_BOX_HD inline double psi_hinge_halfspace(const double* p, const double* x, i
 }
 
 // signed Euclidean distance to the nearest active face (negative: past it); eps plays no part; +inf when every row is off
-GVI_BOX_HD inline double halfspace_margin(const double* p, const double* x, int d, int J) {
+GVI_HD inline double halfspace_margin(const double* p, const double* x, int d, int J) {
   const double* A = p + 3 * J;
   double mg = INFINITY;
   for (int j = 0; j < J; ++j) {
@@ -53,7 +53,7 @@ GVI_BOX_HD inline double halfspace_margin(const double* p, const double* x, int 
 // One row's work: v_out[c * vstride] = v_j[c] = sum_i a_j[i] S[i * d + c] (c = 0 .. d - 1; vstride lets a kernel interleave the
 // rows of a wave), sd_j = |v_j|, gap = a_j^T mu - (b_j - eps_j); returns box_side of the upper side.  An off row (sigma_j = 0)
 // returns zeros and writes nothing.
-GVI_BOX_HD inline BoxSide halfspace_row(const double* p, int d, int J, int j, const double* mu, const double* S, double* v_out,
+GVI_HD inline BoxSide halfspace_row(const double* p, int d, int J, int j, const double* mu, const double* S, double* v_out,
                                         int vstride = 1) {
   const double sigma = p[j];
   if (!(sigma > 0.0)) return BoxSide{0.0, 0.0, 0.0};

@@ -21,6 +21,7 @@
 // (The tail protocol on a factor's idle second wave, as factor_fused_kernel runs it: every form tried made the compiler merge
 // call sites over a pointer into the argument block and copy the block to scratch -- see block_products_of; not kept.)
 #pragma once
+#include "factor_dev.hpp"
 #include "kernels_factor.hpp"
 
 namespace gvi {

@@ -28,71 +28,19 @@
 // Sum-of-squares psi kinds (quadratic priors) are evaluated as psi = sum_r s_r (u0 + H z)_r^2 with
 // H = A S folded per pass, A = diag(sqrt|e|) W^T [Phi, -I] from the eigen-decomposition of Qinv done
 // once on the host at gvi_factors_add.
+// FactorDev: factor_dev.hpp.  psi of the raw-block kinds at one state (look-ups, *_points walks, psi_point): psi_point.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <utility>
 
-#include "balls_psi.hpp"
-#include "box_moments.hpp"
 #include "device_common.hpp"
 #include "dpp_rowb.hpp"
-#include "halfspace_moments.hpp"
-#include "psi_kinds.hpp"
+#include "factor_dev.hpp"
+#include "psi_point.hpp"
 
 namespace gvi {
-
-__host__ __device__ inline int npairs(int d) { return (d + 1) * (d + 2) / 2; }
-
-// packed z-space moment layout: [0] m0 | [1..d] m1 | then upper triangle of M2 row by row
-__host__ __device__ inline int pair_index(int d, int a, int b) {  // a <= b < d
-  return 1 + d + a * d - a * (a - 1) / 2 + (b - a);
-}
-
-struct FactorDev {
-  int K, d, m, kind;
-  int64_t N, Np;            // points, padded to a multiple of 64 (pad: z = 0, w = 0)
-  const double* Zt;         // [d][Np] dimension-major: lane-over-points loads are coalesced
-  const double* w;          // [Np]
-  const double* Zq;         // [Np / 64][d + 1][64] tile-major copy (row d = w): one contiguous block per 64-point step
-  // Mirror-half table: a sparse Gauss-Hermite grid is symmetric -- with every point z it holds -z with the same weight --
-  // so only one representative per +-pair is stored (first non-zero coordinate positive; the origin with HALF its weight)
-  // and the kernels evaluate psi at z and -z from one load:  Zm [Nmp / 64][d + 1][64], Nm representatives, null if the
-  // table is not symmetric.
-  const double* Zm;
-  int64_t Nm, Nmp;
-  int all_pos;              // 1: every sgn entry is +1 (sum-of-squares kinds with a positive-definite weight)
-  const uint32_t* codes;    // [d/4][Np] four 8-bit node codes per word (tables with <= 256 distinct values) or null
-  const double* lut;        // [256] code -> node value
-  const double* A;          // [K][m][d]   sum-of-squares kinds
-  const double* b;          // [K][m]
-  const double* sgn;        // [K][m]
-  const double* raw;        // [K][raw_stride] raw parameter block (RANGE_1D, HINGE_SDF_*, HINGE_BOX, HINGE_HALFSPACE)
-  int raw_stride;
-  const double* temperature;  // [K]
-  // per-pass products of prep_kernel
-  double* S;                // [K][d][d]
-  double* Sinv;             // [K][d][d]
-  double* Lam;              // [K][d][d]
-  double* H;                // [K][d][m]  H = A S, stored column by column
-  double* Hq;               // [K][4][d][R], R = ceil(m/4): rows v R .. v R + R of H per wave v (split kernel) or null
-  double* u0;               // [K][m]
-  const double* sdf;        // HINGE_SDF_2D: column-major rows x cols signed-distance grid
-  int sdf_rows, sdf_cols, sdf_nz;
-  double sdf_ox, sdf_oy, sdf_oz, sdf_cell;
-  double sdf_inv_cell;                // 1 / sdf_cell: the look-ups multiply (an fp64 division is ~12 VALU instructions; two per 2-D look-up were 25 of the hinge kernel's 79)
-  const double* arm;        // HINGE_SDF_3D_ARM: [ndof, ns, a[ndof], alpha[ndof], d[ndof], bias[ndof], frame[ns], centre[ns][3], radius[ns]]
-  double jko_h;             // > 0: the third spectral output is the JKO map 1 / (l/2 + h + sqrt(l (l + 4h))/2) instead of 1/l
-  double jtol;              // Jacobi stops when off^2 <= jtol * diag^2 (sums of squares)
-  // 1: S is the Cholesky factor L of Sigma instead of its symmetric square root (prep_chol_body), the Sinv slot holds
-  // L^-T.  Only for sum-of-squares psi on a degree >= 3 table, where the quadrature of psi {1, z, z z^T} is exact and
-  // the moments do not depend on WHICH factor S S^T = Sigma maps the nodes (host: FactorSet::dev).
-  int chol;
-  double* Vws;              // [K][d][d] eigenvectors of the previous prep (warm start) or null
-  int warm;                 // 1: start the Jacobi sweeps from Vws (resident NGD iteration only)
-  int seg_J;                // HINGE_SDF_*_SEG: check points per factor (1 .. SEG_MAX_J); HINGE_HALFSPACE: rows per factor (1 .. HALFSPACE_MAX_J); else 0
-};
 
 // ---------------------------------------------------------------------------------------------
 // prep_kernel: one wave (block of 64) per factor.  Parallel-ordered (round-robin) cyclic Jacobi on
@@ -839,230 +787,6 @@ __global__ __launch_bounds__(64) void prep_all_kernel(PrepList L) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// psi evaluation at an x-space point (generic kernel, expand-based).
-// ---------------------------------------------------------------------------------------------
-__device__ inline double psi_range_1d(const double* p, double x) {
-  // p = [y, mu_p, f*b, sig_r_sq, sig_p_sq]            (src/1d_example.cpp:25-35)
-  const double e = x - p[1], r = p[0] - p[2] / x;
-  return e * e / p[4] / 2 + r * r / p[3] / 2;
-}
-
-// PlanarSDF::getSignedDistance (helpers/CudaOperation.h:61-103): query clamped to the grid, bilinear
-// interpolation of the column-major field (data[r + c rows], :130).
-__device__ inline double sdf2d_lookup(const FactorDev& f, double px, double py) {
-  const double xmax = f.sdf_ox + (f.sdf_cols - 1.0) * f.sdf_cell, ymax = f.sdf_oy + (f.sdf_rows - 1.0) * f.sdf_cell;
-  const double xin = px < f.sdf_ox ? f.sdf_ox : (px > xmax ? xmax : px);
-  const double yin = py < f.sdf_oy ? f.sdf_oy : (py > ymax ? ymax : py);
-  const double col = (xin - f.sdf_ox) * f.sdf_inv_cell, row = (yin - f.sdf_oy) * f.sdf_inv_cell;
-  const double lr = floor(row), lc = floor(col), hr = lr + 1.0, hc = lc + 1.0;
-  const int lri = (int)lr, lci = (int)lc;
-  const int hri = lri + 1 < f.sdf_rows ? lri + 1 : f.sdf_rows - 1;    // weight is 0 there; keeps the read in bounds
-  const int hci = lci + 1 < f.sdf_cols ? lci + 1 : f.sdf_cols - 1;
-  const int R = f.sdf_rows;
-  return (hr - row) * (hc - col) * f.sdf[lri + lci * R] + (row - lr) * (hc - col) * f.sdf[hri + lci * R] +
-         (hr - row) * (col - lc) * f.sdf[lri + hci * R] + (row - lr) * (col - lc) * f.sdf[hri + hci * R];
-}
-
-// SignedDistanceField::getSignedDistance (helpers/CudaOperation.h:165-226): clamped trilinear interpolation of
-// data[r + c rows + z rows cols] (:304-306); x -> column, y -> row, z -> slice.
-__device__ inline double sdf3d_lookup(const FactorDev& f, double px, double py, double pz) {
-  const double xmax = f.sdf_ox + (f.sdf_cols - 1.0) * f.sdf_cell, ymax = f.sdf_oy + (f.sdf_rows - 1.0) * f.sdf_cell,
-               zmax = f.sdf_oz + (f.sdf_nz - 1.0) * f.sdf_cell;
-  const double xin = px < f.sdf_ox ? f.sdf_ox : (px > xmax ? xmax : px);
-  const double yin = py < f.sdf_oy ? f.sdf_oy : (py > ymax ? ymax : py);
-  const double zin = pz < f.sdf_oz ? f.sdf_oz : (pz > zmax ? zmax : pz);
-  const double col = (xin - f.sdf_ox) * f.sdf_inv_cell, row = (yin - f.sdf_oy) * f.sdf_inv_cell, zz = (zin - f.sdf_oz) * f.sdf_inv_cell;
-  const double lr = floor(row), lc = floor(col), lz = floor(zz), hr = lr + 1.0, hc = lc + 1.0, hz = lz + 1.0;
-  const int lri = (int)lr, lci = (int)lc, lzi = (int)lz;
-  const int hri = lri + 1 < f.sdf_rows ? lri + 1 : f.sdf_rows - 1;
-  const int hci = lci + 1 < f.sdf_cols ? lci + 1 : f.sdf_cols - 1;
-  const int hzi = lzi + 1 < f.sdf_nz ? lzi + 1 : f.sdf_nz - 1;
-  const size_t R = f.sdf_rows, RC = R * f.sdf_cols;
-  const double* g = f.sdf;
-  return (hr - row) * (hc - col) * (hz - zz) * g[lri + lci * R + lzi * RC] + (row - lr) * (hc - col) * (hz - zz) * g[hri + lci * R + lzi * RC] +
-         (hr - row) * (col - lc) * (hz - zz) * g[lri + hci * R + lzi * RC] + (row - lr) * (col - lc) * (hz - zz) * g[hri + hci * R + lzi * RC] +
-         (hr - row) * (hc - col) * (zz - lz) * g[lri + lci * R + hzi * RC] + (row - lr) * (hc - col) * (zz - lz) * g[hri + lci * R + hzi * RC] +
-         (hr - row) * (col - lc) * (zz - lz) * g[lri + hci * R + hzi * RC] + (row - lr) * (col - lc) * (zz - lz) * g[hri + hci * R + hzi * RC];
-}
-
-__device__ __forceinline__ double hinge_sq(double sd, double thr, double slope, double sigma) {
-  const double err = sd > thr ? 0.0 : (thr - sd) * slope;
-  return err * err * sigma;
-}
-
-// Check points of the hinge-on-SDF kinds.  Each *_points function walks the check points b of one factor at one state and
-// calls visit(sd_b, r_b) with the signed distance at the point and the radius of its ball; psi (the sum of the hinges) and the
-// clearance (min_b sd_b - r_b, costs of sampled trajectories: kernels_sample_cost.hpp) are two visitors of the SAME points
-// in the same arithmetic.
-
-// planar point robot (CudaOperation_PlanarPR::cost_obstacle_planar, helpers/CudaOperation.h:491-523): one ball at
-// (x0, x1), slope 1.  p = [sigma, eps, r].
-template <typename V>
-__device__ __forceinline__ void hinge_sdf2d_points(const FactorDev& f, const double* p, double px, double py, V&& visit) {
-  visit(sdf2d_lookup(f, px, py), p[2]);
-}
-__device__ inline double psi_hinge_sdf2d(const FactorDev& f, const double* p, double px, double py) {
-  double cost = 0.0;
-  hinge_sdf2d_points(f, p, px, py, [&](double sd, double r) { cost = hinge_sq(sd, p[1] + r, 1.0, p[0]); });
-  return cost;
-}
-
-// planar quadrotor body (CudaOperation_Quad::cost_obstacle_planar / vec_balls, helpers/CudaOperation.h:565-606):
-// pose (x, z, phi) = x[0:3]; n_balls check points along the body axis starting at
-// pos - (L - 1.5 r)/2 (cos phi, sin phi), spaced L/n_balls.  p = [sigma, eps, r, slope, n_balls, L].
-template <typename V>
-__device__ __forceinline__ void hinge_sdf2d_body_points(const FactorDev& f, const double* p, double px, double pz, double phi, V&& visit) {
-  double sn, cs;
-  sincos(phi, &sn, &cs);
-  const double r = p[2], L = p[5];
-  const int nb = (int)p[4];
-  const double lx = px - (L - r * 1.5) * cs / 2.0, lz = pz - (L - r * 1.5) * sn / 2.0;
-  for (int i = 0; i < nb; ++i) visit(sdf2d_lookup(f, lx + L * cs / nb * i, lz + L * sn / nb * i), r);
-}
-__device__ inline double psi_hinge_sdf2d_body(const FactorDev& f, const double* p, double px, double pz, double phi) {
-  const double thr = p[1] + p[2];
-  double cost = 0.0;
-  hinge_sdf2d_body_points(f, p, px, pz, phi, [&](double sd, double) { cost += hinge_sq(sd, thr, p[3], p[0]); });
-  return cost;
-}
-
-// 3-D point robot (CudaOperation_3dpR::cost_obstacle_planar, helpers/CudaOperation.h:650-683).  p = [sigma, eps, r].
-template <typename V>
-__device__ __forceinline__ void hinge_sdf3d_points(const FactorDev& f, const double* p, double px, double py, double pz, V&& visit) {
-  visit(sdf3d_lookup(f, px, py, pz), p[2]);
-}
-__device__ inline double psi_hinge_sdf3d(const FactorDev& f, const double* p, double px, double py, double pz) {
-  double cost = 0.0;
-  hinge_sdf3d_points(f, p, px, py, pz, [&](double sd, double r) { cost = hinge_sq(sd, p[1] + r, 1.0, p[0]); });
-  return cost;
-}
-
-// 7-DOF-style arm (CudaOperation_3dArm::cost_obstacle + ForwardKinematics, helpers/CudaOperation.h:325-399, 752-771):
-// sphere s sits on frame[s] of the DH chain T = prod_{i <= frame} DH(i, x_i + bias_i); n_balls = the factor dimension
-// (theta.size(), :753), cost = sigma sum_s hinge(eps + radius_s - sdf(p_s))^2.  The reference builds every DH matrix
-// from cosf / sinf (single precision, :388-395; products of two trig terms are float products) -- restated as such.
-// Frames are non-decreasing (checked on the host), so the chain is advanced once.  p = [sigma, eps].
-template <typename V>
-__device__ __forceinline__ void hinge_sdf3d_arm_points(const FactorDev& f, const double* x, int d, V&& visit) {
-  const double* A = f.arm;
-  const int nd = (int)A[0], ns = (int)A[1];
-  const double *a = A + 2, *al = a + nd, *dl = al + nd, *tb = dl + nd, *fr = tb + nd, *ce = fr + ns, *ra = ce + 3 * ns;
-  double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};           // rows 0..2 of the homogeneous transform
-  const int nb = d < ns ? d : ns;
-  int done = -1;                                                  // last joint folded into T
-  for (int s = 0; s < nb; ++s) {
-    const int frame = (int)fr[s];
-    while (done < frame) {
-      const int i = ++done;
-      const float th = (float)(x[i] + tb[i]), alf = (float)al[i];
-      // cosf / sinf of the reference: float in, float out.  Libm's differ in the last float bit; the correctly rounded
-      // value (double trig of the float argument, rounded to float) is the representative, as in the oracle
-      const float c = (float)cos((double)th), sn = (float)sin((double)th), cA = (float)cos((double)alf), sA = (float)sin((double)alf);
-      const double m00 = c, m01 = -sn * cA, m02 = sn * sA, m03 = a[i] * c;
-      const double m10 = sn, m11 = c * cA, m12 = -c * sA, m13 = a[i] * sn;
-      const double m21 = sA, m22 = cA, m23 = dl[i];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const double t0 = T[r * 4], t1 = T[r * 4 + 1], t2 = T[r * 4 + 2], t3 = T[r * 4 + 3];
-        T[r * 4] = t0 * m00 + t1 * m10;
-        T[r * 4 + 1] = t0 * m01 + t1 * m11 + t2 * m21;
-        T[r * 4 + 2] = t0 * m02 + t1 * m12 + t2 * m22;
-        T[r * 4 + 3] = t0 * m03 + t1 * m13 + t2 * m23 + t3;
-      }
-    }
-    const double cx = ce[3 * s], cy = ce[3 * s + 1], cz = ce[3 * s + 2];
-    const double px = T[3] + (T[0] * cx + T[1] * cy + T[2] * cz);
-    const double py = T[7] + (T[4] * cx + T[5] * cy + T[6] * cz);
-    const double pz = T[11] + (T[8] * cx + T[9] * cy + T[10] * cz);
-    visit(sdf3d_lookup(f, px, py, pz), ra[s]);
-  }
-}
-__device__ inline double psi_hinge_sdf3d_arm(const FactorDev& f, const double* p, const double* x, int d) {
-  double cost = 0.0;
-  hinge_sdf3d_arm_points(f, x, d, [&](double sd, double r) { cost += hinge_sq(sd, p[1] + r, 1.0, p[0]); });
-  return cost;
-}
-
-// Obstacle factor on a segment (no reference counterpart): J = f.seg_J check points, each a linear
-// read-out q_j = W_j x + c_j of the factor's slice x [d] (for d = 2n the pair of support states: W_j = the position rows of the
-// Gauss-Markov interpolation [A(tau_j) | B(tau_j)]), one ball of radius r at each, slope 1.
-// p = [sigma, eps, r | W_0 (P x d, row-major) | c_0 (P) | ... | W_{J-1} | c_{J-1}].  P = 2: the planar grid, P = 3: the 3-D field.
-template <int P, typename V>
-__device__ __forceinline__ void hinge_sdf_seg_points(const FactorDev& f, const double* p, const double* x, int d, V&& visit) {
-  const double* wc = p + 3;
-  for (int j = 0; j < f.seg_J; ++j, wc += P * (d + 1)) {
-    double q[P];
-#pragma unroll
-    for (int r = 0; r < P; ++r) {
-      double v = wc[P * d + r];
-      for (int c = 0; c < d; ++c) v = fma(wc[r * d + c], x[c], v);
-      q[r] = v;
-    }
-    if constexpr (P == 2) visit(sdf2d_lookup(f, q[0], q[1]), p[2]);
-    else visit(sdf3d_lookup(f, q[0], q[1], q[P - 1]), p[2]);
-  }
-}
-template <typename V>
-__device__ __forceinline__ void hinge_sdf2d_seg_points(const FactorDev& f, const double* p, const double* x, int d, V&& visit) {
-  hinge_sdf_seg_points<2>(f, p, x, d, visit);
-}
-template <typename V>
-__device__ __forceinline__ void hinge_sdf3d_seg_points(const FactorDev& f, const double* p, const double* x, int d, V&& visit) {
-  hinge_sdf_seg_points<3>(f, p, x, d, visit);
-}
-__device__ inline double psi_hinge_sdf2d_seg(const FactorDev& f, const double* p, const double* x, int d) {
-  double cost = 0.0;
-  hinge_sdf2d_seg_points(f, p, x, d, [&](double sd, double r) { cost += hinge_sq(sd, p[1] + r, 1.0, p[0]); });
-  return cost;
-}
-__device__ inline double psi_hinge_sdf3d_seg(const FactorDev& f, const double* p, const double* x, int d) {
-  double cost = 0.0;
-  hinge_sdf3d_seg_points(f, p, x, d, [&](double sd, double r) { cost += hinge_sq(sd, p[1] + r, 1.0, p[0]); });
-  return cost;
-}
-
-// psi of factor k of a set that keeps its raw parameter block (PSI_RAW, psi_kinds.hpp) at the state slice x [d]: THE chain
-// from a kind to its psi_* function.  NaN for a kind without raw psi (sum of squares: the caller's (A, b, sgn) form; host psi).
-__device__ __forceinline__ double psi_point(const FactorDev& f, int k, const double* x) {
-  const double* p = f.raw + (size_t)k * f.raw_stride;
-  if (f.kind == KIND_RANGE_1D) return psi_range_1d(p, x[0]);
-  if (f.kind == KIND_HINGE_SDF_2D) return psi_hinge_sdf2d(f, p, x[0], x[1]);
-  if (f.kind == KIND_HINGE_SDF_2D_BODY) return psi_hinge_sdf2d_body(f, p, x[0], x[1], x[2]);
-  if (f.kind == KIND_HINGE_SDF_3D) return psi_hinge_sdf3d(f, p, x[0], x[1], x[2]);
-  if (f.kind == KIND_HINGE_SDF_3D_ARM) return psi_hinge_sdf3d_arm(f, p, x, f.d);
-  if (f.kind == KIND_HINGE_SDF_2D_SEG) return psi_hinge_sdf2d_seg(f, p, x, f.d);
-  if (f.kind == KIND_HINGE_SDF_3D_SEG) return psi_hinge_sdf3d_seg(f, p, x, f.d);
-  if (f.kind == KIND_HINGE_BOX) return psi_hinge_box(p, x, f.d);
-  if (f.kind == KIND_HINGE_HALFSPACE) return psi_hinge_halfspace(p, x, f.d, f.seg_J);
-  if (f.kind == KIND_HINGE_BALLS_2D) return psi_hinge_balls<2>(p, x, f.d, f.seg_J);
-  if (f.kind == KIND_HINGE_BALLS_3D) return psi_hinge_balls<3>(p, x, f.d, f.seg_J);
-  return __builtin_nan("");
-}
-
-// psi and / or clearance of factor k of a raw-block set at the state slice x [d].  psi is psi_point; the clearance (PSI_CLEARANCE
-// kinds) walks the same *_points as the kind's psi with a min-visitor.  eps and slope play no part in the clearance.
-__device__ __forceinline__ void hinge_psi_clearance(const FactorDev& f, int k, const double* x, bool want_psi, bool want_clr,
-                                                    double& psi, double& clr) {
-  if (want_psi) psi = psi_point(f, k, x);
-  if (!want_clr) return;
-  const double* p = f.raw + (size_t)k * f.raw_stride;
-  double c = __builtin_inf();
-  auto keep = [&](double sd, double r) { c = fmin(c, sd - r); };
-  if (f.kind == KIND_HINGE_SDF_2D) hinge_sdf2d_points(f, p, x[0], x[1], keep);
-  else if (f.kind == KIND_HINGE_SDF_2D_BODY) hinge_sdf2d_body_points(f, p, x[0], x[1], x[2], keep);
-  else if (f.kind == KIND_HINGE_SDF_3D) hinge_sdf3d_points(f, p, x[0], x[1], x[2], keep);
-  else if (f.kind == KIND_HINGE_SDF_3D_ARM) hinge_sdf3d_arm_points(f, x, f.d, keep);
-  else if (f.kind == KIND_HINGE_SDF_2D_SEG) hinge_sdf2d_seg_points(f, p, x, f.d, keep);
-  else if (f.kind == KIND_HINGE_SDF_3D_SEG) hinge_sdf3d_seg_points(f, p, x, f.d, keep);
-  else if (f.kind == KIND_HINGE_BOX) c = box_margin(p, x, f.d);                        // limits on the slice itself (box_moments.hpp): the margin
-  else if (f.kind == KIND_HINGE_HALFSPACE) c = halfspace_margin(p, x, f.d, f.seg_J);   // rows a_j^T x <= b_j (halfspace_moments.hpp): distance to the nearest active face
-  else if (f.kind == KIND_HINGE_BALLS_2D) hinge_balls_points<2>(p, x, f.d, f.seg_J, keep);   // analytic balls (balls_psi.hpp): no grid
-  else if (f.kind == KIND_HINGE_BALLS_3D) hinge_balls_points<3>(p, x, f.d, f.seg_J, keep);
-  else c = __builtin_nan("");   // no clearance for this kind: the host refuses such a set before any launch
-  clr = c;
-}
-
-// ---------------------------------------------------------------------------------------------
 // moments_generic_kernel: any d (<= 32), any psi kind.  Block = 256 threads handles one factor and a
 // range of points in sub-chunks of 256: stage 1 (thread = point) expands x = mu + S z, evaluates
 // psi and parks [z, 1] and c = w psi in LDS; stage 2 (thread = output pair (a,b)) accumulates
@@ -1404,7 +1128,7 @@ struct PsiRange1D {
 // nonlinear obstacle costs: pose = (mu + S z)[0:NPOSE] (NPOSE rows of S in LDS), SDF look-ups straight from L2
 template <int D, int KIND>
 struct PsiHingeSdf {
-  static constexpr int NPOSE = KIND == KIND_HINGE_SDF_2D ? 2 : 3;
+  static constexpr int NPOSE = psi_kind_lead(KIND);
   static constexpr int NPAR = KIND == KIND_HINGE_SDF_2D_BODY ? 6 : 3;
   static constexpr int LDS = NPOSE * D + NPOSE + NPAR;
   static constexpr bool GUARD = false;
@@ -1415,13 +1139,7 @@ struct PsiHingeSdf {
   }
   __device__ static double eval(const double (&z)[D], const double* hs, const MomArgs& a) {
     double pose[NPOSE];
-#pragma unroll
-    for (int r = 0; r < NPOSE; ++r) {
-      double v = hs[NPOSE * D + r];
-#pragma unroll
-      for (int c = 0; c < D; ++c) v = fma(hs[r * D + c], z[c], v);
-      pose[r] = v;
-    }
+    readout_q<D, NPOSE>(hs, z, pose);                                       // (S rows | mu) is a (G | g) block
     const double* p = hs + NPOSE * D + NPOSE;
     if (KIND == KIND_HINGE_SDF_2D) return psi_hinge_sdf2d(a.f, p, pose[0], pose[1]);
     if (KIND == KIND_HINGE_SDF_2D_BODY) return psi_hinge_sdf2d_body(a.f, p, pose[0], pose[1], pose[NPOSE - 1]);
@@ -1446,23 +1164,7 @@ struct PsiHingeSeg {
     const double* S = a.f.S + (size_t)k * D * D;
     const double* mu = a.mu + (size_t)k * D;
     const int J = a.f.seg_J < SEG_MAX_J ? a.f.seg_J : SEG_MAX_J;      // the host admits 1 .. SEG_MAX_J; keeps the LDS slice
-    for (int e = lane; e < J * STRIDE; e += 64) {
-      const int j = e / STRIDE, rem = e - j * STRIDE;
-      const double* Wj = raw + 3 + j * STRIDE;
-      double v;
-      if (rem < P * D) {                                              // G_j[r][c] = sum_e W_j[r][e] S[e][c]
-        const int r = rem / D, c = rem - r * D;
-        v = 0.0;
-#pragma unroll
-        for (int q = 0; q < D; ++q) v = fma(Wj[r * D + q], S[q * D + c], v);
-      } else {                                                        // g_j[r] = c_j[r] + W_j[r] mu
-        const int r = rem - P * D;
-        v = Wj[P * D + r];
-#pragma unroll
-        for (int q = 0; q < D; ++q) v = fma(Wj[r * D + q], mu[q], v);
-      }
-      hs[e] = v;
-    }
+    readout_fold<D, P>(ReadoutView{raw, P, D, J, READOUT_SEG}, S, mu, hs, lane);
     if (lane < 3) hs[SEG_MAX_J * STRIDE + lane] = raw[lane];
   }
   __device__ static double eval(const double (&z)[D], const double* hs, const MomArgs& a) {
@@ -1471,15 +1173,8 @@ struct PsiHingeSeg {
     double cost = 0.0;
 #pragma unroll 1
     for (int j = 0; j < J; ++j) {
-      const double* G = hs + j * STRIDE;
       double q[P];
-#pragma unroll
-      for (int r = 0; r < P; ++r) {
-        double v = G[P * D + r];
-#pragma unroll
-        for (int c = 0; c < D; ++c) v = fma(G[r * D + c], z[c], v);
-        q[r] = v;
-      }
+      readout_q<D, P>(hs + j * STRIDE, z, q);
       const double sd = P == 2 ? sdf2d_lookup(a.f, q[0], q[1]) : sdf3d_lookup(a.f, q[0], q[1], q[P - 1]);
       cost += hinge_sq(sd, thr, 1.0, sigma);
     }
@@ -1511,24 +1206,9 @@ struct PsiHingeBalls {
     const double* S = a.f.S + (size_t)k * D * D;
     const double* mu = a.mu + (size_t)k * D;
     const int J = a.f.seg_J < SEG_MAX_J ? a.f.seg_J : SEG_MAX_J;      // the host admits 1 .. SEG_MAX_J; keeps the LDS slice
-    for (int e = lane; e < J * STRIDE; e += 64) {
-      const int j = e / STRIDE, rem = e - j * STRIDE;
-      const double* Wj = raw + 3 + j * (STRIDE + 1);
-      double v;
-      if (rem < P * D) {                                              // G_j[r][c] = sum_e W_j[r][e] S[e][c]
-        const int r = rem / D, c = rem - r * D;
-        v = 0.0;
-#pragma unroll
-        for (int q = 0; q < D; ++q) v = fma(Wj[r * D + q], S[q * D + c], v);
-      } else {                                                        // g_j[r] = c_j[r] + W_j[r] mu
-        const int r = rem - P * D;
-        v = Wj[P * D + r];
-#pragma unroll
-        for (int q = 0; q < D; ++q) v = fma(Wj[r * D + q], mu[q], v);
-      }
-      hs[e] = v;
-    }
-    const double* balls = raw + 3 + J * (STRIDE + 1);
+    const ReadoutView v{raw, P, D, J, READOUT_BALLS};
+    readout_fold<D, P>(v, S, mu, hs, lane);
+    const double* balls = v.balls();
     const double thr = raw[1] + raw[2];
     if (lane < J * BALLS_SLOTS) {                                     // lane = (check point j, slot m)
       const int j = lane / BALLS_SLOTS, m = lane - j * BALLS_SLOTS;
@@ -1537,7 +1217,7 @@ struct PsiHingeBalls {
       if (!balls_slot_empty(R)) {
         int rank = 0;                                                 // non-empty slots before m
         for (int q = 0; q < m; ++q) rank += balls_slot_empty(balls[q * (2 * P + 1) + 2 * P]) ? 0 : 1;
-        const double tau = raw[3 + j * (STRIDE + 1) + STRIDE];
+        const double tau = v.tau(j);
 #pragma unroll
         for (int r = 0; r < P; ++r) hs[CEN + (j * BALLS_SLOTS + rank) * P + r] = fma(tau, b[P + r], b[r]);
         if (j == 0) {
@@ -1562,15 +1242,8 @@ struct PsiHingeBalls {
     double cost = 0.0;
 #pragma unroll 1
     for (int j = 0; j < J; ++j) {
-      const double* G = hs + j * STRIDE;
       double q[P];
-#pragma unroll
-      for (int r = 0; r < P; ++r) {
-        double v = G[P * D + r];
-#pragma unroll
-        for (int c = 0; c < D; ++c) v = fma(G[r * D + c], z[c], v);
-        q[r] = v;
-      }
+      readout_q<D, P>(hs + j * STRIDE, z, q);
       const double* cen = hs + CEN + j * BALLS_SLOTS * P;
       double sd = INFINITY;
 #pragma unroll 1

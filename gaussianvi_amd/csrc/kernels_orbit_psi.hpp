@@ -17,6 +17,7 @@
 // root) and epilogue (back-transform) are the existing ones.
 #pragma once
 #include "kernels_orbit.hpp"
+#include "psi_point.hpp"
 
 namespace gvi {
 
@@ -31,12 +32,10 @@ struct OrbitPsiArgs {
   OrbitDev ob;
 };
 
-// leading coordinates of x that psi reads
-__host__ __device__ constexpr int orbit_psi_rows(int kind) {
-  return kind == KIND_RANGE_1D ? 1 : kind == KIND_HINGE_SDF_2D ? 2 : kind == KIND_HINGE_SDF_3D_ARM ? 7 : 3;
-}
+// leading coordinates of x that psi reads: the kind's `lead` column (psi_kinds.hpp)
+__host__ __device__ constexpr int orbit_psi_rows(int kind) { return psi_kind_lead(kind); }
 
-// psi_hinge_sdf3d_arm (kernels_factor.hpp; CudaOperation_3dArm::cost_obstacle + ForwardKinematics, helpers/CudaOperation.h:
+// psi_hinge_sdf3d_arm (psi_point.hpp; CudaOperation_3dArm::cost_obstacle + ForwardKinematics, helpers/CudaOperation.h:
 // 325-399, 752-771) with the joint angles in REGISTERS: the joints are folded in a compile-time loop (x[i] with a constant
 // index), the spheres of frame i follow joint i -- frames are non-decreasing (host-checked), so this is the same sequence of
 // operations, sphere by sphere, as the generic form's "advance the chain to the sphere's frame".

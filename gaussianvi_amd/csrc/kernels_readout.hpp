@@ -21,13 +21,10 @@
 #include "device_common.hpp"
 #include "kernels_factor.hpp"
 #include "kernels_orbit.hpp"
+#include "psi_point.hpp"
 #include "readout_moments.hpp"
 
 namespace gvi {
-
-// how a kind lays its read-outs out: the first P coordinates of the slice (HINGE_SDF_2D / _3D), [W_j | c_j] blocks (the _SEG
-// kinds), [W_j | c_j | tau_j] blocks and ball slots (HINGE_BALLS_*)
-enum { READOUT_LEAD = 0, READOUT_SEG = 1, READOUT_BALLS = 2 };
 
 struct ReadoutArgs {
   MomArgs a;
@@ -45,7 +42,7 @@ __global__ __launch_bounds__(256) void moments_readout_kernel(ReadoutArgs ra) {
   extern __shared__ double rosm[];
   const FactorDev& f = a.f;
   const int d = f.d, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, order = ra.order;
-  const int J = CLS == READOUT_LEAD ? 1 : f.seg_J;
+  const int J = readout_check_points(CLS, f.seg_J);
   const int64_t kw = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
   if (kw >= f.K) return;                                       // the whole wave; nothing below waits for another wave
   const int k = (int)kw;
@@ -60,7 +57,9 @@ __global__ __launch_bounds__(256) void moments_readout_kernel(ReadoutArgs ra) {
   const double* p = f.raw + (size_t)k * f.raw_stride;
   const double* mu = a.mu + (size_t)k * d;
   const double* S = f.S + (size_t)k * d * d;
-  const int stride = CLS == READOUT_BALLS ? balls_point_stride(P, d) : P * (d + 1);
+  // Not through ReadoutView: its form of the same addresses took the <3, SEG / BALLS> instances from 127 / 125 to 129 VGPRs, one
+  // occupancy step; P * (d + 1) spelled out keeps the SEG instances' code what it was (profiles/psi_point_refactor.txt).
+  const int stride = CLS == READOUT_BALLS ? readout_stride(CLS, P, d) : P * (d + 1);
   const double* balls = p + 3 + J * stride;                    // READOUT_BALLS only
   const double sigma = p[0], thr = p[1] + p[2];
   const bool full = a.full != 0;

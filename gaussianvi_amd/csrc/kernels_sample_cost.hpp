@@ -1,6 +1,6 @@
 // Costs of sampled trajectories: the factors' psi, and the clearance of the hinge-on-SDF factors, evaluated at samples
 // X [S][T][n] of q instead of at sigma points.  No reference counterpart (the reference evaluates psi at sigma points only;
-// the psi functions called here cite their reference lines in kernels_factor.hpp).
+// the psi functions called here cite their reference lines in psi_point.hpp).
 //
 //   cost[s][k] = psi_k(x_s[start_k n .. start_k n + d)) / temperature_k        clr[s][k] = min_b sdf(p_b) - r_b
 //
@@ -13,7 +13,7 @@
 //     forms its residual and squares it; the m squares are summed by an xor butterfly over the group (rows m .. P - 1 carry 0),
 //     a fixed tree.  Lane r = 0 stores.
 //   the other kinds (RANGE_1D, HINGE_SDF_*): one thread per (sample, factor), factor index fastest, through the psi_* functions
-//     and the *_points walkers of kernels_factor.hpp.
+//     and the *_points walkers of psi_point.hpp (hinge_psi_clearance).
 //   A slice that holds a non-finite value gives NaN without entering the psi / SDF code (no index is formed from a NaN).
 // sample_cost_reduce_kernel, one workgroup of 256 per sample: J[s] = sum over the concatenated cost row [set 0 | set 1 | ...]
 //   -- thread t adds entries t, t + 256, ... in ascending order, then the 256 partial sums are folded by halving (t += t + 128,
@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "kernels_factor.hpp"
+#include "psi_point.hpp"
 
 namespace gvi {
 

@@ -2,19 +2,14 @@
 // about a kind -- its operand rows m, the size of its parameter block, the condition on the factor dimension and what it
 // keeps, reads and offers.  gvi_factors_add lays a set out with psi_kind_layout and checks the values of its parameter
 // blocks with psi_kind_check_params; every other site asks psi_kind_is.  A new kind is one row here, its psi_* function in
-// kernels_factor.hpp (psi_point) and, where it has compiled instances, a line in the with_*_instance lists of routes.hpp.
+// psi_point.hpp (psi_point) and, where it has compiled instances, a line in the with_*_instance lists of routes.hpp.
 // Plain C++17 that also compiles without HIP (tests/stubs/psi_kinds_check.cpp runs it under AddressSanitizer / UBSan).
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/gvi_hip.h"
-
-#if defined(__HIPCC__)
-#define GVI_KIND_HD __host__ __device__
-#else
-#define GVI_KIND_HD
-#endif
+#include "hd.hpp"
 
 namespace gvi {
 
@@ -49,16 +44,20 @@ enum : unsigned {
   PSI_SDF = PSI_SDF_2D | PSI_SDF_3D
 };
 
+// how a PSI_READOUT kind lays its read-outs out (ReadoutView, readout_view.hpp): the first P coordinates of the slice (HINGE_SDF_2D / _3D),
+// [W_j | c_j] blocks (the _SEG kinds), [W_j | c_j | tau_j] blocks and ball slots (HINGE_BALLS_*)
+enum { READOUT_NONE = -1, READOUT_LEAD = 0, READOUT_SEG = 1, READOUT_BALLS = 2 };
+
 // m: operand rows of the sum-of-squares form.  need: doubles of one factor's parameter block.
 enum PsiRows { M_NONE, M_HALF_D, M_D };
 enum PsiNeed {
   NEED_FIXED,       // `arg` doubles; a caller's stride may be longer
   NEED_QUAD,        // [Phi (m x m) | Qinv (m x m)]: 2 m^2
   NEED_MEAN_QUAD,   // [mu0 (d) | Qinv (d x d)]: d + d^2
-  NEED_SEG,         // exactly 3 + J P (d + 1), P = `arg`, 1 <= J <= SEG_MAX_J: J is a property of the set
+  NEED_SEG,         // exactly 3 + J P (d + 1), P = `ro_P`, 1 <= J <= SEG_MAX_J: J is a property of the set
   NEED_BOX,         // exactly 4 d: [sigma | eps | lo | hi]
   NEED_HALFSPACE,   // exactly J (d + 3), 1 <= J <= HALFSPACE_MAX_J: J is a property of the set
-  NEED_BALLS        // exactly 3 + J (P (d + 1) + 1) + BALLS_MAX_M (2 P + 1), P = `arg`, 1 <= J <= SEG_MAX_J: J is a property of the set
+  NEED_BALLS        // exactly 3 + J (P (d + 1) + 1) + BALLS_MAX_M (2 P + 1), P = `ro_P`, 1 <= J <= SEG_MAX_J: J is a property of the set
 };
 enum PsiDim { D_ANY, D_ONE, D_EVEN, D_MIN };   // D_MIN: d >= `dmin`
 
@@ -71,24 +70,27 @@ struct PsiKindRow {
   PsiDim dim;
   int dmin;
   const char* dim_msg;
+  int ro_P;     // dimension of the kind's read-outs (2: the planar grid / planar balls, 3: the 3-D field / balls); 0: no read-out
+  int ro_cls;   // READOUT_*
+  int lead;     // leading coordinates of the slice that the kind's point psi reads (the pose, the joint angles); 0: not a leading slice
 };
 
 constexpr PsiKindRow PSI_KINDS[KIND_COUNT] = {
-  {KIND_RANGE_1D, PSI_RAW, M_NONE, NEED_FIXED, 5, D_ONE, 0, "RANGE_1D needs d == 1"},
-  {KIND_QUAD_PRIOR, PSI_SUMSQ | PSI_CLOSED, M_HALF_D, NEED_QUAD, 0, D_EVEN, 0, "QUAD_PRIOR needs even d"},
-  {KIND_FIXED_PRIOR, PSI_SUMSQ | PSI_CLOSED, M_D, NEED_MEAN_QUAD, 0, D_ANY, 0, nullptr},
-  {KIND_HOST_CALLBACK, PSI_NO_DEVICE, M_NONE, NEED_FIXED, 0, D_ANY, 0, nullptr},
-  {KIND_HINGE_SDF_2D, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_FIXED, 3, D_MIN, 2, "HINGE_SDF_2D needs d >= 2"},
-  {KIND_HINGE_SDF_2D_BODY, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE, M_NONE, NEED_FIXED, 6, D_MIN, 3, "HINGE_SDF_2D_BODY needs d >= 3"},
-  {KIND_HINGE_SDF_3D, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_FIXED, 3, D_MIN, 3, "HINGE_SDF_3D needs d >= 3"},
-  {KIND_HINGE_SDF_3D_ARM, PSI_RAW | PSI_SDF_3D | PSI_ARM | PSI_CLEARANCE, M_NONE, NEED_FIXED, 2, D_ANY, 0, nullptr},
-  {KIND_HINGE_SDF_2D_SEG, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_SEG, 2, D_ANY, 0, nullptr},
-  {KIND_HINGE_SDF_3D_SEG, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_SEG, 3, D_ANY, 0, nullptr},
-  {KIND_HINGE_BOX, PSI_RAW | PSI_CLEARANCE | PSI_CLOSED | PSI_CLOSED_DEFAULT, M_NONE, NEED_BOX, 0, D_ANY, 0, nullptr},
-  {KIND_HINGE_HALFSPACE, PSI_RAW | PSI_CLEARANCE | PSI_CLOSED | PSI_CLOSED_DEFAULT, M_NONE, NEED_HALFSPACE, 0, D_ANY, 0, nullptr},
-  {KIND_HOLE, 0, M_NONE, NEED_FIXED, 0, D_ANY, 0, nullptr},
-  {KIND_HINGE_BALLS_2D, PSI_RAW | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_BALLS, 2, D_ANY, 0, nullptr},
-  {KIND_HINGE_BALLS_3D, PSI_RAW | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_BALLS, 3, D_ANY, 0, nullptr},
+  {KIND_RANGE_1D, PSI_RAW, M_NONE, NEED_FIXED, 5, D_ONE, 0, "RANGE_1D needs d == 1", 0, READOUT_NONE, 1},
+  {KIND_QUAD_PRIOR, PSI_SUMSQ | PSI_CLOSED, M_HALF_D, NEED_QUAD, 0, D_EVEN, 0, "QUAD_PRIOR needs even d", 0, READOUT_NONE, 0},
+  {KIND_FIXED_PRIOR, PSI_SUMSQ | PSI_CLOSED, M_D, NEED_MEAN_QUAD, 0, D_ANY, 0, nullptr, 0, READOUT_NONE, 0},
+  {KIND_HOST_CALLBACK, PSI_NO_DEVICE, M_NONE, NEED_FIXED, 0, D_ANY, 0, nullptr, 0, READOUT_NONE, 0},
+  {KIND_HINGE_SDF_2D, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_FIXED, 3, D_MIN, 2, "HINGE_SDF_2D needs d >= 2", 2, READOUT_LEAD, 2},
+  {KIND_HINGE_SDF_2D_BODY, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE, M_NONE, NEED_FIXED, 6, D_MIN, 3, "HINGE_SDF_2D_BODY needs d >= 3", 0, READOUT_NONE, 3},
+  {KIND_HINGE_SDF_3D, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_FIXED, 3, D_MIN, 3, "HINGE_SDF_3D needs d >= 3", 3, READOUT_LEAD, 3},
+  {KIND_HINGE_SDF_3D_ARM, PSI_RAW | PSI_SDF_3D | PSI_ARM | PSI_CLEARANCE, M_NONE, NEED_FIXED, 2, D_ANY, 0, nullptr, 0, READOUT_NONE, 7},
+  {KIND_HINGE_SDF_2D_SEG, PSI_RAW | PSI_SDF_2D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_SEG, 0, D_ANY, 0, nullptr, 2, READOUT_SEG, 0},
+  {KIND_HINGE_SDF_3D_SEG, PSI_RAW | PSI_SDF_3D | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_SEG, 0, D_ANY, 0, nullptr, 3, READOUT_SEG, 0},
+  {KIND_HINGE_BOX, PSI_RAW | PSI_CLEARANCE | PSI_CLOSED | PSI_CLOSED_DEFAULT, M_NONE, NEED_BOX, 0, D_ANY, 0, nullptr, 0, READOUT_NONE, 0},
+  {KIND_HINGE_HALFSPACE, PSI_RAW | PSI_CLEARANCE | PSI_CLOSED | PSI_CLOSED_DEFAULT, M_NONE, NEED_HALFSPACE, 0, D_ANY, 0, nullptr, 0, READOUT_NONE, 0},
+  {KIND_HOLE, 0, M_NONE, NEED_FIXED, 0, D_ANY, 0, nullptr, 0, READOUT_NONE, 0},
+  {KIND_HINGE_BALLS_2D, PSI_RAW | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_BALLS, 0, D_ANY, 0, nullptr, 2, READOUT_BALLS, 0},
+  {KIND_HINGE_BALLS_3D, PSI_RAW | PSI_CLEARANCE | PSI_READOUT, M_NONE, NEED_BALLS, 0, D_ANY, 0, nullptr, 3, READOUT_BALLS, 0},
 };
 constexpr bool psi_kind_known(int kind) { return kind >= 0 && kind < KIND_COUNT && kind != KIND_HOLE; }
 
@@ -110,17 +112,21 @@ constexpr unsigned psi_kind_mask(unsigned flags) {
 // Does `kind` have (one of) FLAGS?  The table folds into one word at compile time, so a kernel pays a shift and a test
 // (sample_cost_kernel asks per block); false for a number that is no kind.
 template <unsigned FLAGS>
-GVI_KIND_HD constexpr bool psi_kind_is(int kind) {
+GVI_HD constexpr bool psi_kind_is(int kind) {
   constexpr unsigned mask = psi_kind_mask(FLAGS);
   return kind >= 0 && kind < KIND_COUNT && ((mask >> kind) & 1u) != 0;
 }
 
 // P of a PSI_READOUT kind: the dimension of its read-outs (2: the planar grid / planar balls, 3: the 3-D field / balls); 0 for
 // every other kind
-GVI_KIND_HD constexpr int psi_kind_readout_P(int kind) {
-  if (!psi_kind_is<PSI_READOUT>(kind)) return 0;
-  return kind == KIND_HINGE_SDF_2D || kind == KIND_HINGE_SDF_2D_SEG || kind == KIND_HINGE_BALLS_2D ? 2 : 3;
-}
+GVI_HD constexpr int psi_kind_readout_P(int kind) { return psi_kind_known(kind) ? PSI_KINDS[kind].ro_P : 0; }
+// the leading coordinates of the slice that the kind's point psi reads (RANGE_1D, the hinges on a pose, the arm); 0 for every other kind
+GVI_HD constexpr int psi_kind_lead(int kind) { return psi_kind_known(kind) ? PSI_KINDS[kind].lead : 0; }
+
+// doubles of one check point in a factor's block (SEG [W_j | c_j], BALLS [W_j | c_j | tau_j]; LEAD has none: its ONE read-out is the
+// first P coordinates of the slice) and the check points of a factor whose set has seg_J of them; ReadoutView reads a block with these
+constexpr int readout_stride(int cls, int P, int d) { return cls == READOUT_BALLS ? P * (d + 1) + 1 : P * (d + 1); }
+constexpr int readout_check_points(int cls, int seg_J) { return cls == READOUT_LEAD ? 1 : seg_J; }
 
 // Layout of a set of `kind` on factors of dimension d whose parameter blocks are params_per_factor doubles apart: operand
 // rows m, check points / rows per factor J (0 for the kinds without), doubles `need` of a block.  GVI_ERR_ARG and the text
@@ -136,7 +142,7 @@ inline gvi_status psi_kind_layout(int kind, int d, int64_t params_per_factor, in
     case NEED_QUAD: *need = 2 * (int64_t)*m * *m; break;
     case NEED_MEAN_QUAD: *need = d + (int64_t)d * d; break;
     case NEED_SEG: {
-      const int64_t per = (int64_t)r.arg * (d + 1), body = params_per_factor - 3;
+      const int64_t per = readout_stride(r.ro_cls, r.ro_P, d), body = params_per_factor - 3;
       if (body < per || body % per != 0 || body / per > SEG_MAX_J) {
         *msg = "HINGE_SDF_*_SEG needs params_per_factor = 3 + J P (d + 1) with 1 <= J <= 8 check points "
                "(P = 2 for _2D_SEG, 3 for _3D_SEG)";
@@ -161,7 +167,7 @@ inline gvi_status psi_kind_layout(int kind, int d, int64_t params_per_factor, in
       break;
     }
     case NEED_BALLS: {
-      const int64_t per = (int64_t)r.arg * (d + 1) + 1, body = params_per_factor - 3 - BALLS_MAX_M * (2 * (int64_t)r.arg + 1);
+      const int64_t per = readout_stride(r.ro_cls, r.ro_P, d), body = params_per_factor - 3 - BALLS_MAX_M * (2 * (int64_t)r.ro_P + 1);
       if (body < per || body % per != 0 || body / per > SEG_MAX_J) {
         *msg = "HINGE_BALLS_* needs params_per_factor = 3 + J (P (d + 1) + 1) + 8 (2 P + 1) with 1 <= J <= 8 check points "
                "(P = 2 for _2D, 3 for _3D)";
@@ -216,8 +222,8 @@ inline gvi_status psi_kind_check_params(int kind, int d, int J, int64_t params_p
     }
   }
   if (need == NEED_BALLS) {
-    const int P = PSI_KINDS[kind].arg;
-    const int64_t per = (int64_t)P * (d + 1) + 1, slot = 2 * (int64_t)P + 1;
+    const int P = PSI_KINDS[kind].ro_P;
+    const int64_t per = readout_stride(READOUT_BALLS, P, d), slot = 2 * (int64_t)P + 1;
     for (int64_t k = 0; k < K; ++k) {
       const double* B = params + k * params_per_factor;
       for (int64_t e = 0; e < params_per_factor; ++e)

@@ -13,19 +13,12 @@
 //   E[psi] = sum_j e0_j     E[z psi] = sum_j Gam_j^T h_j     E[z z^T psi] = E[psi] I + sum_j Gam_j^T H_j Gam_j.
 // The tensor rule depends on the root of C_j, so L_j is exactly the Cholesky factor; it does not depend on the root S of Sigma.
 // Every product that is added goes through fma explicitly, so the host build and the device build round alike.
+// Where W_j, c_j and tau_j sit in a block, and the entries of G_j and g_j (readout_G_entry / readout_g_entry): readout_view.hpp.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "balls_psi.hpp"
-
-#if defined(__HIPCC__)
-#define GVI_RO_HD __host__ __device__ __forceinline__
-#define GVI_RO_UNROLL _Pragma("unroll")     // P-long loops: the P-long arrays stay in registers
-#else
-#define GVI_RO_HD inline
-#define GVI_RO_UNROLL
-#endif
 
 namespace gvi {
 
@@ -43,21 +36,6 @@ constexpr bool readout_order_ok(int order, int P) {
   return order >= 2 && order <= READOUT_MAX_ORDER && readout_points(order, P) <= READOUT_MAX_POINTS;
 }
 
-// entry (r, c) of G = W S, and g_r = (W mu + c)_r in the association of the *_points walks (start from c_r, ascending i).
-// W == nullptr: the read-out is the first P coordinates of the slice (HINGE_SDF_2D / _3D), c = 0.
-GVI_RO_HD double readout_G_entry(const double* W, const double* S, int d, int r, int c) {
-  if (!W) return S[r * d + c];
-  double v = 0.0;
-  for (int i = 0; i < d; ++i) v = fma(W[r * d + i], S[i * d + c], v);
-  return v;
-}
-GVI_RO_HD double readout_g_entry(const double* W, const double* cvec, const double* mu, int d, int r) {
-  if (!W) return mu[r];
-  double v = cvec[r];
-  for (int i = 0; i < d; ++i) v = fma(W[r * d + i], mu[i], v);
-  return v;
-}
-
 // The lower Cholesky factor of the P x P matrix C (only its lower triangle is read) under the semidefinite rule, per column k:
 //   pivot p = C_kk - sum_{i<k} L_ki^2, thr = 64 2^-52 C_kk;
 //   |p| <= thr: coordinate k is DROPPED -- its column of L is zero and its rule is the single node 0 with weight 1;
@@ -70,17 +48,17 @@ struct ReadoutChol {
   int nkept;
 };
 template <int P>
-GVI_RO_HD ReadoutChol<P> readout_chol(const double* C) {
+GVI_HD_INLINE ReadoutChol<P> readout_chol(const double* C) {
   ReadoutChol<P> o;
   o.ok = true;
   o.nkept = 0;
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int e = 0; e < P * P; ++e) o.L[e] = 0.0;
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int k = 0; k < P; ++k) {
     const double ckk = C[k * P + k];
     double p = ckk;
-  GVI_RO_UNROLL
+  GVI_UNROLL
     for (int i = 0; i < k; ++i) p = fma(-o.L[k * P + i], o.L[k * P + i], p);
     const double thr = 64.0 * 0x1p-52 * ckk;
     if (isnan(p) || p < -thr || ckk < 0.0) o.ok = false;
@@ -89,10 +67,10 @@ GVI_RO_HD ReadoutChol<P> readout_chol(const double* C) {
       ++o.nkept;
       const double piv = sqrt(p);
       o.L[k * P + k] = piv;
-  GVI_RO_UNROLL
+  GVI_UNROLL
       for (int r = k + 1; r < P; ++r) {
         double v = C[r * P + k];
-  GVI_RO_UNROLL
+  GVI_UNROLL
         for (int i = 0; i < k; ++i) v = fma(-o.L[r * P + i], o.L[k * P + i], v);
         o.L[r * P + k] = v / piv;
       }
@@ -103,12 +81,12 @@ GVI_RO_HD ReadoutChol<P> readout_chol(const double* C) {
 
 // Column c of Gam by forward substitution, in place: col[k * stride] holds G_kc on entry and Gam_kc on return.
 template <int P>
-GVI_RO_HD void readout_gamma_col(const ReadoutChol<P>& ch, double* col, int stride) {
+GVI_HD_INLINE void readout_gamma_col(const ReadoutChol<P>& ch, double* col, int stride) {
   double gm[P];
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int k = 0; k < P; ++k) {
     double v = col[k * stride];
-  GVI_RO_UNROLL
+  GVI_UNROLL
     for (int i = 0; i < k; ++i) v = fma(-ch.L[k * P + i], gm[i], v);
     gm[k] = ch.keep[k] ? v / ch.L[k * P + k] : 0.0;
     col[k * stride] = gm[k];
@@ -117,9 +95,9 @@ GVI_RO_HD void readout_gamma_col(const ReadoutChol<P>& ch, double* col, int stri
 
 // nodes of the tensor rule of one check point: order^nkept
 template <int P>
-GVI_RO_HD int readout_node_count(const ReadoutChol<P>& ch, int order) {
+GVI_HD_INLINE int readout_node_count(const ReadoutChol<P>& ch, int order) {
   int n = 1;
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int k = 0; k < P; ++k)
     if (ch.keep[k]) n *= order;
   return n;
@@ -128,9 +106,9 @@ GVI_RO_HD int readout_node_count(const ReadoutChol<P>& ch, int order) {
 // Node idx of the tensor rule: the kept coordinates are the digits of idx in base `order`, the first kept coordinate the lowest
 // digit.  xi [P] (0 on a dropped coordinate), the weight is returned.  nodes / weights: the 1-D rule [order] each.
 template <int P>
-GVI_RO_HD double readout_node(const ReadoutChol<P>& ch, int order, const double* nodes, const double* weights, int idx, double* xi) {
+GVI_HD_INLINE double readout_node(const ReadoutChol<P>& ch, int order, const double* nodes, const double* weights, int idx, double* xi) {
   double om = 1.0;
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int k = 0; k < P; ++k) {
     if (ch.keep[k]) {
       const int a = idx % order;
@@ -146,11 +124,11 @@ GVI_RO_HD double readout_node(const ReadoutChol<P>& ch, int order, const double*
 
 // q = g + L xi
 template <int P>
-GVI_RO_HD void readout_point(const ReadoutChol<P>& ch, const double* g, const double* xi, double* q) {
-  GVI_RO_UNROLL
+GVI_HD_INLINE void readout_point(const ReadoutChol<P>& ch, const double* g, const double* xi, double* q) {
+  GVI_UNROLL
   for (int r = 0; r < P; ++r) {
     double v = g[r];
-  GVI_RO_UNROLL
+  GVI_UNROLL
     for (int k = 0; k <= r; ++k) v = fma(ch.L[r * P + k], xi[k], v);
     q[r] = v;
   }
@@ -164,33 +142,33 @@ struct ReadoutSums {
   double H[P * (P + 1) / 2];
 };
 template <int P>
-GVI_RO_HD void readout_zero(ReadoutSums<P>& s) {
+GVI_HD_INLINE void readout_zero(ReadoutSums<P>& s) {
   s.e0 = 0.0;
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int k = 0; k < P; ++k) s.h[k] = 0.0;
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int e = 0; e < P * (P + 1) / 2; ++e) s.H[e] = 0.0;
 }
 template <int P>
-GVI_RO_HD void readout_accumulate(ReadoutSums<P>& s, double om, const double* xi, double f) {
+GVI_HD_INLINE void readout_accumulate(ReadoutSums<P>& s, double om, const double* xi, double f) {
   const double wf = om * f;
   s.e0 += wf;
   int e = 0;
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int k = 0; k < P; ++k) {
     s.h[k] = fma(wf, xi[k], s.h[k]);
-  GVI_RO_UNROLL
+  GVI_UNROLL
     for (int l = k; l < P; ++l, ++e) s.H[e] = fma(wf, fma(xi[k], xi[l], k == l ? -1.0 : 0.0), s.H[e]);
   }
 }
 // h -> hs [P], H -> Hs [P x P] symmetric; zero on the dropped coordinates (H is defined on the kept ones)
 template <int P>
-GVI_RO_HD void readout_store_sums(const ReadoutChol<P>& ch, const ReadoutSums<P>& s, double* hs, double* Hs) {
+GVI_HD_INLINE void readout_store_sums(const ReadoutChol<P>& ch, const ReadoutSums<P>& s, double* hs, double* Hs) {
   int e = 0;
-  GVI_RO_UNROLL
+  GVI_UNROLL
   for (int k = 0; k < P; ++k) {
     hs[k] = ch.keep[k] ? s.h[k] : 0.0;
-  GVI_RO_UNROLL
+  GVI_UNROLL
     for (int l = k; l < P; ++l, ++e) {
       const double v = ch.keep[k] && ch.keep[l] ? s.H[e] : 0.0;
       Hs[k * P + l] = v;
@@ -200,10 +178,10 @@ GVI_RO_HD void readout_store_sums(const ReadoutChol<P>& ch, const ReadoutSums<P>
 }
 
 // f at a read-out point for the analytic balls: the hinge of psi_hinge_balls on the distance of hinge_balls_points.
-// p: the factor's block, balls = p + 3 + J balls_point_stride(P, d), tau the time of the check point.
+// p: the factor's block, balls its slots and tau the time of the check point (ReadoutView::balls, tau).
 template <int P>
-GVI_RO_HD double readout_f_balls(const double* p, const double* balls, double tau, const double* q) {
-  return balls_hinge_sq(balls_signed_distance<P>(balls, tau, q), p[1] + p[2], p[0]);
+GVI_HD_INLINE double readout_f_balls(const double* p, const double* balls, double tau, const double* q) {
+  return hinge_sq(balls_signed_distance<P>(balls, tau, q), p[1] + p[2], 1.0, p[0]);
 }
 
 // One check point, the nodes one after the other (a wave of the kernel strides its lanes over them and adds the lanes' sums up):

@@ -37,7 +37,7 @@ template <int M, int SMAX, int WAVES, int D0, int D1> struct FusedInst {};
 struct ClosedSumsq {};
 struct ClosedBox {};
 struct ClosedHalfspace {};
-template <int P, int CLS> struct ReadoutInst {};   // CLS: how the kind lays its read-outs out (0 the leading coordinates, 1 _SEG blocks, 2 BALLS blocks)
+template <int P, int CLS> struct ReadoutInst {};   // CLS: READOUT_LEAD / _SEG / _BALLS, how the kind lays its read-outs out (psi_kinds.hpp)
 constexpr auto any_instance = [](auto) {};
 template <class F, class Inst> bool hit(F& f, Inst inst) { f(inst); return true; }
 
@@ -197,12 +197,12 @@ bool with_closed_instance(int kind, F&& f) {
 template <class F>
 bool with_readout_instance(int kind, F&& f) {
   switch (kind) {
-    case KIND_HINGE_SDF_2D: return hit(f, ReadoutInst<2, 0>{});
-    case KIND_HINGE_SDF_3D: return hit(f, ReadoutInst<3, 0>{});
-    case KIND_HINGE_SDF_2D_SEG: return hit(f, ReadoutInst<2, 1>{});
-    case KIND_HINGE_SDF_3D_SEG: return hit(f, ReadoutInst<3, 1>{});
-    case KIND_HINGE_BALLS_2D: return hit(f, ReadoutInst<2, 2>{});
-    case KIND_HINGE_BALLS_3D: return hit(f, ReadoutInst<3, 2>{});
+    case KIND_HINGE_SDF_2D: return hit(f, ReadoutInst<2, READOUT_LEAD>{});
+    case KIND_HINGE_SDF_3D: return hit(f, ReadoutInst<3, READOUT_LEAD>{});
+    case KIND_HINGE_SDF_2D_SEG: return hit(f, ReadoutInst<2, READOUT_SEG>{});
+    case KIND_HINGE_SDF_3D_SEG: return hit(f, ReadoutInst<3, READOUT_SEG>{});
+    case KIND_HINGE_BALLS_2D: return hit(f, ReadoutInst<2, READOUT_BALLS>{});
+    case KIND_HINGE_BALLS_3D: return hit(f, ReadoutInst<3, READOUT_BALLS>{});
   }
   return false;
 }
@@ -258,7 +258,7 @@ struct RouteFacts {
   bool psi_ext = false;              // the caller supplies psi at the sigma points (gvi_moments_from_psi)
   bool has_arm = false, has_sdf = false;
   int arm_ndof = 0, seg_J = 0;
-  int opsi_rows = 0;                  // leading coordinates the kind's register psi reads (orbit_psi_rows, kernels_orbit_psi.hpp)
+  int opsi_rows = 0;                  // leading coordinates the kind's register psi reads: psi_kind_lead (psi_kinds.hpp)
   // of its table
   int64_t Np = 0, Nmp = 0;
   int p = 0;

@@ -39,9 +39,22 @@ def sym_root(Sigma):
 
 
 # ---- 1. the header on the CPU ----
+LEAD, SEG, BALLS = 0, 1, 2                   # READOUT_* of psi_kinds.hpp
+KIND_OF = {(LEAD, 2): syn.PSI_HINGE_SDF_2D, (LEAD, 3): syn.PSI_HINGE_SDF_3D, (SEG, 2): syn.PSI_HINGE_SDF_2D_SEG, (SEG, 3): syn.PSI_HINGE_SDF_3D_SEG,
+           (BALLS, 2): syn.PSI_HINGE_BALLS_2D, (BALLS, 3): syn.PSI_HINGE_BALLS_3D}
+
+
+def grid_of(P):
+    """a disc / ball of radius 0.7 at the origin on a grid whose cell is a power of two (1 / cell exact)"""
+    if P == 2:
+        return dict(sdf_origin=(-2.0, -2.0), sdf_cell=0.25, sdf_field=syn.circle_sdf((-2.0, -2.0), 0.25, 17, 17, [(0.0, 0.0)], [0.7]))
+    return dict(sdf_origin=(-2.0, -2.0, -2.0), sdf_cell=0.5, sdf_field=syn.sphere_sdf3d((-2.0, -2.0, -2.0), 0.5, 9, 9, 9, [(0.0, 0.0, 0.0)], [0.7]))
+
+
 def stub_cases():
-    """(P, d, J, order, block [1][...], mu [d], Sigma [d][d], tag): random read-outs with the means 0.3 off a ball's rim, then a
-    zero row of W, two parallel rows, and both together."""
+    """(P, d, J, order, block [1][...], mu [d], Sigma [d][d], tag, cls): BALLS blocks with random read-outs whose means are 0.3
+    off a ball's rim, then a zero row of W, two parallel rows, and both together; one LEAD and one SEG case per P on a grid, the
+    means 0.3 off the obstacle's rim."""
     rng = np.random.default_rng(18)
     cases = []
     for P, d, J, order in [(2, 2, 1, 7), (2, 4, 3, 8), (2, 8, 8, 16), (2, 12, 3, 2), (3, 3, 1, 4), (3, 6, 3, 5), (3, 12, 8, 10), (2, 32, 3, 9)]:
@@ -62,29 +75,51 @@ def stub_cases():
             target = (cen[0] + tau[:, None] * vel[0]) + (rad[0] + 0.3) * u
             c = target - W @ mu[0]
             blk = syn.balls_params(rng.uniform(5, 20), 0.2, 0.1, W, c, tau, cen, vel, rad)
-            cases.append((P, d, J, order, blk, mu[0], Sigma[0], tag))
+            cases.append((P, d, J, order, blk, mu[0], Sigma[0], tag, BALLS))
+    rng = np.random.default_rng(1806)                                # the grid classes, after the BALLS cases and on their own stream
+    for P, d, J, order in [(2, 4, 1, 8), (3, 6, 1, 5), (2, 8, 3, 8), (3, 6, 3, 5)]:
+        cls = LEAD if J == 1 else SEG
+        mu, Sigma = syn.random_marginals(rng, 1, d, 0.05)
+        u = rng.normal(size=(J, P))
+        target = (0.7 + 0.3) * u / np.linalg.norm(u, axis=1, keepdims=True)
+        if cls == LEAD:
+            mu[0, :P] = target[0]
+            blk = np.array([[12.0, 0.3, 0.1]])
+        else:
+            W = rng.normal(size=(J, P, d)) / np.sqrt(d) * 2.0
+            blk = syn.segment_params(12.0, 0.3, 0.1, W, target - W @ mu[0])
+        cases.append((P, d, J, order, blk, mu[0], Sigma[0], "random", cls))
     return cases
 
 
 def write_cases(path, cases, which):
     with open(path, "w") as f:
         f.write(f"{len(cases)}\n")
-        for P, d, J, order, blk, mu, Sigma, _ in cases:
+        for P, d, J, order, blk, mu, Sigma, _, cls in cases:
             S = sym_root(Sigma) if which == 0 else np.linalg.cholesky(Sigma)
             if which == 1 and d > 1:
                 assert np.abs(S - S.T).max() > 1e-3                      # a root whose rows and columns differ
             x, w = rr.rule(order)
-            f.write(f"mom {P} {d} {J} {order}\n" + "\n".join(" ".join(float(v).hex() for v in np.ravel(a)) for a in (blk, mu, S, x, w)) + "\n")
+            f.write(f"mom {P} {cls} {d} {J} {order}\n")
+            if cls != BALLS:
+                g = grid_of(P)
+                shape = g["sdf_field"].shape
+                f.write("%d %d %d " % (shape[0], shape[1], shape[2] if P == 3 else 0))
+                f.write(" ".join(float(v).hex() for v in list(g["sdf_origin"]) + [0.0] * (3 - P) + [g["sdf_cell"]]) + "\n")
+                f.write(" ".join(float(v).hex() for v in np.ravel(g["sdf_field"], order="F")) + "\n")     # r + c rows + z rows cols
+            f.write("\n".join(" ".join(float(v).hex() for v in np.ravel(a)) for a in (blk, mu, S, x, w)) + "\n")
 
 
 @pytest.mark.parametrize("flags", [[], SAN], ids=["plain", "sanitized"])
 def test_header_on_cpu(tmp_path, flags):
-    """readout_moments.hpp as a stand-alone host program, run on stub_cases() with the symmetric root of Sigma and with its lower
+    """readout_moments.hpp as a stand-alone host program, run on stub_cases() -- the three read-out classes, the grid classes through
+    the look-ups of psi_point.hpp -- with the symmetric root of Sigma and with its lower
     Cholesky factor (row-major, x = mu + S z): S m1 and S M2 S^T of the two roots agree with each other and with readout_ref to
     1e-12 (max-norm relative), the bound of the half-space program's test; the result depends on Sigma only."""
     exe = compile_stub(tmp_path, "readout_on_cpu", flags)
     cases = stub_cases()
     assert {c[0] for c in cases} == {2, 3} and {c[7] for c in cases} == {"random", "zero_row", "parallel", "zero_and_parallel"}
+    assert {(c[8], c[0]) for c in cases} == set(KIND_OF)                 # every class at every P
     back = {}
     worst = 0.0
     for which in (0, 1):
@@ -94,14 +129,14 @@ def test_header_on_cpu(tmp_path, flags):
         assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout[-2000:] + r.stderr[-4000:]
         lines = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("mom")]
         assert len(lines) == len(cases)
-        for ci, (P, d, J, order, blk, mu, Sigma, tag) in enumerate(cases):
+        for ci, (P, d, J, order, blk, mu, Sigma, tag, cls) in enumerate(cases):
             t = lines[ci]
             assert int(t[1]) == ci and int(t[2]) == 1
             v = np.array([float.fromhex(s) for s in t[3:]])
             S = sym_root(Sigma) if which == 0 else np.linalg.cholesky(Sigma)
             m0, m1, M2 = v[0], v[1:1 + d], v[1 + d:].reshape(d, d)
             got = dict(E_phi=m0, E_xmuphi=S @ m1, E_xxphi=S @ M2 @ S.T)
-            spec = dict(kind={2: syn.PSI_HINGE_BALLS_2D, 3: syn.PSI_HINGE_BALLS_3D}[P], d=d, params=blk, temperature=np.ones(1))
+            spec = dict(kind=KIND_OF[(cls, P)], d=d, params=blk, temperature=np.ones(1), **({} if cls == BALLS else grid_of(P)))
             diag = []
             ref = rr.spec_moments(spec, mu[None], Sigma[None], order, diag=diag)
             keeps = {tuple(e["keep"]) for e in diag[0]}
