@@ -91,7 +91,8 @@ inline hipError_t chain_launch_t(const ChainPlan& pl, ChainArgs a0, ChainArgs a1
   const int npass = (int)pl.passes.size();
   // N = 6, per pass: the two-row form (the kernels' default bodies) where some level is crowded -- more eliminations at the pass's
   // first level than two per SIMD, the levels on which it puts two nodes into one wave -- and option chain_pair is on; else the
-  // v_readlane kernels (a plan-time decision: without a crowded level the two-row form is the slower one)
+  // v_readlane kernels (a plan-time decision: without a crowded level the two-row form is the slower one -- also with its lane
+  // records, by ~260 stamped cycles per one-node level where it was ~740; profiles/chain_index_work.txt section 2)
   const bool pair_on = N == 6 && a0.pair != 0;
   auto rowb = [&](const ChainPass& ps) { return pair_on && (ps.S >> 1) > pl.threads / 128; };
   // the top pass carries the backward workgroups of the last segmented pass when there is one and its LDS fits

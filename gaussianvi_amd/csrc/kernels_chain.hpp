@@ -46,6 +46,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "chain_lane_record.hpp"
 #include "device_common.hpp"
 #include "dpp_rowb.hpp"
 #include "kernels_bt.hpp"
@@ -374,7 +375,18 @@ struct ElimIO {
   int oZero;           // N zeros
   // top pass: factors stay in LDS, row-major
   int oEl, oGAl, oGBl, ovl;
+  int oRec;            // two-row form: the pass's lane records, then an identity and a zero block of N x N (chain_lane_record.hpp)
 };
+
+// ---- the two-row form (ROWB, N = 6): a lane's column addresses from its record (chain_lane_record.hpp) ----
+// Not in the v_readlane form: its roles are contiguous lane ranges, cheap to form, and the record's LDS round trip in front of
+// the column loads cost what it saved (chain_bench, chain_pair = 0: 48.5 -> 49.0 us)
+__device__ __forceinline__ double& lds_b(double* sm, const unsigned byte_off) { return *(double*)((char*)sm + byte_off); }
+__device__ __forceinline__ LaneRec lane_rec_load(const double* sm, const int oRec, const int idx) {
+  typedef unsigned u4 __attribute__((ext_vector_type(4)));
+  const u4 v = *(const u4*)(sm + oRec + 2 * idx);                    // one ds_read_b128
+  return LaneRec{v.x, v.y, v.z, v.w};
+}
 
 // ---- Gauss-Jordan with row-broadcast pivots (eliminate, ROWB): steps P .. N - 1 ----
 // The arithmetic of the v_readlane form below: fma(-ap[r], f, col[r]) and col[r] += bcast_P(col[r]) * (-f) are the same bits.
@@ -439,23 +451,34 @@ __device__ __forceinline__ void gj_rowb(double (&col)[N], double& mp, int& es, i
 //   solve           row 0: D(6) | Ua^T(6) | Ub[0..3]     row 1: D'(6) | Ub[4..5] | y
 template <bool PIVOT, bool HAS_E, bool HAS_Y, bool TOP, int N, bool ROWB = false>
 __device__ __forceinline__ void eliminate(double* sm, const int lane, const ElimIO io, double* gE, double* gGA, double* gGB,
-                                          double* gv, double* gNU, LogPiv& lp) {
+                                          double* gv, double* gNU, LogPiv& lp, [[maybe_unused]] const LaneRec rec = LaneRec{}) {
+  // rec (two-row form): the lane's record, requested by the caller in front of the scalar work that forms io
   using C = Cols<HAS_E, HAS_Y, N>;
   const bool has_a = io.oUa >= 0, has_b = io.oUb >= 0;              // wave-uniform
   bool isD, isE, isA, isB, isY;
   int cc;                                                           // column inside its group
+  [[maybe_unused]] unsigned ccN8 = 0, cc8 = 0, so8 = 0;             // ROWB: 8 N cc, 8 cc, the factor store's row stride (bytes)
+  double col[N];
   if constexpr (ROWB) {
-    constexpr int G0 = 16 - 2 * N;                                  // columns of the split group (Ua^T / Ub) that fit row 0
-    static_assert(!ROWB || (G0 > 0 && G0 <= N && 2 * N - G0 + (HAS_E ? N : 1) <= 16), "two-row layout");
-    constexpr int l1 = 16 + N, l2 = l1 + N - G0;                    // row 1: rest of the split group, then Ub / y
-    const bool split0 = lane >= 16 - G0 && lane < 16, split1 = lane >= l1 && lane < l2;
-    isD = lane < N || (lane >= 16 && lane < l1);
-    isE = HAS_E && lane >= N && lane < 2 * N;
-    isA = HAS_E ? (split0 || split1) : (lane >= N && lane < 2 * N);
-    isB = HAS_E ? (lane >= l2 && lane < l2 + N) : (split0 || split1);
-    isY = HAS_Y && lane == l2;
-    const int cs = split0 ? lane - (16 - G0) : lane - l1 + G0;      // column of a lane of the split group
-    cc = isD ? (lane < N ? lane : lane - 16) : (isE ? lane - N : (isA ? (HAS_E ? cs : lane - N) : (isB ? (HAS_E ? lane - l2 : cs) : 0)));
+    // role, column and offsets come from the lane's record; a column of I, of a missing neighbour or of a lane outside the
+    // tile is LOADED from the identity / zero block behind the table: 1 + 0 and 0 + 0 are the values the selects produced
+    const unsigned role = rec_role(rec);
+    isD = role == ROLE_D; isE = HAS_E && role == ROLE_E; isA = role == ROLE_A; isB = role == ROLE_B; isY = HAS_Y && role == ROLE_Y;
+    cc = (int)rec_cc(rec);
+    ccN8 = rec_ccN8(rec); cc8 = rec_cc8(rec); so8 = rec_so(rec);
+    const int oI = io.oRec + 128, oZ = oI + N * N;
+    const int bA = has_a ? io.oUa : oZ, bB = has_b ? io.oUb : oZ;   // scalar selects
+    int b0 = oZ, b1 = oZ;
+    b0 = isD ? io.oD : b0; b1 = isD ? io.oR : b1;
+    if (HAS_E) b0 = isE ? oI : b0;
+    b0 = isA ? bA : b0;
+    b0 = isB ? bB : b0;
+    if (HAS_Y) { b0 = isY ? io.oy : b0; b1 = isY ? io.oyR : b1; }
+    const unsigned a0 = 8u * b0 + rec_off0(rec), a1 = 8u * b1 + rec_off1(rec), s0 = rec_s0(rec);
+    CHAIN_STAMP(TOP && HAS_E);
+#pragma unroll
+    for (int r = 0; r < N; ++r) col[r] = lds_b(sm, a0 + r * s0) + lds_b(sm, a1 + 8u * r);
+    CHAIN_STAMP(TOP && HAS_E);
   } else {
     isD = lane < N;
     isE = HAS_E && lane >= C::cE && lane < C::cA;
@@ -463,23 +486,22 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
     isB = lane >= C::cB && lane < C::cY;
     isY = HAS_Y && lane == C::cY;
     cc = isD ? lane : (isE ? lane - C::cE : (isA ? lane - C::cA : (isB ? lane - C::cB : 0)));
+    // ---- this lane's column: col[r] = sm[p0 + r s0] + sm[p1 + r] ----
+    int p0 = io.oZero, s0 = 0, p1 = io.oZero;
+    if (isD) { p0 = io.oD + cc * N; s0 = 1; p1 = io.oR + cc * N; }                     // symmetric: row = column
+    else if (isA) { if (has_a) { p0 = io.oUa + cc; s0 = N; } }                        // column c of Ua^T = UaT[:, c]
+    else if (isB) { if (has_b) { p0 = io.oUb + cc * N; s0 = 1; } }                    // column c of Ub  = UbT[c, :]
+    else if (isY) { p0 = io.oy; s0 = 1; p1 = io.oyR; }
+    CHAIN_STAMP(TOP && HAS_E);
+#pragma unroll
+    for (int r = 0; r < N; ++r) col[r] = sm[p0 + r * s0] + sm[p1 + r];
+    CHAIN_STAMP(TOP && HAS_E);
+    if (HAS_E) {
+#pragma unroll
+      for (int r = 0; r < N; ++r) col[r] = isE ? (r == cc ? 1.0 : 0.0) : col[r];
+    }
   }
   const bool isF = ROWB ? (isE || isA || isB || isY) : (lane >= N && lane < C::NC);   // lanes that hold a factor column (E / GA / GB / v)
-  // ---- this lane's column: col[r] = sm[p0 + r s0] + sm[p1 + r] ----
-  int p0 = io.oZero, s0 = 0, p1 = io.oZero;
-  if (isD) { p0 = io.oD + cc * N; s0 = 1; p1 = io.oR + cc * N; }                       // symmetric: row = column
-  else if (isA) { if (has_a) { p0 = io.oUa + cc; s0 = N; } }                          // column c of Ua^T = UaT[:, c]
-  else if (isB) { if (has_b) { p0 = io.oUb + cc * N; s0 = 1; } }                      // column c of Ub  = UbT[c, :]
-  else if (isY) { p0 = io.oy; s0 = 1; p1 = io.oyR; }
-  CHAIN_STAMP(TOP && HAS_E);
-  double col[N];
-#pragma unroll
-  for (int r = 0; r < N; ++r) col[r] = sm[p0 + r * s0] + sm[p1 + r];
-  CHAIN_STAMP(TOP && HAS_E);
-  if (HAS_E) {
-#pragma unroll
-    for (int r = 0; r < N; ++r) col[r] = isE ? (r == cc ? 1.0 : 0.0) : col[r];
-  }
   // The rows of Ua the Schur products will read are known now: request them BEFORE the Gauss-Jordan (which covers their
   // latency) where the register budget allows (N <= 6 at 128 registers)
   constexpr int RB = chain_threads(N) == 1024 ? 128 : 256;              // register budget per lane
@@ -552,15 +574,27 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
   // ---- factors: E / GA / GB / v of this node ----
   if (TOP) {                                               // kept in LDS, row-major, for the backward recursion of this pass
     if (isF) {
-      const int o = isE ? io.oEl + cc : (isA ? io.oGAl + cc : (isB ? io.oGBl + cc : io.ovl));
-      const int so = isY ? 1 : N;
+      if constexpr (ROWB) {
+        const int bf = isE ? io.oEl : (isA ? io.oGAl : (isB ? io.oGBl : io.ovl));
+        const unsigned o = 8u * bf + cc8;
 #pragma unroll
-      for (int r = 0; r < N; ++r) sm[o + r * so] = col[r];
+        for (int r = 0; r < N; ++r) lds_b(sm, o + r * so8) = col[r];
+      } else {
+        const int o = isE ? io.oEl + cc : (isA ? io.oGAl + cc : (isB ? io.oGBl + cc : io.ovl));
+        const int so = isY ? 1 : N;
+#pragma unroll
+        for (int r = 0; r < N; ++r) sm[o + r * so] = col[r];
+      }
     }
   } else {                                                 // to the workspace (column-contiguous = transposed), read by pass C
     if (isF) {
-      double* g = isE ? gE + cc * N : (isA ? gGA + cc * N : (isB ? gGB + cc * N : gv));
-      st_row<N>(g, col);
+      if constexpr (ROWB) {
+        double* g = isE ? gE : (isA ? gGA : (isB ? gGB : gv));
+        st_row<N>((double*)((char*)g + ccN8), col);
+      } else {
+        double* g = isE ? gE + cc * N : (isA ? gGA + cc * N : (isB ? gGB + cc * N : gv));
+        st_row<N>(g, col);
+      }
     }
   }
   CHAIN_STAMP(TOP && HAS_E);
@@ -585,13 +619,18 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
   }
   if (has_a) {
     if (isA || isY) {                                      // D_a -= Ua GA (column c) ; y_a -= Ua v
-      double* o = sm + (isY ? io.oyRa : io.oRa + cc * N);
+      double* o = ROWB ? &lds_b(sm, 8u * (isY ? io.oyRa : io.oRa) + ccN8) : sm + (isY ? io.oyRa : io.oRa + cc * N);
 #pragma unroll
       for (int r = 0; r < N; ++r) lds_add(o + r, t[r]);
     }
     if (has_b && isB) {                                    // A[a,b] = -Ua GB, column c contiguous = transposed layout
-      st_row<N>(sm + io.oNU + cc * N, t);
-      if (gNU) st_row<N>(gNU + cc * N, t);
+      if constexpr (ROWB) {
+        st_row<N>(&lds_b(sm, 8u * io.oNU + ccN8), t);
+        if (gNU) st_row<N>((double*)((char*)gNU + ccN8), t);
+      } else {
+        st_row<N>(sm + io.oNU + cc * N, t);
+        if (gNU) st_row<N>(gNU + cc * N, t);
+      }
     }
   }
   if (has_b) {
@@ -623,7 +662,7 @@ __device__ __forceinline__ void eliminate(double* sm, const int lane, const Elim
       s[r] = acc;
     }
     if (isB || isY) {                                      // D_b -= Ub^T GB (column c) ; y_b -= Ub^T v
-      double* o = sm + (isY ? io.oyb : io.oDb + cc * N);
+      double* o = ROWB ? &lds_b(sm, 8u * (isY ? io.oyb : io.oDb) + ccN8) : sm + (isY ? io.oyb : io.oDb + cc * N);
 #pragma unroll
       for (int r = 0; r < N; ++r) lds_add(o + r, s[r]);
     }
@@ -818,7 +857,7 @@ __host__ __device__ constexpr size_t fwd_lds_doubles(int S, bool rowb = false) {
   size_t w = (size_t)2 * (S + 1) * nn + (size_t)2 * S * nn;              // Dl, Rl, Ct, NUt
   if (TOP) w += (size_t)3 * S * nn + (HAS_E ? (size_t)S * nn : 0);       // El, GAl, GBl (+ SRt of the backward recursion)
   if (HAS_Y) w += (size_t)2 * (S + 1) * N + (TOP ? (size_t)(2 * S + 1) * N : 0);   // yl, yRl (+ vl, xl)
-  return w + N + (N & 1) + 128 + (rowb ? 96 : 0);                        // zero block, log-det reduction, eliminate2's log-pivot slots
+  return w + N + (N & 1) + 128 + (rowb ? 96 + lane_record_doubles<N>() : 0);   // zero block, log-det reduction; two-row form: eliminate2's log-pivot slots, lane records
 }
 template <bool HAS_E, int N>
 __host__ __device__ constexpr size_t bwd_lds_doubles(int S) {
@@ -904,6 +943,7 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
   const int oZero = oxl + ((HAS_Y && TOP) ? (S + 1) * N : 0);
   const int oRed = oZero + N + (N & 1);
   [[maybe_unused]] const int oLp2 = oRed + 128;     // N = 6: [2][32 doubles + 32 ints] log-pivots of the nodes of a paired level, by level parity
+  [[maybe_unused]] const int oRec = oRed + 128 + (ROWB ? 96 : 0);   // two-row form: lane records [64][4 words], identity [nn], zeros [nn]
   CHAIN_STAMP(TOP && HAS_E);
   const int cnt = min(S, (T - x0 + st - 1) >> a.level0);    // local nodes that exist (x0 < T for every launched block)
   const int xn = x0 + S * st;
@@ -1067,6 +1107,16 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
   for (int e = tid; e < (S + 1) * nn; e += nthr) sm[oRl + e] = 0.0;
   for (int e = tid; e < (S + 1 - cnt) * nn; e += nthr) sm[oDl + cnt * nn + e] = 0.0;
   if (tid < N + (N & 1)) sm[oZero + tid] = 0.0;
+  if constexpr (ROWB) {                             // what every elimination of this pass reads about its lanes (chain_lane_record.hpp)
+    if (tid < 64) {
+      typedef unsigned u4 __attribute__((ext_vector_type(4)));
+      const LaneRec rc = lane_record<HAS_E, HAS_Y, N>(tid);
+      u4 v;
+      v.x = rc.w0; v.y = rc.w1; v.z = rc.w2; v.w = rc.pad;
+      *(u4*)(sm + oRec + 2 * tid) = v;
+    }
+    for (int e = tid; e < 2 * nn; e += nthr) sm[oRec + 128 + e] = (e < nn && e % (N + 1) == 0) ? 1.0 : 0.0;
+  }
   if (HAS_Y) {
     for (int e = tid; e < (S + 1) * N; e += nthr) {
       const int j = e / N, r = e % N, x = x0 + j * st;
@@ -1143,6 +1193,8 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
       }
     }
     for (int u = wave; u < nel; u += nwaves) {
+      LaneRec rec{};
+      if constexpr (ROWB) { rec = lane_rec_load(sm, oRec, lane); __builtin_amdgcn_sched_barrier(0); }   // (the scalar work below covers its round trip)
       const int j = (2 * u + 1) * h2, x = x0 + j * st;
       const int ja = j - h2, jb = j + h2;
       const bool has_b = (jb < cnt) || (jb == S && ext_right);
@@ -1153,13 +1205,13 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
       io.oRa = oRl + ja * nn; io.oDb = oDl + jb * nn;
       io.oNU = oNU + j * nn;
       io.oy = oyl + j * N; io.oyR = oyR + j * N; io.oyRa = oyR + ja * N; io.oyb = oyl + jb * N;
-      io.oZero = oZero;
+      io.oZero = oZero; io.oRec = oRec;
       io.oEl = oEl + j * nn; io.oGAl = oGAl + j * nn; io.oGBl = oGBl + j * nn; io.ovl = ovl + j * N;
       const size_t gx = (size_t)x * nn;
       // the coupling created at the last level joins this segment's first node and the next one's: the next pass loads it
       double* gNU = (!TOP && lam == a.m - 1 && has_b) ? ws_mat<N>(a, W_NU) + gx : nullptr;
       eliminate<PIVOT, HAS_E, HAS_Y, TOP, N, ROWB>(sm, lane, io, ws_mat<N>(a, W_E) + gx, ws_mat<N>(a, W_GA) + gx, ws_mat<N>(a, W_GB) + gx,
-                                                   ws_vec<N>(a, V_V) + (size_t)x * N, gNU, lp);
+                                                   ws_vec<N>(a, V_V) + (size_t)x * N, gNU, lp, rec);
     }
     lds_barrier();
     CHAIN_STAMP(TOP && HAS_E);
@@ -1186,9 +1238,11 @@ __device__ __forceinline__ void forward_body(const ChainArgs& a, const AsmList& 
     if (wave == 0) {
       ElimIO io;
       io.oD = oDl; io.oR = oRl; io.oUa = -1; io.oUb = -1; io.oRa = 0; io.oDb = 0; io.oNU = 0;
-      io.oy = oyl; io.oyR = oyR; io.oyRa = 0; io.oyb = 0; io.oZero = oZero;
+      io.oy = oyl; io.oyR = oyR; io.oyRa = 0; io.oyb = 0; io.oZero = oZero; io.oRec = oRec;
       io.oEl = oEl; io.oGAl = oGAl; io.oGBl = oGBl; io.ovl = ovl;
-      eliminate<PIVOT, HAS_E, HAS_Y, true, N, ROWB>(sm, lane, io, nullptr, nullptr, nullptr, nullptr, nullptr, lp);
+      LaneRec rec{};
+      if constexpr (ROWB) rec = lane_rec_load(sm, oRec, lane);
+      eliminate<PIVOT, HAS_E, HAS_Y, true, N, ROWB>(sm, lane, io, nullptr, nullptr, nullptr, nullptr, nullptr, lp, rec);
     }
     // ---- 1/2 log det: this pass's waves leave their accumulated pivots in LDS; the LAST wave folds them with the earlier
     // passes' partial products (reduced at the start of this pass, below) and takes the one logarithm -- beside the first
