@@ -4,6 +4,7 @@
 // reads it back with one 128-bit load and adds the wave-uniform bases of its node.  Plain C++ on the host as well
 // (tests/stubs/chain_lane_record_check.cpp restates the expressions the elimination used before and compares every lane).
 #pragma once
+#include "chain_plan.hpp"   // lane_record_doubles: the LDS of the pass's table, identity and zero block
 #include "hd.hpp"
 
 namespace gvi {
@@ -88,10 +89,8 @@ GVI_HD_INLINE LaneRec lane_record(const int lane) {
   return r;
 }
 
-// doubles of LDS behind the arrays of a two-row pass: the table (64 lanes x 16 bytes), an identity block and a zero block of
-// N x N each -- the columns of I, of a missing neighbour's coupling and of a lane outside the tile are LOADED from them like any
-// other column
-template <int N> GVI_HD constexpr int lane_record_doubles() { return 128 + 2 * N * N; }
+// chain_plan.hpp's lane_record_doubles(N) -- the LDS behind the arrays of a two-row pass -- under the block size as a template argument
+template <int N> GVI_HD constexpr int lane_record_doubles() { return lane_record_doubles(N); }
 
 }  // namespace chain
 }  // namespace gvi

@@ -1022,6 +1022,9 @@ ChainArgs make_chain_args(gvi_ctx* c, const ChainWs& w, const double* D, const d
   return a;
 }
 
+// the chain's switches as this context set them (chain_plan.hpp); merge holds where the launch also gets hand-over words
+ChainRules chain_rules(const gvi_ctx* c) { return {c->opt.chain_wave, c->opt.asm_dense, c->opt.chain_pair, c->opt.chain_merge}; }
+
 gvi_status run_chain(gvi_ctx* c, const ChainArgs& a0, const ChainArgs& a1, bool on0, bool on1, const AsmList* AL = nullptr) {
   hipStream_t st = c->stream;
   StageScope scope(c, STAGE_CHAIN);
@@ -1040,7 +1043,7 @@ gvi_status run_chain(gvi_ctx* c, const ChainArgs& a0, const ChainArgs& a1, bool 
     sy.words = (unsigned*)c->chain_sync.p + 2 * (sy.seq % RING);
     sy.fault = c->opt.chain_merge_fault ? 0x40000000u : 0u;
   }
-  const hipError_t e = chain_launch(c->n, chain_plan(c->T, c->n), a0, a1, on0, on1, st, AL, sy);
+  const hipError_t e = chain_launch(c->n, chain_rules(c), a0, a1, on0, on1, st, AL, sy);
   if (e == hipErrorInvalidValue) return fail(c, GVI_ERR_UNSUPPORTED, "chain kernels: block size / LDS budget");
   HIPCK(c, e);
   return GVI_OK;

@@ -32,7 +32,7 @@
 // Selected inverse: lane = element (r, c); all operands row-contiguous in LDS (every Sig[e, neighbour] block is kept
 // in both orientations), 16-byte reads.
 //
-// Passes (host: chain_plan): A -- every workgroup owns S = 2^m consecutive alive nodes and runs m levels on them in LDS;
+// Passes (host: chain_plan.hpp): A -- every workgroup owns S = 2^m consecutive alive nodes and runs m levels on them in LDS;
 // B (top) -- one workgroup takes the survivors through the remaining levels, the root, the log-det reduction and the
 // backward recursion of those nodes; C -- backward recursion inside every segment.  What crosses a segment boundary is
 // accumulated in LDS during the pass and written ONCE at its end: Rs[x0] (updates of the segment's first node from its
@@ -47,19 +47,12 @@
 #include <stdint.h>
 
 #include "chain_lane_record.hpp"
+#include "chain_plan.hpp"
 #include "device_common.hpp"
 #include "dpp_rowb.hpp"
 #include "kernels_bt.hpp"
 
 namespace gvi {
-
-constexpr int CHAIN_MATS = 10;   // E, GAt, GBt, NUt, Deff, Ls[2], Rs, SL, SR      each [T][N][N]
-constexpr int CHAIN_VECS = 5;    // v, yLs[2], yRs, yeff                           each [T][N]
-
-__host__ __device__ inline size_t chain_lp_entries(int T) { return (size_t)2 * T + 1024; }
-__host__ __device__ inline size_t chain_ws_doubles(int T, int n) {
-  return (size_t)CHAIN_MATS * T * n * n + (size_t)CHAIN_VECS * T * n + chain_lp_entries(T);
-}
 
 struct ChainArgs {
   int T;
@@ -105,7 +98,7 @@ struct ChainArgs {
   unsigned sync_seq;
   unsigned sync_fault;   // test hook: added to the word the producer stores (the consumers then time out)
 };
-// what changes from pass to pass (chain_launch.hpp::ChainPass), for the second pass of a merged launch
+// what changes from pass to pass (chain_plan.hpp::ChainPass), for the second pass of a merged launch
 struct ChainPassDev { int level0, m, S, first, par, lp_off; };
 
 // Chain-structured factor sets for the assemble-on-load: factor k of a binary set (d = 2n) couples states k, k + 1, factor
@@ -174,7 +167,7 @@ __device__ __forceinline__ void asm_pair(const AsmList& L, const int n, const in
   }
 }
 
-// ---- DENSE assemble-on-load (ChainArgs::asm_on == ASM_DENSE; the host classifies, chain_asm_dense below) ----
+// ---- DENSE assemble-on-load (ChainArgs::asm_on == ASM_DENSE; the host classifies, chain_plan.hpp::chain_asm_dense) ----
 // asm_pair / asm_element walk the sets in a run-time loop: per set four or five scalar loads of its fields one after the other,
 // the element loads each behind its own branch, and a wait for them before the next set starts -- about five dependent
 // vector-memory round trips and fifteen scalar ones in front of a pass's first level, on data the factor pass of other XCDs
@@ -253,22 +246,6 @@ __device__ __forceinline__ double asm_dense_g_sum(const AsmDense& q, const bool 
   if (q.two_sets) acc += q.b_first ? su : sb;
   return acc;
 }
-// host: the pattern above (every set present, with data; set order free)
-inline bool chain_asm_dense(const AsmList& L, const int n) {
-  if (L.nsets < 1 || L.nsets > 2) return false;
-  int nb = 0, nu = 0;
-  for (int i = 0; i < L.nsets; ++i) {
-    const AsmSet& s = L.s[i];
-    if (s.nsp != 0 || s.K < 1 || !s.Vdmu || !s.Vddmu) return false;
-    if (s.d == 2 * n) ++nb;
-    else if (s.d == n) ++nu;
-    else return false;
-  }
-  return nb <= 1 && nu <= 1;
-}
-
-constexpr int chain_threads(int n) { return n <= 8 ? 1024 : 512; }
-
 // -DGVI_CHAIN_TIMING (tools/ubench/chain_bench.hip only): shader-clock stamps of wave 0 of the top pass's factorisation
 #ifdef GVI_CHAIN_TIMING
 __device__ unsigned long long gvi_chain_stamps[256];
@@ -848,23 +825,6 @@ __device__ __forceinline__ void marginal_node(double* sm, const int lane, const 
     }
   }
   CHAIN_STAMP(stamp);
-}
-
-// LDS footprint (doubles)
-template <bool HAS_E, bool HAS_Y, bool TOP, int N>
-__host__ __device__ constexpr size_t fwd_lds_doubles(int S, bool rowb = false) {   // rowb: the two-row form (N = 6) runs this pass
-  constexpr int nn = N * N;
-  size_t w = (size_t)2 * (S + 1) * nn + (size_t)2 * S * nn;              // Dl, Rl, Ct, NUt
-  if (TOP) w += (size_t)3 * S * nn + (HAS_E ? (size_t)S * nn : 0);       // El, GAl, GBl (+ SRt of the backward recursion)
-  if (HAS_Y) w += (size_t)2 * (S + 1) * N + (TOP ? (size_t)(2 * S + 1) * N : 0);   // yl, yRl (+ vl, xl)
-  return w + N + (N & 1) + 128 + (rowb ? 96 + lane_record_doubles<N>() : 0);   // zero block, log-det reduction; two-row form: eliminate2's log-pivot slots, lane records
-}
-template <bool HAS_E, int N>
-__host__ __device__ constexpr size_t bwd_lds_doubles(int S) {
-  constexpr int nn = N * N;
-  return (HAS_E ? (size_t)5 * (S + 1) * nn + (size_t)3 * S * nn            // Sg, SL, SLt, SR, SRt ; E, GA, GB
-                : (size_t)(S + 1) * N + (size_t)S * N + (size_t)2 * S * nn)   // x, v, GA, GB
-         + 2;                                                              // chain_wait's word
 }
 
 // ---- hand-over inside a launch (chain_top_back_kernel) ----

@@ -14,13 +14,11 @@
 // Launch: blocks [0, nb0) of 64 threads = factorisation a0 (unpivoted, log-det, selected inverse when need_back), the rest the
 // pivoted solve a1; assemble-on-load, the fused trial precision (mix) and predicates as in chain_forward_kernel.
 #pragma once
+#include "chain_plan.hpp"   // WN, WT_MAX
 #include "kernels_chain.hpp"
 
 namespace gvi {
 namespace chain_wave {
-
-constexpr int WN = 2;            // compiled block size (n = 1 is padded by the identity)
-constexpr int WT_MAX = 65;
 
 __device__ __forceinline__ double shf(const double v, const int src) { return __shfl(v, src); }   // source lane mod 64
 

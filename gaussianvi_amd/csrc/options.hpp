@@ -14,11 +14,6 @@
 
 namespace gvi {
 
-// process-wide A/B switches of the chain kernels (chain_launch.hpp): the rows below write them through these accessors
-inline bool& chain_wave_enabled();
-inline bool& chain_asm_dense_enabled();
-inline bool& chain_pair_enabled();
-
 struct Options {
   bool warm_start = true;             // resident NGD: Jacobi warm start from the previous eigenvectors
   // gvi_ngd_step: trial cost from the full moments pass at the trial point (one psi pass per accepted iteration).
@@ -63,6 +58,12 @@ struct Options {
   // is not launched behind the factor pass but done by the first pass of the chain operations that consume it
   // (kernels_chain.hpp, AsmList; NgdBook::asm_pending)
   bool asm_on_load = true;
+  // A/B legs of the chain kernels (chain_plan.hpp::ChainRules): 0 keeps short chains of 2 x 2 blocks (T <= 65, n <= 2) on the
+  // generic kernels instead of the lane-per-node kernel / an assemble-on-load on the generic set loop instead of the batched
+  // first-pass load / the N = 6 eliminations of every pass on the v_readlane kernels instead of the two-row form
+  bool chain_wave = true;
+  bool asm_dense = true;
+  bool chain_pair = true;
   bool chain_merge = true;            // top pass + first backward pass of the chain in one launch (chain_launch.hpp::ChainSync)
   bool chain_merge_fault = false;     // option chain_merge = 2 only: the hand-over word is stored wrong (test of the bounded wait)
   // gvi_ngd_run queues iteration i + 1 (predicated) before it has read the cost of iteration i.  Round 2 measured no gain
@@ -90,18 +91,16 @@ struct OptionRow {
   const char* env;               // environment variable read at gvi_ctx_create, or null: option only
   OptionRule rule;
   int lo, hi;
-  bool Options::*flag;           // the field: exactly one of these four is set
+  bool Options::*flag;           // the field: exactly one of these three is set
   int Options::*num;
   double Options::*real;
-  bool& (*process)();            // process-wide switch
 };
 
-constexpr OptionRow opt_flag(const char* name, const char* env, bool Options::*f) { return {name, env, OPT_FLAG, 0, 0, f, nullptr, nullptr, nullptr}; }
-constexpr OptionRow opt_flag_inv(const char* name, const char* env, bool Options::*f) { return {name, env, OPT_FLAG_INV, 0, 0, f, nullptr, nullptr, nullptr}; }
-constexpr OptionRow opt_process(const char* name, const char* env, bool& (*f)()) { return {name, env, OPT_FLAG, 0, 0, nullptr, nullptr, nullptr, f}; }
-constexpr OptionRow opt_min(const char* name, const char* env, int Options::*f, int lo) { return {name, env, OPT_MIN, lo, 0, nullptr, f, nullptr, nullptr}; }
-constexpr OptionRow opt_clamp(const char* name, const char* env, int Options::*f, int lo, int hi) { return {name, env, OPT_CLAMP, lo, hi, nullptr, f, nullptr, nullptr}; }
-constexpr OptionRow opt_pow10(const char* name, double Options::*f, int hi) { return {name, nullptr, OPT_POW10_MAX, 0, hi, nullptr, nullptr, f, nullptr}; }
+constexpr OptionRow opt_flag(const char* name, const char* env, bool Options::*f) { return {name, env, OPT_FLAG, 0, 0, f, nullptr, nullptr}; }
+constexpr OptionRow opt_flag_inv(const char* name, const char* env, bool Options::*f) { return {name, env, OPT_FLAG_INV, 0, 0, f, nullptr, nullptr}; }
+constexpr OptionRow opt_min(const char* name, const char* env, int Options::*f, int lo) { return {name, env, OPT_MIN, lo, 0, nullptr, f, nullptr}; }
+constexpr OptionRow opt_clamp(const char* name, const char* env, int Options::*f, int lo, int hi) { return {name, env, OPT_CLAMP, lo, hi, nullptr, f, nullptr}; }
+constexpr OptionRow opt_pow10(const char* name, double Options::*f, int hi) { return {name, nullptr, OPT_POW10_MAX, 0, hi, nullptr, nullptr, f}; }
 
 // A name with two rows (pair_fuse, fuse_gather) has its option under the plain sense and its environment variable inverted.
 constexpr OptionRow OPTION_ROWS[] = {
@@ -109,9 +108,9 @@ constexpr OptionRow OPTION_ROWS[] = {
   opt_flag("fused", "GVI_FUSED", &Options::fused),
   opt_flag("assemble_on_load", "GVI_ASM_ON_LOAD", &Options::asm_on_load),
   opt_flag("pipeline", "GVI_PIPELINE", &Options::pipeline),
-  opt_process("chain_wave", "GVI_CHAIN_WAVE", &chain_wave_enabled),        // A/B leg of kernels_chain_wave.hpp
-  opt_process("asm_dense", "GVI_ASM_DENSE", &chain_asm_dense_enabled),     // A/B leg of the batched first-pass load
-  opt_process("chain_pair", "GVI_CHAIN_PAIR", &chain_pair_enabled),        // A/B leg of the row-broadcast eliminations
+  opt_flag("chain_wave", "GVI_CHAIN_WAVE", &Options::chain_wave),          // A/B leg of kernels_chain_wave.hpp
+  opt_flag("asm_dense", "GVI_ASM_DENSE", &Options::asm_dense),             // A/B leg of the batched first-pass load
+  opt_flag("chain_pair", "GVI_CHAIN_PAIR", &Options::chain_pair),          // A/B leg of the row-broadcast eliminations
   opt_flag("chain_merge", "GVI_CHAIN_MERGE", &Options::chain_merge),       // (option value 2: gvi_set_option sets chain_merge_fault)
   opt_flag("chol_rowb", "GVI_CHOL_ROWB", &Options::chol_rowb),
   opt_clamp(nullptr, "GVI_FUSE_TRIAL", &Options::fuse_trial, 0, 2),
@@ -142,11 +141,7 @@ constexpr OptionRow OPTION_ROWS[] = {
 inline bool option_apply(Options& o, const OptionRow& r, int v, std::string* msg) {
   switch (r.rule) {
     case OPT_FLAG:
-    case OPT_FLAG_INV: {
-      const bool on = r.rule == OPT_FLAG ? v != 0 : v == 0;
-      if (r.process) r.process() = on; else o.*r.flag = on;
-      break;
-    }
+    case OPT_FLAG_INV: o.*r.flag = r.rule == OPT_FLAG ? v != 0 : v == 0; break;
     case OPT_MIN: o.*r.num = v > r.lo ? v : r.lo; break;
     case OPT_CLAMP: o.*r.num = v < r.lo ? r.lo : v > r.hi ? r.hi : v; break;
     case OPT_POW10_MAX:

@@ -222,7 +222,7 @@ static gvi_status run_logpdf(gvi_ctx* ctx, const double* dD, const double* dU, c
   a.T = T; a.n = n; a.need_back = 0;
   a.D = dD; a.U = dU; a.rhs_scale = 1.0;
   a.ws = ctx->post.smp_cws.d(); a.wsi = (int*)ctx->post.smp_cwsi.p; a.hld = dh;
-  const hipError_t e = chain_launch(n, chain_plan(T, n), a, a, true, false, ctx->stream);
+  const hipError_t e = chain_launch(n, chain_rules(ctx), a, a, true, false, ctx->stream);
   if (e == hipErrorInvalidValue) return fail(ctx, GVI_ERR_UNSUPPORTED, "chain kernels: block size / LDS budget");
   HIPCK(ctx, e);
   const int64_t items = (int64_t)S * T;

@@ -638,15 +638,16 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * sum, cost and back-transform of a factor in one workgroup; 0: the three launches prep -> psi -> epilogue),
  * "jacobi_tol_exp" (stopping threshold 10^value of the symmetric-root solve, on SQUARED off-diagonal / diagonal mass; values
  * above -20 return GVI_ERR_ARG).
- * chain_wave (default 1; process-wide, environment GVI_CHAIN_WAVE): chains of T <= 65 states of size n <= 2 run on the
+ * chain_wave (default 1; environment GVI_CHAIN_WAVE): chains of T <= 65 states of size n <= 2 run on the
  * lane-per-node kernel (one wave per chain operation) instead of the generic block-cyclic-reduction kernels.
- * asm_dense (default 1; process-wide, environment GVI_ASM_DENSE): an assemble-on-load over at most one binary (d = 2n) and one
+ * asm_dense (default 1; environment GVI_ASM_DENSE): an assemble-on-load over at most one binary (d = 2n) and one
  * unary (d = n) chain-structured set issues all loads of a thread's round before the first use; 0 keeps the generic set loop.
- * chain_pair (default 1; process-wide, environment GVI_CHAIN_PAIR): chains of block size 5 or 6 run the forward eliminations of every
+ * chain_pair (default 1; environment GVI_CHAIN_PAIR): chains of block size 5 or 6 run the forward eliminations of every
  * pass that has a level with more than eight eliminations per workgroup (any chain of 18 or more states) in the two-row tile layout,
  * whose pivot columns are broadcast inside a 16-lane row by DPP (row_newbcast) instead of v_readlane, with two nodes per wave on
  * those levels; the other passes, and every pass under 0, keep one node per wave on v_readlane (kernels of their own).
  * Same arithmetic, same association of the log-pivot product: every result is bit-identical.
+ * chain_wave, asm_dense and chain_pair belong, like every option, to the context they are set on.
  * chain_merge (default 1; environment GVI_CHAIN_MERGE): a chain of more than one pass runs its top pass and the backward
  * recursion of the last segmented pass in ONE launch (the backward workgroups wait for a device word the top pass's workgroup
  * releases); 0: one launch per pass.  The wait is bounded (1 s); on a time-out the waiting workgroups take NaN for what they

@@ -13,7 +13,7 @@ import functools
 
 import numpy as np
 
-# ---- chain_launch.hpp::chain_plan, restated: padded block size N -> (cap = longest top pass, m_seg = levels of a segmented pass)
+# ---- chain_plan.hpp::chain_passes, restated: padded block size N -> (cap = longest top pass, m_seg = levels of a segmented pass)
 # (test_chain_pivot_host.py compares the two expressions with the header's text)
 PADDED = (1, 2, 3, 4, 6, 8, 12, 16)
 CAP_EXPR = "n <= 2 ? 128 : (n <= 4 ? 64 : (n <= 6 ? 48 : (n <= 8 ? 24 : 8)))"

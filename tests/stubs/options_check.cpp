@@ -11,12 +11,6 @@
 
 #include "../../gaussianvi_amd/csrc/options.hpp"
 
-namespace gvi {   // the process-wide switches live in chain_launch.hpp, which needs HIP: the same accessors over plain statics
-inline bool& chain_wave_enabled() { static bool on = true; return on; }
-inline bool& chain_asm_dense_enabled() { static bool on = true; return on; }
-inline bool& chain_pair_enabled() { static bool on = true; return on; }
-}
-
 using namespace gvi;
 
 static void dump(const Options& o) {
@@ -27,7 +21,7 @@ static void dump(const Options& o) {
               o.warm_start, o.fuse_trial, o.target_waves, o.mirror, o.split_flush, o.sreg_pipe, o.no_scost, o.orbit, o.fused,
               o.orbit_waves, o.jacobi_tol, o.chol_sqrt, o.chol_rowb, o.trust_table_degree, o.orbit_min_tiles, o.orbit_copies,
               o.pair_fuse, o.fuse_gather, o.side_solve, o.asm_on_load, o.chain_merge, o.chain_merge_fault, o.pipeline, o.spin_ms,
-              o.safe_publish, o.sample_sweep, o.solve_lds, chain_wave_enabled(), chain_asm_dense_enabled(), chain_pair_enabled());
+              o.safe_publish, o.sample_sweep, o.solve_lds, o.chain_wave, o.asm_dense, o.chain_pair);
 }
 
 int main(int argc, char** argv) {
@@ -39,7 +33,6 @@ int main(int argc, char** argv) {
     std::string cmd, name, value;
     ls >> cmd >> name >> value;
     Options o;
-    chain_wave_enabled() = chain_asm_dense_enabled() = chain_pair_enabled() = true;
     if (cmd == "rows") {
       std::printf("rows");
       for (const OptionRow& r : OPTION_ROWS) std::printf(" %s:%s", r.name ? r.name : "-", r.env ? r.env : "-");

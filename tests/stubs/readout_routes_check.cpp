@@ -6,13 +6,6 @@
 #include "readout_moments.hpp"
 #include "routes.hpp"
 
-// the process-wide switches of the chain kernels that the option table names (chain_launch.hpp defines them in the library)
-namespace gvi {
-inline bool& chain_wave_enabled() { static bool on = true; return on; }
-inline bool& chain_asm_dense_enabled() { static bool on = true; return on; }
-inline bool& chain_pair_enabled() { static bool on = true; return on; }
-}  // namespace gvi
-
 using namespace gvi;
 
 static int failures = 0;

@@ -17,13 +17,6 @@
 
 #include "../../gaussianvi_amd/csrc/routes.hpp"
 
-// the process-wide switches of the chain kernels that the option table names (chain_launch.hpp defines them in the library)
-namespace gvi {
-inline bool& chain_wave_enabled() { static bool on = true; return on; }
-inline bool& chain_asm_dense_enabled() { static bool on = true; return on; }
-inline bool& chain_pair_enabled() { static bool on = true; return on; }
-}  // namespace gvi
-
 using namespace gvi;
 using KV = std::map<std::string, long long>;
 

@@ -50,7 +50,7 @@ from test_handover_fresh_gpu import far_at_every_node
 
 pytestmark = pytest.mark.gpu
 
-DENSE_DEFAULT = int(os.environ.get("GVI_ASM_DENSE", "1") != "0")     # the process-wide switches as the library read them
+DENSE_DEFAULT = int(os.environ.get("GVI_ASM_DENSE", "1") != "0")     # the switches as a context reads them at creation
 WAVE_DEFAULT = int(os.environ.get("GVI_CHAIN_WAVE", "1") != "0")
 STEP = 0.55 * 0.75                                                   # the first trial of ngd_step(0.55, .)
 ALL_ON = dict(asm_dense=1, assemble_on_load=1, chain_merge=1)
@@ -165,7 +165,7 @@ def _context(P, wave, options):
 
 
 def _restore(ctx):
-    ctx.set_option("asm_dense", DENSE_DEFAULT)                    # (process-wide switches)
+    ctx.set_option("asm_dense", DENSE_DEFAULT)                    # (the context closes next: harmless)
     ctx.set_option("chain_wave", WAVE_DEFAULT)
     ctx.close()
 

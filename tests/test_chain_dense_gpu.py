@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 syn.CONFIGS.setdefault("c3t75", (39, 75, 6, 5, "ltv"))
 STEPS = 6
-DENSE_DEFAULT = int(os.environ.get("GVI_ASM_DENSE", "1") != "0")     # the process-wide switch as the library read it
+DENSE_DEFAULT = int(os.environ.get("GVI_ASM_DENSE", "1") != "0")     # the switch as a context reads it at creation
 ON_LOAD_DEFAULT = int(os.environ.get("GVI_ASM_ON_LOAD", "1") != "0")  # (per context, read at its creation)
 
 
@@ -45,7 +45,7 @@ def _run(ch, seed, options):
         state = ctx.ngd_get_state()
         after = api.asm_launches()
     finally:
-        ctx.set_option("asm_dense", DENSE_DEFAULT)  # (process-wide switch)
+        ctx.set_option("asm_dense", DENSE_DEFAULT)  # (the context closes next: harmless)
         ctx.close()
     # the launches that assembled while loading: all on the batched path, all on the generic loop, or none at all
     dense, generic = after[0] - before[0], after[1] - before[1]

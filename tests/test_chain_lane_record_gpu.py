@@ -64,7 +64,7 @@ def spd_case(T, n):
 
 
 def _all_settings(T, n, fn):
-    """fn(ctx) under every (chain_pair, chain_merge); the switches are process-wide and are put back"""
+    """fn(ctx) under every (chain_pair, chain_merge); the switches are the context's own; they are put back before it closes"""
     out = {}
     ctx = api.Context(0)
     try:

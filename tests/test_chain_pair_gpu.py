@@ -31,7 +31,7 @@ from test_handover_fresh_gpu import _state_b
 
 pytestmark = pytest.mark.gpu
 
-PAIR_DEFAULT = int(os.environ.get("GVI_CHAIN_PAIR", "1") != "0")      # the process-wide switches as the library read them
+PAIR_DEFAULT = int(os.environ.get("GVI_CHAIN_PAIR", "1") != "0")      # the switches as a context reads them at creation
 DENSE_DEFAULT = int(os.environ.get("GVI_ASM_DENSE", "1") != "0")
 LENGTHS = (2, 3, 5, 33, 34, 35, 48, 49, 70, 97, 1025)
 SHAPES = [(T, n) for n in (6, 5) for T in LENGTHS] + [(T, n) for n in (4, 8) for T in (3, 33, 49, 97)]
@@ -163,7 +163,7 @@ def _ngd(ch, seed, options):
         results = [ctx.ngd_step(0.55, 10) for _ in range(STEPS)]
         state = ctx.ngd_get_state()
     finally:
-        ctx.set_option("chain_pair", PAIR_DEFAULT)               # (process-wide switches)
+        ctx.set_option("chain_pair", PAIR_DEFAULT)               # (the context closes next: harmless)
         ctx.set_option("asm_dense", DENSE_DEFAULT)
         ctx.close()
     return results, state

@@ -95,7 +95,7 @@ def test_pivoted_solve_with_row_swaps(T, n, gen):
             wave = {w: solve_b(ctx, A, B, chain_wave=w) for w in (1, 0)}
     finally:
         ctx.set_option("chain_merge", MERGE_DEFAULT)
-        ctx.set_option("chain_pair", PAIR_DEFAULT)                   # (process-wide switches)
+        ctx.set_option("chain_pair", PAIR_DEFAULT)                   # (the context closes next: harmless)
         ctx.set_option("chain_wave", WAVE_DEFAULT)
         ctx.close()
     errs = [rel(x, ref)] + [rel(v, ref) for v in wave.values()]

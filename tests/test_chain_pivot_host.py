@@ -15,10 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = [f"T{T}-n{n}-{gen}" for T, n, gen in R.CASES]
 
 
-def test_plan_restatement_matches_chain_launch_hpp():
-    """chain_passes restates chain_launch.hpp::chain_plan; the library exposes no call for the plan, so the two expressions that
+def test_plan_restatement_matches_chain_plan_hpp():
+    """chain_passes restates chain_plan.hpp::chain_passes; the library exposes no call for the plan, so the two expressions that
     decide it are compared with the header's text, and the restatement with the issue's table of (cap, S)."""
-    src = open(os.path.join(ROOT, "gaussianvi_amd", "csrc", "chain_launch.hpp")).read()
+    src = open(os.path.join(ROOT, "gaussianvi_amd", "csrc", "chain_plan.hpp")).read()
     assert re.search(r"const int m_seg = " + re.escape(R.MSEG_EXPR) + ";", src)
     assert re.search(r"const int cap = " + re.escape(R.CAP_EXPR) + ";", src)
     assert re.search(r"for \(int N : \{" + ", ".join(map(str, R.PADDED)) + r"\}\)", src)

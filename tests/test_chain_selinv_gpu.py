@@ -102,7 +102,7 @@ def _ids(cases):
 
 def _restore(ctx):
     ctx.set_option("chain_merge", MERGE_DEFAULT)
-    ctx.set_option("chain_pair", PAIR_DEFAULT)                       # (process-wide switches)
+    ctx.set_option("chain_pair", PAIR_DEFAULT)                       # (the context closes next: harmless)
     ctx.set_option("chain_wave", WAVE_DEFAULT)
     ctx.close()
 

@@ -1184,7 +1184,7 @@ def test_lane_per_node_chain_kernel_matches_the_generic_chain_kernels(name):
     """kernels_chain_wave.hpp (lane = node, one wave per chain operation; T <= 65, n <= 2) against kernels_chain.hpp on the same
     chains: chain operators (log-det, marginals, solve) to 1e-13 and six NGD iterations with the same accept decisions, costs
     to 1e-12.  Same elimination tree and the same arithmetic per node; the log-det's pivot product is reduced in another
-    order, hence not bit for bit.  The switch is process-wide: restored in any case."""
+    order, hence not bit for bit.  The switch is the context's own and goes with it."""
     ch = make_chain(name)
     ctx, ids = api.context_for_chain(ch)
     try:
@@ -1198,7 +1198,6 @@ def test_lane_per_node_chain_kernel_matches_the_generic_chain_kernels(name):
             log = ctx.ngd_run(6, 0.9, 10)
             res.append((fac, x, log, ctx.ngd_get_state()))
     finally:
-        ctx.set_option("chain_wave", 1)
         ctx.close()
     (fa, xa, la, sa), (fb, xb, lb, sb) = res
     for u, v in zip(fa, fb):

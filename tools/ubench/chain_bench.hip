@@ -106,6 +106,9 @@ __global__ void asm_fill_kernel(double* Vdmu_b, double* Vddmu_b, double* Vdmu_u,
   }
 }
 
+// the switches the legs below time (chain_plan.hpp); merge holds only where next_sync hands words out
+static gvi::ChainRules g_rules{true, true, true, true};
+
 // CHAIN_MERGE=1: the top pass and the first backward pass in one launch (chain_launch.hpp::ChainSync)
 static unsigned* g_sync_words = nullptr;
 static unsigned g_sync_seq = 0;
@@ -162,8 +165,8 @@ static int run(int T, int n, int reps) {
   a0.SigD = dSig; a0.SigU = dSig + btD; a0.x = nullptr; a0.hld = dhld; a0.mixV = nullptr; a0.mixOut = nullptr; a0.mix_step = 0; a0.pred = nullptr; a0.pred_val = 0;
   a1 = a0;
   a1.need_back = 0; a1.D = dD1; a1.U = dD1 + btD; a1.rhs = drhs; a1.rhs_scale = -1.0; a1.ws = ws1; a1.wsi = wi1; a1.SigD = nullptr; a1.SigU = nullptr; a1.x = dx_; a1.hld = nullptr;
-  const ChainPlan pl = chain_plan(T, n);
-  printf("T = %d, n = %d (kernels at N = %d): %zu forward pass(es), %d threads\n", T, n, NP, pl.passes.size(), pl.threads);
+  const ChainPasses pl = chain_passes(T, n);
+  printf("T = %d, n = %d (kernels at N = %d): %d forward pass(es), %d threads\n", T, n, NP, pl.npass, pl.threads);
 
   auto check = [&](const char* name) {
     std::vector<double> SigD(btD), SigU(btU), x((size_t)T * n);
@@ -179,21 +182,21 @@ static int run(int T, int n, int reps) {
 
   int fail = 0;
   clear_out();
-  CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync()));
+  CK(chain_launch(n, g_rules, a0, a1, true, true, st, nullptr, next_sync()));
   fail |= check("both");
   // single operations through the same kernels
   clear_out();
-  CK(chain_launch(n, pl, a0, a1, true, false, st, nullptr, next_sync()));
-  CK(chain_launch(n, pl, a0, a1, false, true, st, nullptr, next_sync()));
+  CK(chain_launch(n, g_rules, a0, a1, true, false, st, nullptr, next_sync()));
+  CK(chain_launch(n, g_rules, a0, a1, false, true, st, nullptr, next_sync()));
   fail |= check("single");
   // run-to-run bit identity
   {
     std::vector<double> A(btD + btU), B(btD + btU);
-    CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); CK(hipStreamSynchronize(st));
+    CK(chain_launch(n, g_rules, a0, a1, true, true, st, nullptr, next_sync())); CK(hipStreamSynchronize(st));
     CK(hipMemcpy(A.data(), dSig, (btD + btU) * 8, hipMemcpyDeviceToHost));
     int diff = 0;
     for (int it = 0; it < 5; ++it) {
-      CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); CK(hipStreamSynchronize(st));
+      CK(chain_launch(n, g_rules, a0, a1, true, true, st, nullptr, next_sync())); CK(hipStreamSynchronize(st));
       CK(hipMemcpy(B.data(), dSig, (btD + btU) * 8, hipMemcpyDeviceToHost));
       for (size_t i = 0; i < A.size(); ++i) diff += A[i] != B[i];
     }
@@ -201,15 +204,15 @@ static int run(int T, int n, int reps) {
     fail |= diff != 0;
   }
   // chain_pair 1 against 0 (N = 6: two-row eliminations with DPP row-broadcast pivots against the v_readlane form): every output word
-  const bool pair_default = chain_pair_enabled();
+  const bool pair_default = g_rules.pair;
   {
     const size_t nout = btD + btU + (size_t)T * n + 1;
     std::vector<double> R[2];
     for (int leg = 0; leg < 2; ++leg) {
-      chain_pair_enabled() = leg == 0;
+      g_rules.pair = leg == 0;
       clear_out();
       CK(hipMemsetAsync(ws0, 0xff, chain_ws_doubles(T, NP) * 8, st)); CK(hipMemsetAsync(ws1, 0xff, chain_ws_doubles(T, NP) * 8, st));
-      CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync()));
+      CK(chain_launch(n, g_rules, a0, a1, true, true, st, nullptr, next_sync()));
       CK(hipStreamSynchronize(st));
       R[leg].resize(nout);
       double* o = R[leg].data();
@@ -217,7 +220,7 @@ static int run(int T, int n, int reps) {
       CK(hipMemcpy(o, dx_, (size_t)T * n * 8, hipMemcpyDeviceToHost)); o += (size_t)T * n;
       CK(hipMemcpy(o, dhld, 8, hipMemcpyDeviceToHost));
     }
-    chain_pair_enabled() = pair_default;
+    g_rules.pair = pair_default;
     size_t diff = 0, nan = 0;
     for (size_t i = 0; i < nout; ++i) { diff += memcmp(&R[0][i], &R[1][i], 8) != 0; nan += R[0][i] != R[0][i]; }
     printf("chain_pair 1 vs 0 differing words: %zu of %zu (NaN: %zu)\n", diff, nout, nan);
@@ -230,7 +233,7 @@ static int run(int T, int n, int reps) {
     // barrier after each level, root, ..., backward: per node [phase 1 | sync | phase 2], barrier)
     int zero = 0;
     CK(hipMemcpyToSymbol(HIP_SYMBOL(gvi_chain_nstamp), &zero, sizeof(int)));
-    CK(chain_launch(n, pl, a0, a1, true, false, st, nullptr, next_sync()));
+    CK(chain_launch(n, g_rules, a0, a1, true, false, st, nullptr, next_sync()));
     CK(hipStreamSynchronize(st));
     int ns = 0;
     std::vector<unsigned long long> stp(256);
@@ -264,12 +267,12 @@ static int run(int T, int n, int reps) {
     const size_t nout = btD + btU + (size_t)T * n + 1 + (btD + btU) + ((size_t)T * n + btD + btU);
     std::vector<double> R[2];
     for (int leg = 0; leg < 2; ++leg) {
-      chain_asm_dense_enabled() = leg == 0;
+      g_rules.asm_dense = leg == 0;
       clear_out();
       CK(hipMemsetAsync(dMix, 0xff, (btD + btU) * 8, st)); CK(hipMemsetAsync(dAsm, 0xff, ((size_t)T * n + btD + btU) * 8, st));
       salt = 77;
       fill();
-      CK(chain_launch(n, pl, b0, b1, true, true, st, &AL, next_sync()));
+      CK(chain_launch(n, g_rules, b0, b1, true, true, st, &AL, next_sync()));
       CK(hipStreamSynchronize(st));
       R[leg].resize(nout);
       double* o = R[leg].data();
@@ -279,7 +282,7 @@ static int run(int T, int n, int reps) {
       CK(hipMemcpy(o, dMix, (btD + btU) * 8, hipMemcpyDeviceToHost)); o += btD + btU;
       CK(hipMemcpy(o, dAsm, ((size_t)T * n + btD + btU) * 8, hipMemcpyDeviceToHost));
     }
-    chain_asm_dense_enabled() = true;
+    g_rules.asm_dense = true;
     size_t diff = 0, nan = 0;
     for (size_t i = 0; i < nout; ++i) { diff += memcmp(&R[0][i], &R[1][i], 8) != 0; nan += R[0][i] != R[0][i]; }
     printf("assemble-on-load: dense vs generic differing words: %zu of %zu (NaN: %zu)\n", diff, nout, nan);
@@ -289,13 +292,13 @@ static int run(int T, int n, int reps) {
   if (asm_leg) {
     // the same stamps with the assemble-on-load in the first pass, its inputs freshly written; then with the generic set loop
     for (int leg = 0; leg < 2; ++leg) {
-      chain_asm_dense_enabled() = leg == 0;
+      g_rules.asm_dense = leg == 0;
       for (int rep = 0; rep < 3; ++rep) {
         int zero = 0;
         hipLaunchKernelGGL(asm_fill_kernel, dim3(256), dim3(256), 0, st, dGb, dVb, dGu, dVu, T, n, salt++);
         CK(hipStreamSynchronize(st));
         CK(hipMemcpyToSymbol(HIP_SYMBOL(gvi_chain_nstamp), &zero, sizeof(int)));
-        CK(chain_launch(n, pl, b0, b1, true, true, st, &AL, next_sync()));
+        CK(chain_launch(n, g_rules, b0, b1, true, true, st, &AL, next_sync()));
         CK(hipStreamSynchronize(st));
         int ns = 0;
         std::vector<unsigned long long> stp(256);
@@ -306,7 +309,7 @@ static int run(int T, int n, int reps) {
         printf("\n");
       }
     }
-    chain_asm_dense_enabled() = true;
+    g_rules.asm_dense = true;
   }
 #endif
   // timing
@@ -324,28 +327,28 @@ static int run(int T, int n, int reps) {
     printf("%-28s %8.2f us per call\n", name, 1e3 * ms / reps);
   };
   for (int rep = 0; rep < 3; ++rep) {                // interleaved: chain_pair 1, 0, 1, 0, 1, 0
-    chain_pair_enabled() = true;
-    time_it("factor || solve chain_pair=1", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
-    chain_pair_enabled() = false;
-    time_it("factor || solve chain_pair=0", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
+    g_rules.pair = true;
+    time_it("factor || solve chain_pair=1", [&]() { CK(chain_launch(n, g_rules, a0, a1, true, true, st, nullptr, next_sync())); });
+    g_rules.pair = false;
+    time_it("factor || solve chain_pair=0", [&]() { CK(chain_launch(n, g_rules, a0, a1, true, true, st, nullptr, next_sync())); });
   }
-  chain_pair_enabled() = pair_default;
-  time_it("factor || solve", [&]() { CK(chain_launch(n, pl, a0, a1, true, true, st, nullptr, next_sync())); });
-  time_it("factor only", [&]() { CK(chain_launch(n, pl, a0, a1, true, false, st, nullptr, next_sync())); });
-  time_it("solve only", [&]() { CK(chain_launch(n, pl, a0, a1, false, true, st, nullptr, next_sync())); });
+  g_rules.pair = pair_default;
+  time_it("factor || solve", [&]() { CK(chain_launch(n, g_rules, a0, a1, true, true, st, nullptr, next_sync())); });
+  time_it("factor only", [&]() { CK(chain_launch(n, g_rules, a0, a1, true, false, st, nullptr, next_sync())); });
+  time_it("solve only", [&]() { CK(chain_launch(n, g_rules, a0, a1, false, true, st, nullptr, next_sync())); });
   if (asm_leg) {
     auto call = [&]() {
       hipLaunchKernelGGL(asm_fill_kernel, dim3(256), dim3(256), 0, st, dGb, dVb, dGu, dVu, T, n, salt++);
-      CK(chain_launch(n, pl, b0, b1, true, true, st, &AL, next_sync()));
+      CK(chain_launch(n, g_rules, b0, b1, true, true, st, &AL, next_sync()));
     };
     time_it("fill only", [&]() { hipLaunchKernelGGL(asm_fill_kernel, dim3(256), dim3(256), 0, st, dGb, dVb, dGu, dVu, T, n, salt++); });
     for (int rep = 0; rep < 2; ++rep) {              // interleaved: dense, generic, dense, generic
-      chain_asm_dense_enabled() = true;
+      g_rules.asm_dense = true;
       time_it("fill + asm-on-load dense", call);
-      chain_asm_dense_enabled() = false;
+      g_rules.asm_dense = false;
       time_it("fill + asm-on-load generic", call);
     }
-    chain_asm_dense_enabled() = true;
+    g_rules.asm_dense = true;
   }
   {
     // the same launches with a predicate that does not hold: every block returns at its first instruction -- what the launch
@@ -355,7 +358,7 @@ static int run(int T, int n, int reps) {
     CK(hipMemset(dpred, 0, 8));
     ChainArgs s0 = a0, s1 = a1;
     s0.pred = s1.pred = dpred; s0.pred_val = s1.pred_val = 1.0;
-    time_it("skipped (predicate): both", [&]() { CK(chain_launch(n, pl, s0, s1, true, true, st, nullptr, next_sync())); });
+    time_it("skipped (predicate): both", [&]() { CK(chain_launch(n, g_rules, s0, s1, true, true, st, nullptr, next_sync())); });
     CK(hipFree(dpred));
   }
   return fail;
@@ -363,7 +366,7 @@ static int run(int T, int n, int reps) {
 
 int main(int argc, char** argv) {
   const int T = argc > 1 ? atoi(argv[1]) : 1025, n = argc > 2 ? atoi(argv[2]) : 6, reps = argc > 3 ? atoi(argv[3]) : 200;
-  if (const char* e = getenv("CHAIN_PAIR")) chain_pair_enabled() = atoi(e) != 0;      // the default of every leg but the chain_pair A/B
+  if (const char* e = getenv("CHAIN_PAIR")) g_rules.pair = atoi(e) != 0;      // the default of every leg but the chain_pair A/B
   if (!chain_supported(n)) { fprintf(stderr, "n must be in 1..16\n"); return 2; }
   const int rc = run(T, n, reps);
   printf(rc ? "FAILED\n" : "OK\n");
