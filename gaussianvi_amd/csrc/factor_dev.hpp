@@ -7,7 +7,7 @@
 
 namespace gvi {
 
-GVI_HD inline int npairs(int d) { return (d + 1) * (d + 2) / 2; }
+GVI_HD constexpr int npairs(int d) { return (d + 1) * (d + 2) / 2; }
 
 // packed z-space moment layout: [0] m0 | [1..d] m1 | then upper triangle of M2 row by row
 GVI_HD inline int pair_index(int d, int a, int b) {  // a <= b < d

@@ -649,8 +649,8 @@ gvi_status launch_fused_t(gvi_ctx* c, const FusedArgs& A, unsigned grid, size_t 
 
 // prep_kernel for the f.K factors of f at (mu, Sigma) device pointers: the instance of the dimension and its LDS
 gvi_status launch_prep(gvi_ctx* c, const FactorDev& f, const double* mu, const double* Sigma, hipStream_t st) {
-  const int d = f.d, dp = d + (d & 1);
-  const size_t lds = (size_t)(4 * d * d + 2 * dp + 3 * d) * 8 + (size_t)dp * 4 + 16;
+  const int d = f.d;
+  const size_t lds = prep_lds_bytes(d);
   if (d <= 8) hipLaunchKernelGGL(prep_kernel<1>, dim3(f.K), dim3(64), lds, st, f, mu, Sigma);
   else if (d <= 16) hipLaunchKernelGGL(prep_kernel<4>, dim3(f.K), dim3(64), lds, st, f, mu, Sigma);
   else if (d <= 32) hipLaunchKernelGGL(prep_kernel<16>, dim3(f.K), dim3(64), lds, st, f, mu, Sigma);
@@ -712,7 +712,7 @@ struct PassPlan {
 gvi_status plan_closed(gvi_ctx*, const FactorSet&, MomPlan&, ClosedSumsq) { return GVI_OK; }
 gvi_status plan_closed(gvi_ctx* c, const FactorSet& s, MomPlan& p, ClosedBox) {
   p.lds = box_closed_lds_doubles(s.d) * 8;
-  if (p.lds > 64 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_BOX kernel LDS budget (d <= 89)");
+  if (p.lds > BOX_CLOSED_LDS_LIMIT) return fail(c, GVI_ERR_UNSUPPORTED, "closed-form HINGE_BOX kernel LDS budget (d <= 89)");
   return GVI_OK;
 }
 gvi_status plan_closed(gvi_ctx*, const FactorSet& s, MomPlan& p, ClosedHalfspace) {
@@ -797,9 +797,8 @@ gvi_status bind_plan(gvi_ctx* c, FactorSet& s, const RouteDecision& r, const dou
     while (pa.copies * 2 <= c->opt.orbit_copies && (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies * 2, true) * 8 <= 64 * 1024) pa.copies *= 2;
     p.lds = (size_t)4 * orbit_psi_lds_doubles(s.d, NR, pa.copies, full != 0) * 8;
   } else if (r.route == Route::Generic) {
-    const int d = s.d, m = s.m;
-    p.lds = (size_t)(2 * GEN_BS * (d + 1) + GEN_BS + d * d + d + m * d + 2 * m) * 8;
-    if (p.lds > 160 * 1024) return fail(c, GVI_ERR_UNSUPPORTED, "generic kernel LDS budget");
+    p.lds = generic_lds_bytes(s.d, s.m);
+    if (p.lds > GENERIC_LDS_LIMIT) return fail(c, GVI_ERR_UNSUPPORTED, "generic kernel LDS budget");
   }
   return GVI_OK;
 }
@@ -846,7 +845,7 @@ gvi_status launch_plan(gvi_ctx* c, FactorSet& s, const MomPlan& p, hipStream_t s
       hit = with_reg_instance(s.kind, s.d, s.m, [&]<int D, typename Psi>(RegInst<D, Psi>) { launch_reg<D, Psi>(a, p.grid, st); });
       break;
     case Route::Generic:
-      GVICK(allow_lds(c, (const void*)moments_generic_kernel, 160 * 1024));
+      GVICK(allow_lds(c, (const void*)moments_generic_kernel, (int)GENERIC_LDS_LIMIT));
       hipLaunchKernelGGL(moments_generic_kernel, p.grid, dim3(GEN_BS), p.lds, st, a);
       break;
     case Route::Readout:
@@ -1819,8 +1818,7 @@ static gvi_status ngd_prep_all(gvi_ctx* ctx, int i) {
   }
   if (L.nsets == 0) return GVI_OK;
   const unsigned extra = take_gather(ctx, i, L, 64);
-  const int dp = dmax + (dmax & 1);
-  const size_t lds = (size_t)(4 * dmax * dmax + 2 * dp + 3 * dmax + (dp + 1) / 2 + 1 + dmax * dmax + dmax) * 8 + 16;
+  const size_t lds = prep_all_lds_bytes(dmax);
   const dim3 grid(L.koff[L.nsets] + extra);
   if (grid.x == 0) return GVI_OK;                                     // only empty shards
   if (dmax > 32) return fail(ctx, GVI_ERR_UNSUPPORTED, "factor dimension > 32");
@@ -1862,7 +1860,7 @@ static EpiList make_epi_list(gvi_ctx* ctx, int full, const MomPlan* P, int* dmax
 static gvi_status ngd_epilogue_all(gvi_ctx* ctx, int full, const MomPlan* P, int publish_slot = -1) {
   int dmax = 0;
   const EpiList L = make_epi_list(ctx, full, P, &dmax);
-  const size_t lds = (epilogue_lds_doubles(dmax) + 256) * 8;       // + the tail's 256-leaf tree
+  const size_t lds = epilogue_all_lds_doubles(dmax) * 8;
   if (L.koff[L.nsets] == 0) return GVI_OK;
   EpiTail tail;
   GVICK(fill_epi_tail(ctx, L.koff[L.nsets], publish_slot, &tail));
@@ -2979,7 +2977,7 @@ gvi_status gvi_prox_gradients(gvi_ctx* ctx, double h) {
     JkoArgs a;
     a.K = s.K; a.d = s.d; a.h = h; a.Vdmu = s.Vdmu.d(); a.Vddmu = s.Vddmu.d(); a.Sigma = s.Sigma_k[g.cur].d();
     a.Lam = s.Lam.d(); a.Shalf = s.jko_half.d(); a.LamNew = s.jko_Lam.d();
-    hipLaunchKernelGGL(jko_half_kernel, dim3(s.K), dim3(64), 3 * dd * 8, ctx->stream, a);
+    hipLaunchKernelGGL(jko_half_kernel, dim3(s.K), dim3(64), jko_half_lds_bytes(s.d), ctx->stream, a);
     FactorDev f = s.dev(ctx->opt);                         // spectral map of Sig_half into scratch (no psi operands)
     f.m = 0; f.S = s.jko_S.d(); f.Sinv = s.jko_Sinv.d(); f.Lam = s.jko_Lam.d(); f.H = nullptr; f.Hq = nullptr; f.u0 = nullptr;
     f.jko_h = h;

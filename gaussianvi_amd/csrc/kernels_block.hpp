@@ -65,16 +65,18 @@ __device__ __forceinline__ void block_products_of(const FactorDev& f, const doub
   else prep_body<1, 0>(f, mu, Sigma, k, sm, kin);
 }
 
-// phase 1 of one factor by the calling wave (DT = the set's d): prep_all_kernel's block, verbatim
+// phase 1 of one factor by the calling wave (DT = the set's d): prep_all_kernel's block with d at compile time (one shared
+// function for the two was tried: it changes the machine code of both kernels)
 template <int DT, bool CHOL>
 __device__ __forceinline__ void block_products(const Block3Args& A, const BlockSet& S, const int k, double* sm) {
   const FactorDev& f = S.a.f;
   const int lane = threadIdx.x & 63;
   if (!A.gather) { block_products_of<DT, CHOL>(f, S.a.mu, S.Sigma_k, k, sm, k); return; }
-  constexpr int d = DT, dd = d * d, dp = d + (d & 1);
+  constexpr int d = DT, dd = d * d;
+  constexpr ProductsLds P{DT};             // the gather staging behind the products area (factor_lds.hpp)
   const int n = A.n, nn = n * n;
-  double* Sl = sm + 4 * dd + 2 * dp + 3 * d + (dp + 1) / 2 + 1;  // behind the products' own LDS
-  double* ml = Sl + dd;
+  double* Sl = sm + P.Sl();
+  double* ml = sm + P.ml();
   const int s = S.start[k];
   for (int e = lane; e < dd; e += 64) {
     const int r = e / d, c = e % d;
@@ -118,13 +120,7 @@ __device__ __forceinline__ void block_epilogue(const Block3Args& A, const BlockS
 // outstanding stores (vmcnt) on gfx950.  (tests/test_handover_isa.py checks the wait in the built code object.)
 __device__ __forceinline__ void block_products_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-// LDS of one wave's phases 1 and 3 (doubles), d <= 8; a workgroup has four of them
-__host__ __device__ inline size_t block3_lds_doubles() {
-  constexpr size_t d = 8, dd = 64, dp = 8;
-  const size_t prep = 4 * dd + 2 * dp + 3 * d + (dp + 1) / 2 + 1 + dd + d + 2;
-  const size_t epi = epilogue_lds_doubles((int)d) + 2;
-  return ((prep > epi ? prep : epi) + 1) & ~(size_t)1;
-}
+// LDS of one wave's phases 1 and 3, d <= 8: block3_lds_doubles() (factor_lds.hpp); a workgroup has four of them
 // workgroups of a set: G = 4 / nch factors each (nch = 1, 2 or 4 waves per factor)
 __host__ __device__ inline int block3_nch(int nchunk) { return nchunk == 3 ? 4 : nchunk; }
 __host__ __device__ inline int block3_blocks(int K, int nchunk) { const int G = 4 / block3_nch(nchunk); return (K + G - 1) / G; }

@@ -38,6 +38,7 @@
 #include "device_common.hpp"
 #include "dpp_rowb.hpp"
 #include "factor_dev.hpp"
+#include "factor_lds.hpp"
 #include "psi_point.hpp"
 
 namespace gvi {
@@ -71,15 +72,16 @@ template <int EPLP, int DT>   // EPLP: elements of the d x d block per lane: 1 (
 // marginal in LDS); outputs always go to slot k
 __device__ __forceinline__ void prep_body(const FactorDev& f, const double* mu, const double* Sigma, int k, double* sm, int kin) {
   const int d = DT ? DT : f.d, dd = d * d, lane = threadIdx.x & 63;      // one wave per factor (the fused kernel runs several per block)
-  const int dp = d + (d & 1);
-  double* A0 = sm;
-  double* A1 = A0 + dd;
-  double* V0 = A1 + dd;
-  double* V1 = V0 + dd;
-  double* al = V1 + dd;          // [dp]
-  double* be = al + dp;          // [dp]
-  double* lam = be + dp;         // [d] (3 functions of lambda: sqrt, 1/sqrt, 1/x)
-  int* pa = (int*)(lam + 3 * d); // [dp]
+  const ProductsLds L{d};        // the Jacobi view of the products area, region by region (factor_lds.hpp)
+  const int dp = L.dp();
+  double* A0 = sm + L.A0();
+  double* A1 = A0 + (L.A1() - L.A0());
+  double* V0 = A1 + (L.V0() - L.A1());
+  double* V1 = V0 + (L.V1() - L.V0());
+  double* al = V1 + (L.al() - L.V1());          // [dp]
+  double* be = al + (L.be() - L.al());          // [dp]
+  double* lam = be + (L.lam() - L.be());        // [d] (3 functions of lambda: sqrt, 1/sqrt, 1/x)
+  int* pa = (int*)(lam + (L.pa() - L.lam()));   // [dp]
   int ei[EPLP], ej[EPLP];        // (row, col) of this lane's elements, computed once (-1: none)
 #pragma unroll
   for (int q = 0; q < EPLP; ++q) {
@@ -353,8 +355,9 @@ __device__ inline void prep_chol_body(const FactorDev& f, const double* mu, cons
   const bool lean = Hs != nullptr;
   constexpr int d = DT, dd = DT * DT;
   const int lane = threadIdx.x & 63;      // one wave per factor (the fused kernel runs several per block)
-  double* Ll = sm;            // [d][d] L, zeros above the diagonal
-  double* Xl = Ll + dd;       // [d][d] X = L^-1
+  constexpr ProductsLds L{DT};           // the Cholesky view of the products area (factor_lds.hpp)
+  double* Ll = sm + L.Ll();   // [d][d] L, zeros above the diagonal
+  double* Xl = sm + L.Xl();   // [d][d] X = L^-1
   const double* Sg = Sigma + (size_t)kin * dd;
   static_assert(!ROWB || DT <= 16, "row-broadcast form: a row of L per lane of a 16-lane row");
   const int lr = ROWB ? (lane & 15) : lane;                  // ROWB: the four 16-lane rows of the wave are replicas
@@ -430,7 +433,7 @@ __device__ inline void prep_chol_body(const FactorDev& f, const double* mu, cons
     for (int c = 0; c < d; ++c) { Ll[lane * d + c] = row[c]; Xl[c * d + lane] = xcol[c]; }
   }
   // the prefetched rows of A also go to LDS (one copy per row: lanes e = r d hold row r), for u0 = b + A mu below
-  double* Al = Xl + dd;        // [m][d]
+  double* Al = sm + L.Al();    // [m][d]
   if (pre) {
 #pragma unroll
     for (int q = 0; q < HPL; ++q) {
@@ -563,8 +566,9 @@ __device__ inline void prep_chol_hu0(const FactorDev& f, const double* mul, cons
 template <int EPLP>
 __device__ inline void prep_chol_lds_body(const FactorDev& f, const double* mu, const double* Sigma, int k, double* sm, int kin, double* Zs) {
   const int d = f.d, dd = d * d, lane = threadIdx.x & 63;
-  double* Ll = sm;             // [d][d] row-major, zeros above the diagonal
-  double* Xl = Ll + dd;        // [d][d] X = L^-1 (row-major, lower triangular)
+  const ProductsLds L{d};      // the Cholesky view of the products area (factor_lds.hpp); Al stays unused
+  double* Ll = sm + L.Ll();    // [d][d] row-major, zeros above the diagonal
+  double* Xl = Ll + (L.Xl() - L.Ll());        // [d][d] X = L^-1 (row-major, lower triangular)
   const double* Sg = Sigma + (size_t)kin * dd;
   for (int e = lane; e < dd; e += 64) {
     const int i = e / d, j = e % d;
@@ -686,9 +690,10 @@ struct JkoArgs {
 __global__ __launch_bounds__(64) void jko_half_kernel(JkoArgs a) {
   extern __shared__ double sm[];
   const int d = a.d, dd = d * d, k = blockIdx.x, lane = threadIdx.x;
-  double* M = sm;            // I - h S
-  double* Sg = M + dd;
-  double* Tm = Sg + dd;      // M Sigma
+  const JkoLds L{d};         // region by region (factor_lds.hpp)
+  double* M = sm + L.M();                  // I - h S
+  double* Sg = M + (L.Sg() - L.M());
+  double* Tm = Sg + (L.Tm() - L.Sg());     // M Sigma
   for (int e = lane; e < dd; e += 64) {
     const int i = e / d, j = e % d;
     M[e] = (i == j ? 1.0 : 0.0) - a.h * a.Vddmu[(size_t)k * dd + e];
@@ -762,9 +767,10 @@ __global__ __launch_bounds__(64) void prep_all_kernel(PrepList L) {
   const int k = (int)blockIdx.x - L.koff[si];
   if (!L.gather) { prep_body_d<EPLP, ROWB>(L.f[si], L.mu[si], L.Sigma[si], k, sm, k); return; }
   const FactorDev& f = L.f[si];
-  const int d = f.d, dd = d * d, dp = d + (d & 1), n = L.n, nn = n * n;
-  double* Sl = sm + 4 * dd + 2 * dp + 3 * d + (dp + 1) / 2 + 1;  // behind prep_body's own LDS
-  double* ml = Sl + dd;
+  const int d = f.d, dd = d * d, n = L.n, nn = n * n;
+  const ProductsLds P{d};                  // the gather staging behind the products area (factor_lds.hpp)
+  double* Sl = sm + P.Sl();
+  double* ml = Sl + (P.ml() - P.Sl());
   const int s = L.start[si][k];
   for (int e = lane; e < dd; e += 64) {
     const int r = e / d, c = e % d;
@@ -860,8 +866,6 @@ __global__ __launch_bounds__(64) void moments_closed_kernel(MomArgs a) {
 // epilogue is shared.  Lane i takes coordinate i (erfc and exp once per finite side), S and (e1, e2) go through LDS
 // (d d + 2 d doubles of dynamic LDS), then lane j forms output j as a d-long sum in ascending i: deterministic.
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ inline size_t box_closed_lds_doubles(int d) { return (size_t)d * d + 2 * (size_t)d; }
-
 __global__ __launch_bounds__(64) void moments_box_closed_kernel(MomArgs a) {
   if (pred_skip(a.pred, a.pred_val)) return;
   extern __shared__ double bsm[];
@@ -925,7 +929,6 @@ __global__ __launch_bounds__(64) void moments_box_closed_kernel(MomArgs a) {
 // LDS: 64 d + 128 doubles per wave.
 // ---------------------------------------------------------------------------------------------
 __host__ __device__ inline int halfspace_group(int J) { int P = 1; while (P < J) P <<= 1; return P; }
-__host__ __device__ inline size_t halfspace_closed_lds_doubles(int d) { return 64 * (size_t)d + 128; }
 
 __global__ __launch_bounds__(256) void moments_halfspace_closed_kernel(MomArgs a) {
   if (pred_skip(a.pred, a.pred_val)) return;
@@ -974,7 +977,6 @@ __global__ __launch_bounds__(256) void moments_halfspace_closed_kernel(MomArgs a
   }
 }
 
-constexpr int GEN_BS = 256;
 constexpr int GEN_MAX_OUT = 3;   // outputs per thread: npairs(d) <= 768 -> d <= 37
 
 __global__ __launch_bounds__(GEN_BS) void moments_generic_kernel(MomArgs a) {
@@ -982,15 +984,16 @@ __global__ __launch_bounds__(GEN_BS) void moments_generic_kernel(MomArgs a) {
   extern __shared__ double sm[];
   const FactorDev& f = a.f;
   const int d = f.d, m = f.m, k = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
-  const int dz = d + 1;
-  double* zs = sm;                         // [256][dz]   z and the constant 1
-  double* xs = zs + GEN_BS * dz;           // [256][dz]   x = mu + S z
-  double* cs = xs + GEN_BS * dz;           // [256]
-  double* Ssh = cs + GEN_BS;               // [d][d]
-  double* mush = Ssh + d * d;              // [d]
-  double* Ash = mush + d;                  // [m][d]
-  double* bsh = Ash + m * d;               // [m]
-  double* gsh = bsh + m;                   // [m]
+  const GenericLds L{d, m};                // region by region (factor_lds.hpp)
+  const int dz = L.dz();
+  double* zs = sm + L.zs();                // [256][dz]   z and the constant 1
+  double* xs = zs + (L.xs() - L.zs());     // [256][dz]   x = mu + S z
+  double* cs = xs + (L.cs() - L.xs());     // [256]
+  double* Ssh = cs + (L.Ssh() - L.cs());   // [d][d]
+  double* mush = Ssh + (L.mush() - L.Ssh());   // [d]
+  double* Ash = mush + (L.Ash() - L.mush());   // [m][d]
+  double* bsh = Ash + (L.bsh() - L.Ash());     // [m]
+  double* gsh = bsh + (L.gsh() - L.bsh());     // [m]
   for (int e = tid; e < d * d; e += GEN_BS) Ssh[e] = f.S[(size_t)k * d * d + e];
   for (int e = tid; e < d; e += GEN_BS) mush[e] = a.mu[(size_t)k * d + e];
   for (int e = tid; e < m * d; e += GEN_BS) Ash[e] = f.A[(size_t)k * m * d + e];
@@ -1447,7 +1450,6 @@ __device__ __forceinline__ void split_reduce(const double* acc, double* rw, doub
 // tile transpose as split_reduce) and added, with Neumaier compensation, into a wave-private (sum, comp) pair per moment in
 // LDS; the registers restart from zero.  First level: 64 terms per lane; cross-lane: a tree; second level: compensated.
 constexpr int SPLIT_FLUSH = 64;
-constexpr int SPLIT_LVL2_SLOTS = 96;     // >= accumulators per wave (83 at D = 24)
 template <int NT>
 __device__ __forceinline__ void split_flush(double* acc, double* rw, double* s2, double* c2, int lane) {
   constexpr int NB = (NT + 15) / 16;
@@ -1629,8 +1631,6 @@ __device__ __forceinline__ void split_cost_body(const MomArgs& a, const int k, c
   __syncthreads();
   if (threadIdx.x == 0) a.partial[(size_t)k * a.nchunk + blockIdx.y] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-
-constexpr int SPLIT_LDS_DOUBLES(int D) { return 256 + 2 * D + 8 + 2 * 4 * 64 + 4 * 16 * 65 + 4 * 2 * SPLIT_LVL2_SLOTS; }
 
 template <int D, int R, bool FULL>
 __global__ __launch_bounds__(256, 2) void moments_split_kernel(MomArgs a) {
@@ -2174,9 +2174,6 @@ struct EpiArgs {
   double* E_xxphi;         // [K][d][d] or null
 };
 
-// LDS doubles of the epilogue: packed moments, M2, one product, and the factor's Sinv / Lam (or S) staged once
-__host__ __device__ inline size_t epilogue_lds_doubles(int d) { return (size_t)npairs(d) + 4 * (size_t)d * d; }
-
 // returns the factor's cost E[psi] / T_k (wave-uniform).
 // DT = d at compile time (inner products fully unrolled: their LDS loads pipeline) or 0 (any d).  The operands of the
 // back-transform (Sinv, Lam; S for the raw integrals) are fetched into LDS in one round trip at the top -- with the
@@ -2191,11 +2188,12 @@ __device__ __forceinline__ double epilogue_body_t(const EpiArgs& a, int k, doubl
   const FactorDev& f = a.f;
   const int d = DT ? DT : f.d, dd = d * d, lane = threadIdx.x & 63;      // one wave per factor (the fused kernel runs several per block)
   const int npo = a.full ? npairs(d) : 1;
-  double* Ms = sm;              // [npo]
-  double* M2 = Ms + npairs(d);  // [d][d]
-  double* Tm = M2 + dd;         // [d][d]
-  double* Sv = Zs ? Zs : Tm + dd;           // [d][d] Sinv
-  double* Lv = Tm + 2 * dd;                 // [d][d] Lam (unused when Zs)
+  const EpilogueLds L{d};       // the epilogue area, region by region (factor_lds.hpp)
+  double* Ms = sm + L.Ms();                     // [npo]
+  double* M2 = Ms + (L.M2() - L.Ms());          // [d][d]
+  double* Tm = M2 + (L.Tm() - L.M2());          // [d][d]
+  double* Sv = Zs ? Zs : Tm + (L.Sv() - L.Tm());    // [d][d] Sinv
+  double* Lv = Tm + (L.Lv() - L.Tm());          // [d][d] Lam (unused when Zs)
   const double Tk = f.temperature[k];                     // issued with the other loads, used after the chunk sums
   const bool want_v = a.full && (a.Vdmu || a.Vddmu);
   if (want_v && phase != 2 && !Zs) {

@@ -62,19 +62,14 @@ struct FusedArgs {
   CostList cl;
 };
 
-// LDS of one item's phase-1 / phase-3 work (doubles): prep area (+ gather staging) or epilogue area.  Item i works in the
-// walk region of wave i (dead outside phase 2).
-__host__ __device__ inline size_t fused_item_doubles(int d) {
-  const size_t dd = (size_t)d * d, dp = d + (d & 1);
-  const size_t prep = 4 * dd + 2 * dp + 3 * d + (dp + 1) / 2 + 1 + dd + d + 2;
-  const size_t epi = epilogue_lds_doubles(d) + 2;
-  return ((prep > epi ? prep : epi) + 1) & ~(size_t)1;
-}
+// LDS of one item's phase-1 / phase-3 work: the item area of factor_lds.hpp (products area + gather staging, or epilogue area).
+// Item i works in the walk region of wave i (dead outside phase 2).
 // per-wave region: the walk's H + accumulator copies, or the item area if that is larger
-__host__ __device__ inline size_t fused_region_doubles(int dmax, int M, int copies) {
-  const size_t a = (size_t)orbit_lds_doubles(dmax, M, copies), b = fused_item_doubles(dmax);
-  return ((a > b ? a : b) + 1) & ~(size_t)1;
+__host__ __device__ constexpr size_t fused_region_doubles(int dmax, int M, int copies) {
+  return fused_region_of((size_t)orbit_lds_doubles(dmax, M, copies), dmax);
 }
+static_assert(factor_lds_check::helper_ok(6, 12, fused_region_doubles(12, 6, 1)) && factor_lds_check::helper_ok(2, 4, fused_region_doubles(4, 2, 1)),
+              "the helper wave's [Al | mh] inside a region of both fused instances (routes.hpp) at copies = 1");
 // per item, outside the regions: S^-T (phase 3), the psi operands H (walk layout) and u0 (phases 1 -> 2)
 __host__ __device__ inline size_t fused_keep_doubles(int dmax, int M) {
   return (size_t)dmax * dmax + (size_t)dmax * orbit_hstride(M) + (size_t)(M + (M & 1));
@@ -212,7 +207,7 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
     const int k = b + (iw < c0 ? iw : iw - c0) * A.nblk;
     const FusedSet& S = A.s[si];
     const FactorDev& f = S.f;
-    const int d = f.d, dd = d * d, lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63;
     double* area = sm + (size_t)wave * region;
     double* Zs = Zbase + (size_t)iw * zs;
     int* flag = helped(iw) ? &l_ready[iw] : nullptr;
@@ -220,9 +215,9 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
       if (si == 0) prep_chol_body<D0>(f, S.mu, S.Sigma, k, area, k, Zs, Zs + oH, Zs + oU, orbit_hstride(M), flag);
       else prep_chol_body<D1>(f, S.mu, S.Sigma, k, area, k, Zs, Zs + oH, Zs + oU, orbit_hstride(M), flag);
     } else {
-      const int dp = d + (d & 1);
-      double* Sl = area + 4 * dd + 2 * dp + 3 * d + (dp + 1) / 2 + 1;   // behind prep_body's own LDS
-      double* ml = Sl + dd;
+      const ProductsLds P{f.d};
+      double* Sl = area + P.Sl();
+      double* ml = Sl + (P.ml() - P.Sl());
       if (si == 0 ? fused_gather<D0>(A, S, k, lane, Sl, ml, lpred) : fused_gather<D1>(A, S, k, lane, Sl, ml, lpred)) return;
       wave_lds_sync();
       if (si == 0) prep_chol_body<D0>(f, ml, Sl, k, area, 0, Zs, Zs + oH, Zs + oU, orbit_hstride(M), flag);
@@ -243,10 +238,10 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
         if ((((hw & 3) - (h0 >> 4)) & 3) == it) wi = w;
       }
     }
-    double* own = sm + (size_t)wave * region;
+    double* own = sm + (size_t)wave * region;                 // this wave's view of its own region: [Al | mh] (factor_lds.hpp)
     double* Zs = Zbase + (size_t)it * zs;
     // the item's mean, as its own wave gathers it (same expression: bit-identical u0)
-    double* mh = own + (size_t)S.f.m * d;
+    double* mh = own + HelperLds{d, S.f.m}.mh();
     if (lane < d) {
       double mval;
       if (A.gather) {
@@ -313,7 +308,7 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
     if (!A.tail.on || helpers) { epi(0); return; }
     const double costk = epi(1);
     FUSED_STAMP(5);
-    int* last = (int*)(area + epilogue_lds_doubles(d));
+    int* last = (int*)(area + EpilogueLds{d}.last());
     epi_tail_arrive(A.cl, A.tail, S.cost + k, costk, (int)(threadIdx.x & 63), (unsigned)(A.koff[si] + k), (unsigned)A.koff[A.nsets], last);
     FUSED_STAMP(6);
     epi(2);

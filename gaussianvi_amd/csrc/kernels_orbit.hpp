@@ -743,7 +743,7 @@ __device__ __forceinline__ double* orbit_out(const OrbitArgs& a, const int k, co
 }
 
 // LDS doubles per wave
-__host__ __device__ inline int orbit_lds_doubles(int d, int M, int copies) {
+__host__ __device__ constexpr int orbit_lds_doubles(int d, int M, int copies) {
   return (d * orbit_hstride(M) + copies * (d + 1) * (d + 2) / 2 + 1) & ~1;      // even: every wave's H stays 16-byte aligned
 }
 
