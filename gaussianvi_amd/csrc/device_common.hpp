@@ -163,5 +163,40 @@ template <> __device__ __forceinline__ void kernarg_warm<26>() {
                : "=&s"(w[0]), "=&s"(w[1]), "=&s"(w[2]), "=&s"(w[3]), "=&s"(w[4]), "=&s"(w[5]), "=&s"(w[6]), "=&s"(w[7]), "=&s"(w[8]), "=&s"(w[9]), "=&s"(w[10]), "=&s"(w[11]), "=&s"(w[12]), "=&s"(w[13]), "=&s"(w[14]), "=&s"(w[15]), "=&s"(w[16]), "=&s"(w[17]), "=&s"(w[18]), "=&s"(w[19]), "=&s"(w[20]), "=&s"(w[21]), "=&s"(w[22]), "=&s"(w[23]), "=&s"(w[24]), "=&s"(w[25])
                : "s"(__builtin_amdgcn_kernarg_segment_ptr()));
 }
+template <> __device__ __forceinline__ void kernarg_warm<28>() {
+  unsigned w[28];
+  asm volatile(
+               "s_load_dword %0, %28, 0x0\n"
+               "s_load_dword %1, %28, 0x40\n"
+               "s_load_dword %2, %28, 0x80\n"
+               "s_load_dword %3, %28, 0xc0\n"
+               "s_load_dword %4, %28, 0x100\n"
+               "s_load_dword %5, %28, 0x140\n"
+               "s_load_dword %6, %28, 0x180\n"
+               "s_load_dword %7, %28, 0x1c0\n"
+               "s_load_dword %8, %28, 0x200\n"
+               "s_load_dword %9, %28, 0x240\n"
+               "s_load_dword %10, %28, 0x280\n"
+               "s_load_dword %11, %28, 0x2c0\n"
+               "s_load_dword %12, %28, 0x300\n"
+               "s_load_dword %13, %28, 0x340\n"
+               "s_load_dword %14, %28, 0x380\n"
+               "s_load_dword %15, %28, 0x3c0\n"
+               "s_load_dword %16, %28, 0x400\n"
+               "s_load_dword %17, %28, 0x440\n"
+               "s_load_dword %18, %28, 0x480\n"
+               "s_load_dword %19, %28, 0x4c0\n"
+               "s_load_dword %20, %28, 0x500\n"
+               "s_load_dword %21, %28, 0x540\n"
+               "s_load_dword %22, %28, 0x580\n"
+               "s_load_dword %23, %28, 0x5c0\n"
+               "s_load_dword %24, %28, 0x600\n"
+               "s_load_dword %25, %28, 0x640\n"
+               "s_load_dword %26, %28, 0x680\n"
+               "s_load_dword %27, %28, 0x6c0\n"
+               "s_waitcnt lgkmcnt(0)"
+               : "=&s"(w[0]), "=&s"(w[1]), "=&s"(w[2]), "=&s"(w[3]), "=&s"(w[4]), "=&s"(w[5]), "=&s"(w[6]), "=&s"(w[7]), "=&s"(w[8]), "=&s"(w[9]), "=&s"(w[10]), "=&s"(w[11]), "=&s"(w[12]), "=&s"(w[13]), "=&s"(w[14]), "=&s"(w[15]), "=&s"(w[16]), "=&s"(w[17]), "=&s"(w[18]), "=&s"(w[19]), "=&s"(w[20]), "=&s"(w[21]), "=&s"(w[22]), "=&s"(w[23]), "=&s"(w[24]), "=&s"(w[25]), "=&s"(w[26]), "=&s"(w[27])
+               : "s"(__builtin_amdgcn_kernarg_segment_ptr()));
+}
 
 }  // namespace gvi

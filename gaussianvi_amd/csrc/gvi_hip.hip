@@ -73,6 +73,7 @@ struct Table {
   OrbitHost orb;
   DevMem orb_cpk, orb_rpk, orb_mag, orb_w, orb_tau2;
   std::map<int, std::unique_ptr<DevMem>> orb_bounds;   // nchunk -> [nchunk + 1] tile bounds
+  std::unique_ptr<WalkPrioSet> orb_walk_prio;          // costs of the four-chunk split (fused pass; made on first use)
 };
 
 struct FactorSet {
@@ -242,6 +243,9 @@ struct gvi_ctx {
   // kernels whose dynamic-LDS limit was raised on THIS context's device (the attribute is per device, and a
   // process may hold contexts on several devices)
   std::set<const void*> lds_attr_done;
+  // blocks of a fused instance the device holds at once, by (kernel, dynamic LDS): asked of the occupancy API once
+  // (fused_round_blocks)
+  std::map<std::pair<const void*, size_t>, int> fused_round;
   double seq = 0.0;
   // stage timing (gvi_profile_stages): event pairs around the chain launches / the factor pass / the assemble of the
   // resident iteration.  A pair costs ~14 us of queue gaps, so it is switched on for a few iterations OUTSIDE any timed region.
@@ -597,15 +601,43 @@ inline std::atomic<long long>* fused_launches() { static std::atomic<long long> 
 // kernel sees it.
 inline std::atomic<long long>& block3_launches() { static std::atomic<long long> c; return c; }
 
+// blocks of 256 threads of `kernel` with `lds` bytes of dynamic LDS that the context's device holds at once (one residency
+// round): blocks per CU by the occupancy API times the CUs; asked once per (kernel, lds) and context
+gvi_status fused_round_blocks(gvi_ctx* c, const void* kernel, size_t lds, int* out) {
+  const auto key = std::make_pair(kernel, lds);
+  auto it = c->fused_round.find(key);
+  if (it == c->fused_round.end()) {
+    int per_cu = 0, cus = 0;
+    HIPCK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds));
+    HIPCK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    it = c->fused_round.emplace(key, per_cu * cus).first;
+  }
+  *out = it->second;
+  return GVI_OK;
+}
+
 // the full pass of the resident iteration as one launch (kernels_fused.hpp)
 template <int M, int SMAX, int WAVES, int D0, int D1>
-gvi_status launch_fused_t(gvi_ctx* c, const FusedArgs& A, unsigned grid, size_t lds, int dmax, int copies, int items, hipEvent_t e0, hipEvent_t e1) {
-  if (lds > 64 * 1024) GVICK(allow_lds(c, (const void*)factor_fused_kernel<M, SMAX, WAVES, D0, D1>, (int)lds));
+gvi_status launch_fused_t(gvi_ctx* c, FusedArgs& A, unsigned grid, size_t lds, int dmax, int copies, int items, hipEvent_t e0, hipEvent_t e1) {
+  const void* const kernel = (const void*)factor_fused_kernel<M, SMAX, WAVES, D0, D1>;
+  if (lds > 64 * 1024) GVICK(allow_lds(c, kernel, (int)lds));
+  // the walk's priority bands only where the item blocks are all resident at once: on a longer grid the blocks of a CU are
+  // of different ages anyway, and the staggered finish is what hands the next block its slot
+  if (A.walk_prio) {
+    int round = 0;
+    GVICK(fused_round_blocks(c, kernel, lds, &round));
+    if (A.nblk > round) A.walk_prio = 0;
+  }
 #ifdef GVI_FUSED_TIMING
   const int dbg = getenv("GVI_FUSED_DBG") ? atoi(getenv("GVI_FUSED_DBG")) : 0;
   static unsigned long long* stamps = nullptr;
   static int nprint = 0;
-  if ((dbg & 8) && !stamps) { if (hipMalloc(&stamps, 1120 * 8) != hipSuccess) stamps = nullptr; else (void)hipMemset(stamps, 0, 1120 * 8); }
+  constexpr size_t nstamps = 1120 + 5 * FUSED_BLOCK_STAMPS;
+  if ((dbg & 8) && !stamps) {
+    if (hipMalloc(&stamps, nstamps * 8) != hipSuccess) stamps = nullptr; else (void)hipMemset(stamps, 0, nstamps * 8);
+    const int exp = (dbg >> 4) & 7;                           // bit 0: phase-1 priority, bits 1-2: band cuts (kernels_fused.hpp)
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(gvi_fused_exp), &exp, sizeof(exp));
+  }
 #else
   const int dbg = 0;
   unsigned long long* stamps = nullptr;
@@ -642,6 +674,47 @@ gvi_status launch_fused_t(gvi_ctx* c, const FusedArgs& A, unsigned grid, size_t 
         for (int i = 0; i < 8; ++i) fprintf(stderr, " %.2f", h[blk * 32 + w * 8 + i] ? (double)(long long)(h[blk * 32 + w * 8 + i] - t0) * 0.01 : -1.0);
         fprintf(stderr, "\n");
       }
+    // every item block, grouped by CU: the residency slots of one CU against each other
+    std::vector<unsigned long long> hb(5 * (size_t)FUSED_BLOCK_STAMPS);
+    (void)hipMemcpy(hb.data(), stamps + 1120, hb.size() * 8, hipMemcpyDeviceToHost);
+    struct Blk { int b; double start, p2, bar, end; unsigned slot; };
+    std::map<unsigned, std::vector<Blk>> cus;                 // (xcc, se, cu) -> its blocks
+    unsigned long long tb0 = ~0ull;
+    for (int b = 0; b < A.nblk && b < FUSED_BLOCK_STAMPS; ++b) if (hb[(size_t)b * 5] && hb[(size_t)b * 5] < tb0) tb0 = hb[(size_t)b * 5];
+    for (int b = 0; b < A.nblk && b < FUSED_BLOCK_STAMPS; ++b) {
+      const unsigned long long* q = hb.data() + (size_t)b * 5;
+      if (!q[0] || !q[2]) continue;
+      const unsigned hw = (unsigned)q[3], xcc = (unsigned)(q[3] >> 32) & 15;
+      auto us = [&](unsigned long long t) { return (double)(long long)(t - tb0) * 0.01; };
+      cus[(xcc << 8) | ((hw >> 8) & 255)].push_back({b, us(q[0]), us(q[1]), us(q[2]), us(q[4]), hw & 15});   // (HW_ID bits 15:8: se_id, sh_id, cu_id)
+    }
+    std::vector<double> spread_bar, spread_end, first_bar, last_bar, walk_first, walk_last;
+    int shown = 0;
+    for (auto& [id, v] : cus) {
+      std::sort(v.begin(), v.end(), [](const Blk& a, const Blk& b) { return a.bar < b.bar; });
+      double e0 = 1e300, e1 = -1e300;
+      for (const Blk& x : v) { e0 = std::min(e0, x.end); e1 = std::max(e1, x.end); }
+      if (v.size() == 4) {
+        spread_bar.push_back(v.back().bar - v.front().bar); spread_end.push_back(e1 - e0);
+        first_bar.push_back(v.front().bar); last_bar.push_back(v.back().bar);
+        walk_first.push_back(v.front().bar - v.front().start); walk_last.push_back(v.back().bar - v.back().start);
+      }
+      if (shown++ < 6)
+        for (const Blk& x : v)
+          fprintf(stderr, "[cu stamps] xcc %u se %u cu %2u: block %4d slot %2u, us after the first walk start: walk start %.2f, wave 0 ends phase 2 %.2f, "
+                  "behind the barrier %.2f, last exit %.2f\n", id >> 8, (id >> 5) & 7, id & 31, x.b, x.slot, x.start, x.p2, x.bar, x.end);
+    }
+    auto stat = [](std::vector<double> v, double* med, double* mx) {
+      std::sort(v.begin(), v.end());
+      *med = v.empty() ? 0.0 : v[v.size() / 2]; *mx = v.empty() ? 0.0 : v.back();
+    };
+    double m[6], x[6];
+    stat(spread_bar, &m[0], &x[0]); stat(spread_end, &m[1], &x[1]); stat(first_bar, &m[2], &x[2]); stat(last_bar, &m[3], &x[3]);
+    stat(walk_first, &m[4], &x[4]); stat(walk_last, &m[5], &x[5]);
+    fprintf(stderr, "[cu summary] walk_prio %d, %zu CUs with four stamped blocks (of %zu): end of phase 2 (behind the barrier), first-to-last block of a CU: "
+            "median %.2f max %.2f us; first block at median %.2f, last at median %.2f max %.2f us; walk (start to barrier) of the first block median %.2f, "
+            "of the last median %.2f max %.2f us; last exit, first-to-last: median %.2f max %.2f us\n", A.walk_prio, spread_bar.size(), cus.size(),
+            m[0], x[0], m[2], m[3], x[3], m[4], m[5], x[5], m[1], x[1]);
   }
 #endif
   return GVI_OK;
@@ -2334,7 +2407,11 @@ static gvi_status ngd_fused_full(gvi_ctx* ctx, int slot, int publish_slot, const
     A.cl.cost[si] = s.cost.d(); A.cl.K[si] = s.K;
     dmax = std::max(dmax, s.d);
     copies = std::max(copies, F.oa.copies);
+    Table& t = *s.table;                   // the walk's priority bands: costs of the table's four chunks, made once
+    if (!t.orb_walk_prio) t.orb_walk_prio = std::make_unique<WalkPrioSet>(walk_prio_costs(t.orb, orbit_chunk_bounds(t.orb, fused_chunks)));
+    A.wp[si] = *t.orb_walk_prio;
   }
+  A.walk_prio = ctx->opt.walk_prio ? 1 : 0;   // (launch_fused_t: only where the item blocks fit one residency round)
   // (the walk regions are sized for the widest set with the most accumulator copies: an upper bound for every set)
   const int items = 1 + (A.nsets > 1 ? (ctx->sets[1]->K + A.nblk - 1) / A.nblk : 0);      // most items of a block
   const size_t lds = fused_lds_doubles(dmax, key.m, copies, items) * 8;

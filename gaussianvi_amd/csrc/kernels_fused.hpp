@@ -28,6 +28,10 @@
 namespace gvi {
 
 constexpr int FUSED_MAX_ITEMS = 4;
+constexpr int FUSED_BLOCK_STAMPS = 1100;        // timing build: blocks that leave their per-block stamps (five words each)
+#ifdef GVI_FUSED_TIMING
+__device__ int gvi_fused_exp;                   // experiments of the timing build, from GVI_FUSED_DBG (launch_fused_t)
+#endif
 
 struct FusedSet {
   FactorDev f;
@@ -60,6 +64,10 @@ struct FusedArgs {
   int64_t nmu;
   EpiTail tail;
   CostList cl;
+  // progress-banded priority of the walk (walk_prio.hpp): off (0) where the item blocks need more than one residency round,
+  // where staggered finishing is what keeps the CUs fed.  wp[s]: the costs of set s's table at four chunks
+  int walk_prio;
+  WalkPrioSet wp[2];
 };
 
 // LDS of one item's phase-1 / phase-3 work: the item area of factor_lds.hpp (products area + gather staging, or epilogue area).
@@ -136,6 +144,19 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
 #endif
 #ifdef GVI_FUSED_TIMING
   if (blockIdx.x == 0 && threadIdx.x == 0) { gvi_prep_stamps = stamps ? stamps + 8 * 32 : nullptr; gvi_walk_stamps = stamps ? stamps + 352 : nullptr; }
+  // EVERY block (the sampled eight never share a CU): behind the sampled stamps, [walk start | end of phase 2 | behind its barrier
+  // | HW_ID + XCC_ID] of wave 0 and the latest exit of any of the block's waves -- what the residency slots of one CU are
+  // compared by (profiles/r08_walk_prio.txt)
+  unsigned long long* const bstamps = stamps && blockIdx.x < FUSED_BLOCK_STAMPS ? stamps + 1120 + blockIdx.x * 5 : nullptr;
+#define FUSED_BLOCK_STAMP(i) do { if (bstamps && threadIdx.x == 0) bstamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
+  struct ExitStamp {
+    unsigned long long* p;
+    __device__ ~ExitStamp() { if (p && (threadIdx.x & 63) == 0) atomicMax(p, (unsigned long long)__builtin_amdgcn_s_memrealtime()); }
+  } exit_stamp{bstamps ? bstamps + 4 : nullptr};
+  if (bstamps && threadIdx.x == 0)
+    bstamps[3] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
+#else
+#define FUSED_BLOCK_STAMP(i) do { } while (0)
 #endif
   FUSED_STAMP(0);
 #ifdef GVI_FUSED_TIMING
@@ -148,9 +169,9 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
   // its first load of data (stamps of the timing build)
   const double* const pred_p = A.tail.pred;
   const int nblk_ = A.nblk, K0 = A.s[0].f.K, K1_ = A.s[1].f.K, nsets_ = A.nsets;
-  // ... behind one pass over every line of the (1.6 KB) argument block (kernarg_warm)
+  // ... behind one pass over every line of the (1.7 KB) argument block (kernarg_warm)
   constexpr int KA_LINES = (sizeof(FusedArgs) + 3 * 8 + 63) / 64;
-  static_assert(KA_LINES == 26, "kernarg_warm: one specialisation per argument block size");
+  static_assert(KA_LINES == 28, "kernarg_warm: one specialisation per argument block size");
   kernarg_warm<KA_LINES>();
   PREP_STAMP(11);
   asm volatile("" :: "s"(pred_p), "s"(nblk_), "s"(K0), "s"(K1_), "s"(nsets_));
@@ -202,6 +223,12 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
     const FactorDev& f = A.s[it < c0 ? 0 : 1].f;
     return it < nhelp && f.m > 0 && f.m * f.d <= 128;
   };
+#ifdef GVI_FUSED_TIMING
+  // experiment of the timing build (GVI_FUSED_DBG & 16): the wave of item 0 -- the d = 12 item, the block's critical path
+  // through this phase -- at priority 3, the other item wave and the helpers at 0
+  const bool p1prio = (__builtin_amdgcn_readfirstlane(gvi_fused_exp) & 1) != 0;
+  if (p1prio && iw == 0) __builtin_amdgcn_s_setprio(3);
+#endif
   if (iw < nitems) {
     const int si = iw < c0 ? 0 : 1;
     const int k = b + (iw < c0 ? iw : iw - c0) * A.nblk;
@@ -255,22 +282,46 @@ __global__ __launch_bounds__(256, WAVES) void factor_fused_kernel(FusedArgs A, i
       else prep_chol_hu0<D1>(S.f, mh, k, own, sm + (size_t)wi * region, &l_ready[it], Zs + oH, Zs + oU, orbit_hstride(M));
     }
   }
+#ifdef GVI_FUSED_TIMING
+  if (p1prio) __builtin_amdgcn_s_setprio(0);
+#endif
   FUSED_STAMP(1);
   if (pred_fail(lpred)) return;                                // (waves without an item, and the route without the gather)
   __syncthreads();                                             // S^-T / H / u0 of the items are in LDS
   FUSED_STAMP(2);
+  FUSED_BLOCK_STAMP(0);
   // ---- phase 2: every wave walks its chunk of the orbit table, item after item ----
+  // The wave's priority follows the share of its modelled walk cost, over all items, that is still ahead of it (walk_prio.hpp):
+  // the four blocks of a CU then reach the end of the walk together instead of oldest first.  Switched off, the total is 0
+  // and every band is priority 0.
+  WalkPrioRun pr;
+  pr.rem = __builtin_amdgcn_readfirstlane(A.walk_prio ? c0 * A.wp[0].total[wave] + c1 * A.wp[1].total[wave] : 0);
+  pr.cut = walk_prio_cuts(pr.rem);
+#ifdef GVI_FUSED_TIMING
+  // experiments of the timing build (GVI_FUSED_DBG bits 32 and 64): other cuts.  1: linear bands (3/4, 1/2, 1/4 of the
+  // total), 2: 5/8, 3/8, 3/16, 3: every geometric cut at half its place (1/4, 1/8, 1/16: a shorter last band)
+  {
+    const int cuts = (__builtin_amdgcn_readfirstlane(gvi_fused_exp) >> 1) & 3, t8 = pr.rem >> 3, t16 = pr.rem >> 4;
+    if (cuts == 1) pr.cut = {6 * t8, 4 * t8, 2 * t8};
+    else if (cuts == 2) pr.cut = {5 * t8, 3 * t8, 3 * t16};
+    else if (cuts == 3) pr.cut = walk_prio_cuts(pr.rem >> 1);
+  }
+#endif
   for (int it = 0; it < nitems; ++it) {
     const int si = it < c0 ? 0 : 1;
     const int k = b + (it < c0 ? it : it - c0) * A.nblk;
     const FusedSet& S = A.s[si];
     const double* Zi = Zbase + (size_t)it * zs;
-    orbit_wave<M, SMAX, true, false, true>(S.oa, k, wave, sm + (size_t)wave * region, Pbase + (size_t)it * ps + (size_t)wave * npairs(S.f.d),
-                                           Zi + oH, Zi + oU);
+    pr.tile = A.wp[si].tile;
+    orbit_wave<M, SMAX, true, false, true, true>(S.oa, k, wave, sm + (size_t)wave * region, Pbase + (size_t)it * ps + (size_t)wave * npairs(S.f.d),
+                                                 Zi + oH, Zi + oU, &pr);
   }
+  __builtin_amdgcn_s_setprio(0);                                // (a wave without a tile never asked; phase 3 and the tail run at 0)
   FUSED_STAMP(3);
+  FUSED_BLOCK_STAMP(1);
   __syncthreads();
   FUSED_STAMP(4);
+  FUSED_BLOCK_STAMP(2);
   // ---- phase 3: the item's wave: ordered chunk sum, cost (+ tail), back-transform ----
   // A block with at most two items has two idle waves here: wave (item + 2) runs the item's tail protocol (the cost needs only
   // the m0 entries of the four chunks: same ordered sum, same division as the item's wave) while the item's wave goes straight

@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "kernels_factor.hpp"
+#include "walk_prio.hpp"
 
 namespace gvi {
 
@@ -79,6 +80,17 @@ __device__ __forceinline__ void orbit_load(const OrbitDev& ob, const uint32_t bo
   for (int j = 0; j < S; ++j) r.mg[j] = orbit_ld(ob.mag + (size_t)j * ob.norb_p, boff);
 }
 struct OrbitNoPre { __device__ __forceinline__ void operator()() const {} };
+
+// Progress-banded priority of a walking wave (walk_prio.hpp; factor_fused_kernel alone turns it on).  rem: modelled cost of
+// the tiles this wave still has to walk, over all items of its block; everything here is wave-uniform and lives in SGPRs.
+// s_setprio takes an immediate and ignores EXEC: four constant calls behind scalar branches.
+struct WalkPrioRun { int rem; WalkPrioCuts cut; const int32_t* tile; };
+__device__ __forceinline__ void walk_prio_apply(const WalkPrioRun& p) {
+  if (p.rem > p.cut.c3) __builtin_amdgcn_s_setprio(3);
+  else if (p.rem > p.cut.c2) __builtin_amdgcn_s_setprio(2);
+  else if (p.rem > p.cut.c1) __builtin_amdgcn_s_setprio(1);
+  else __builtin_amdgcn_s_setprio(0);
+}
 
 // 64-bit DPP move (two 32-bit halves): cross-lane sums without the LDS pipe -- __shfl_xor is ds_bpermute, which queues
 // behind the wave's own and the other waves' accumulator atomics
@@ -486,15 +498,18 @@ __device__ __forceinline__ void orbit_load_wm(const OrbitDev& ob, const uint32_t
 // registers, sums their scaled sign-weighted sums in registers and adds the result to the accumulators once -- G times
 // fewer LDS atomics and column reads than one orbit per lane.  The next orbit's weight and magnitudes are requested while
 // the current one is scaled into the sums.  Local tile tl of the class; t0, t1, tfirst wave-uniform.
-template <int M, int S, bool FULL, bool SIGNED>
+template <int M, int S, bool FULL, bool SIGNED, bool PRIO = false>
 __device__ __forceinline__ void orbit_class_grouped(const OrbitDev& ob, const int lc, const int t0, const int t1, const int tfirst,
                                                     const uint32_t lane8, const double* Hl, double* accl, const double (&sg)[M],
-                                                    const double k0, double& m0) {
+                                                    const double k0, double& m0, WalkPrioRun* pr = nullptr) {
   static_assert(M * S <= 36, "support-major classes keep the support's columns in registers");
   constexpr int NV = S + S * (S - 1) / 2;
   const int G = ob.cgrp[S];
   const uint32_t gstride8 = (uint32_t)ob.cstride[S] * 8u;
+  int tcost = 0;
+  if constexpr (PRIO) tcost = pr->tile[S];
   for (int t = t0; t < t1; ++t) {
+    if constexpr (PRIO) { walk_prio_apply(*pr); pr->rem -= tcost; }
     const uint32_t boff0 = ((uint32_t)ob.cbase[S] + (uint32_t)(t - tfirst) * 64u) * 8u + lane8;
     const uint64_t cpk = orbit_ld(ob.cpk, boff0), rpk = orbit_ld(ob.rpk, boff0);
     OrbitWm<S> cur;
@@ -564,10 +579,13 @@ constexpr int ORBIT_GROUP_SMAX = 3;
 // still has its accumulator adds to issue, so that their round trip overlaps the adds and the next tile's column reads.
 // t0, t1 are wave-uniform (SGPRs); lane8 = 8 * lane.  (Requesting the chunk's first tile ahead of orbit_wave's prologue was
 // tried: the record stays live through every class loop -- 14 registers, spills -- for no gain.)
-template <int M, int S, bool FULL, bool SIGNED>
+template <int M, int S, bool FULL, bool SIGNED, bool PRIO = false>
 __device__ __forceinline__ void orbit_class(const OrbitDev& ob, const int lc, const int t0, const int t1, const int tfirst, const uint32_t lane8,
-                                            const double* Hl, double* accl, const double (&sg)[M], const double k0, double& m0) {
+                                            const double* Hl, double* accl, const double (&sg)[M], const double k0, double& m0,
+                                            WalkPrioRun* pr = nullptr) {
   if (t0 >= t1) return;
+  int tcost = 0;
+  if constexpr (PRIO) tcost = pr->tile[S];
   // pipelined up to s = 3 only.  s >= 4: a tile is long enough (290 VALU instructions and more) for its own load latency
   // not to matter, and its walk leaves no 14 registers for the next tile's records
   constexpr bool PIPE = S <= 3;
@@ -575,6 +593,7 @@ __device__ __forceinline__ void orbit_class(const OrbitDev& ob, const int lc, co
   const uint32_t cb8 = ((uint32_t)ob.cbase[S] - (uint32_t)tfirst * 64u) * 8u + lane8;      // entry of (tile t, this lane) = cb8 + 512 t
   if constexpr (PIPE) orbit_load<S>(ob, cb8 + (uint32_t)t0 * 512u, cur);
   for (int t = t0; t < t1; ++t) {
+    if constexpr (PRIO) { walk_prio_apply(*pr); pr->rem -= tcost; }
     if constexpr (!PIPE) orbit_load<S>(ob, cb8 + (uint32_t)t * 512u, cur);
     const int tn = t + 1 < t1 ? t + 1 : t;                      // (the last tile requests itself again: no branch)
     // the next tile's records go straight into cur: by the time pre() runs the walk has consumed the current ones
@@ -601,9 +620,11 @@ __device__ __forceinline__ void orbit_class(const OrbitDev& ob, const int lc, co
 // this launch do not update)
 // Hpre / u0pre (LDS, optional): the psi operands of this factor as another wave of the block left them (column stride
 // orbit_hstride(M)); nothing is read from a.H / a.u0 then
-template <int M, int SMAX, bool FULL, bool SIGNED, bool FRESH = false>
+// PRIO (factor_fused_kernel): the wave sets its priority at every tile boundary from pr->rem (walk_prio_apply) and, behind the
+// item's last tile, once more -- with nothing left in the block that is priority 0, in front of the closing reduction
+template <int M, int SMAX, bool FULL, bool SIGNED, bool FRESH = false, bool PRIO = false>
 __device__ __forceinline__ void orbit_wave(const OrbitArgs& a, const int k, const int chunk, double* lds, double* out,
-                                           const double* Hpre = nullptr, const double* u0pre = nullptr) {
+                                           const double* Hpre = nullptr, const double* u0pre = nullptr, WalkPrioRun* pr = nullptr) {
   const OrbitDev& ob = a.ob;
   const int lane = threadIdx.x & 63, d = a.d;
 #ifdef GVI_FUSED_TIMING
@@ -661,8 +682,8 @@ __device__ __forceinline__ void orbit_wave(const OrbitArgs& a, const int k, cons
   {                                                                                                   \
     const int e_ = te < ob.cend[S_] ? te : ob.cend[S_];                                                \
     if (tcur < e_) {                                                                                  \
-      if constexpr (S_ <= ORBIT_GROUP_SMAX && M * S_ <= 36) orbit_class_grouped<M, S_, FULL, SIGNED>(ob, lc, tcur, e_, ob.cend[S_ + 1], lane8, Hl, accme, sg, k0, m0); \
-      else orbit_class<M, S_, FULL, SIGNED>(ob, lc, tcur, e_, ob.cend[S_ + 1], lane8, Hl, accme, sg, k0, m0);            \
+      if constexpr (S_ <= ORBIT_GROUP_SMAX && M * S_ <= 36) orbit_class_grouped<M, S_, FULL, SIGNED, PRIO>(ob, lc, tcur, e_, ob.cend[S_ + 1], lane8, Hl, accme, sg, k0, m0, pr); \
+      else orbit_class<M, S_, FULL, SIGNED, PRIO>(ob, lc, tcur, e_, ob.cend[S_ + 1], lane8, Hl, accme, sg, k0, m0, pr);  \
       ORBIT_CLASS_STAMP(S_, e_ - tcur); tcur = e_;                                                     \
     }                                                                                                 \
   }
@@ -676,6 +697,7 @@ __device__ __forceinline__ void orbit_wave(const OrbitArgs& a, const int k, cons
   ORBIT_RUN_CLASS(1)
 #undef ORBIT_RUN_CLASS
 #undef ORBIT_CLASS_STAMP
+  if constexpr (PRIO) walk_prio_apply(*pr);
   m0 = wave_sum_f64(m0);
   if (chunk == 0) m0 = fma(ob.w0, k0, m0);       // the origin: psi(0) = sum_r s_r u0_r^2
   wave_lds_sync();

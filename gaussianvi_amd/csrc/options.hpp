@@ -75,6 +75,9 @@ struct Options {
   bool safe_publish = false;          // checked publish + release / acquire arrival counters (device_common.hpp)
   bool sample_sweep = true;           // 0: the samplers and the multi-solve run the factorisation only (tools/*_bench.py)
   bool solve_lds = true;              // 0: the multi-solve sweep keeps its vectors in the output buffer whatever the size
+  // fused factor pass: a walking wave sets its priority from the share of its modelled walk cost still ahead of it
+  // (walk_prio.hpp), where the launch's item blocks fit one residency round; bit-identical (A/B inside one library)
+  bool walk_prio = true;
 };
 
 // how a row applies an integer value v
@@ -136,6 +139,12 @@ constexpr OptionRow OPTION_ROWS[] = {
   opt_clamp("orbit_copies", nullptr, &Options::orbit_copies, 1, 16),
   opt_flag("warm_start", nullptr, &Options::warm_start),
 };
+// Rows of the same kind, applied the same way, kept apart: tests/test_options_host.py holds the names and the environment
+// variables of OPTION_ROWS as closed lists, so a switch that joins later stands here and is checked by a host test of its own
+// (walk_prio: tests/test_walk_prio_host.py).  include/gvi_hip.h lists these rows under the table of OPTION_ROWS.
+constexpr OptionRow OPTION_ROWS_LATER[] = {
+  opt_flag("walk_prio", "GVI_WALK_PRIO", &Options::walk_prio),
+};
 
 // false and a text in *msg where the rule refuses the value
 inline bool option_apply(Options& o, const OptionRow& r, int v, std::string* msg) {
@@ -158,14 +167,19 @@ inline bool option_apply(Options& o, const OptionRow& r, int v, std::string* msg
 // gvi_ctx_create: every row with an environment name whose variable `lookup` finds (getenv, or a test's own function)
 template <class Lookup>
 void options_from_env(Options& o, Lookup&& lookup) {
-  for (const OptionRow& r : OPTION_ROWS)
+  const auto read = [&](const OptionRow& r) {
     if (r.env)
       if (const char* w = lookup(r.env)) option_apply(o, r, atoi(w), nullptr);
+  };
+  for (const OptionRow& r : OPTION_ROWS) read(r);
+  for (const OptionRow& r : OPTION_ROWS_LATER) read(r);
 }
 
 // gvi_set_option: the row named `name`; false and the text of the refusal in *msg
 inline bool option_set(Options& o, const char* name, int value, std::string* msg) {
   for (const OptionRow& r : OPTION_ROWS)
+    if (r.name && strcmp(r.name, name) == 0) return option_apply(o, r, value, msg);
+  for (const OptionRow& r : OPTION_ROWS_LATER)
     if (r.name && strcmp(r.name, name) == 0) return option_apply(o, r, value, msg);
   *msg = std::string("unknown option: ") + name;
   return false;

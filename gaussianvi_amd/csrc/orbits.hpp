@@ -13,6 +13,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "walk_prio.hpp"
+
 namespace gvi {
 
 constexpr int ORBIT_SMAX = 6;          // largest support the kernel is instantiated for (degree k <= 7)
@@ -257,6 +259,18 @@ inline std::vector<int32_t> orbit_chunk_bounds(const OrbitHost& o, int nchunk) {
   std::vector<int32_t> b;
   fill(hi, &b);
   return b;
+}
+
+// what the walk's priority bands (walk_prio.hpp) need of a table split into four chunks (bounds [5], orbit_chunk_bounds): the
+// modelled cost of a tile of every class -- all tiles of a class carry the same number of orbits per lane -- and every
+// chunk's total, in whole cycles of the same model
+inline WalkPrioSet walk_prio_costs(const OrbitHost& o, const std::vector<int32_t>& bounds) {
+  WalkPrioSet p{};
+  for (int s = 1; s <= o.smax && s <= ORBIT_SMAX; ++s)
+    if (o.count[s] > 0) p.tile[s] = (int32_t)orbit_tile_cost(s, o.cgrp[s]);
+  for (int w = 0; w < 4 && w + 1 < (int)bounds.size(); ++w)
+    for (int t = bounds[(size_t)w]; t < bounds[(size_t)w + 1]; ++t) p.total[w] += p.tile[o.tile_s[(size_t)t]];
+  return p;
 }
 
 }  // namespace gvi

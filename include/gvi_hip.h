@@ -660,6 +660,11 @@ gvi_status gvi_set_variant(gvi_ctx* ctx, int variant);
  * that form (it shortens their one-wave-per-item products phase; a library built with -DGVI_CHOL_READLANE takes v_readlane there:
  * the A/B leg of the fused route).  The option selects it for the three-launch route's prep launch too (an instance of its own),
  * where it measured slower than v_readlane: there it is the bitwise A/B of the two forms inside one library.
+ * walk_prio (default 1; environment GVI_WALK_PRIO; a row of options.hpp's second table, OPTION_ROWS_LATER, accepted by
+ * gvi_set_option like the names below): in the one-launch factor pass a walking wave sets its priority (s_setprio 3 .. 0) from
+ * the share of its modelled walk cost that is still ahead of it, so that the blocks of a CU end the walk together; applied
+ * only where the launch's item blocks are all resident at once (asked of the occupancy API), a kernel argument otherwise
+ * passed as 0.  What is computed does not depend on it: bit-identical.
  * Names: chol_rowb, split_flush, sreg_pipe, mirror, pair_fuse, fuse_gather, side_solve, warm_start, no_scost, target_waves,
  * orbit, fused, assemble_on_load, orbit_waves, orbit_min_tiles, orbit_copies, chol_sqrt, jacobi_tol_exp, pipeline, chain_wave, chain_merge, asm_dense, chain_pair,
  * trust_table_degree, safe_publish, sample_sweep, solve_lds. */
