@@ -72,11 +72,12 @@ def cr_factor(D, U):
     return R, GA, GB
 
 
-def cr_solve(D, U, B):
-    """The sweep of solve_sweep_kernel for B [R][T][n]: up (the survivor gathers), then down."""
+def cr_solve(D, U, B, factor=None):
+    """The sweep of solve_sweep_kernel for B [R][T][n]: up (the survivor gathers), then down.
+    factor: a cr_factor(D, U) computed before (it is not written to)."""
     T = D.shape[0]
     L = levels(T)
-    R, GA, GB = cr_factor(D, U)
+    R, GA, GB = cr_factor(D, U) if factor is None else factor
     Y = np.array(B, dtype=float)
     for l in range(L):
         step = 1 << l
