@@ -1,7 +1,7 @@
 // psi and clearance of GVI_PSI_HINGE_BALLS_2D / _3D (include/gvi_hip.h): a hinge on the exact signed
 // distance to a union of balls that move with constant velocities.  Plain C++17 that also compiles for the host
 // (tests/stubs/balls_check.cpp runs it under AddressSanitizer / UBSan); psi_point and hinge_psi_clearance of
-// psi_point.hpp call it, and PsiHingeBalls of kernels_factor.hpp is the register form of the same walk.
+// psi_point.hpp call it, and PsiHingeBalls of kernels_reg.hpp is the register form of the same walk.
 //
 // One factor's block p, P = 2 / 3, x its slice [d], J check points, BALLS_SLOTS = GVI_BALLS_MAX_M ball slots:
 //   p = [sigma, eps, r | J x ( W_j (P x d, row-major) | c_j (P) | tau_j ) | BALLS_SLOTS x ( o_m (P) | v_m (P) | R_m )]

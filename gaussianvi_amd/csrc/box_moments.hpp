@@ -1,6 +1,6 @@
 // Closed-form Gaussian moments of one side of the squared hinge of GVI_PSI_HINGE_BOX.  Plain C++ that
 // also compiles for the host (tests/stubs/box_side_on_cpu.cpp runs it under AddressSanitizer / UBSan); the kernels that call
-// it are in kernels_factor.hpp.
+// it are in kernels_closed.hpp (PsiBoxHinge of kernels_reg.hpp is the quadrature form).
 //
 // One coordinate x = m + sd z, z ~ N(0, 1), one side with threshold a:  h(x) = sigma max(0, sgn (x - a))^2, sgn = +1 for the
 // upper side (a = hi - eps), -1 for the lower one (a = lo + eps).  With t = sgn (m - a) / sd -- the distance of the mean INTO the

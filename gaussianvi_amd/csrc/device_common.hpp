@@ -4,6 +4,10 @@
 
 namespace gvi {
 
+// Factor sets of one problem: the capacity of every per-set list that travels as a kernel argument (SetList, AsmList, PrepList,
+// EpiList, CostList, SampleCostList)
+constexpr int MAX_SETS = 8;
+
 // One-wave workgroups (blockDim == 64): LDS operations of a wave execute in order, so a wave-level
 // "barrier" only has to drain the LDS queue and stop the compiler from moving memory operations
 // across it.  It does not wait for outstanding global loads / stores (vmcnt) -- and neither does __syncthreads() on

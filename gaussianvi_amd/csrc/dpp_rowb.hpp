@@ -1,5 +1,5 @@
 // 64-bit DPP row broadcast (gfx950: row_newbcast:n is the one DPP control of the 64-bit ALU), shared by the chain's
-// Gauss-Jordan (kernels_chain.hpp, gj_rowb) and the Cholesky products of the factor pass (kernels_factor.hpp, prep_chol_body).
+// Gauss-Jordan (kernels_chain.hpp, gj_rowb) and the Cholesky products of the factor pass (kernels_prep.hpp, prep_chol_body).
 #pragma once
 #include <hip/hip_runtime.h>
 

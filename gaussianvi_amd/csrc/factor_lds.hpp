@@ -1,4 +1,4 @@
-// The dynamic LDS of the factor stage: where every kernel of kernels_factor.hpp, kernels_fused.hpp and kernels_block.hpp that
+// The dynamic LDS of the factor stage: where every kernel of the stage headers (kernels_factor.hpp lists them), kernels_fused.hpp and kernels_block.hpp that
 // carves its LDS by hand puts its regions, and how many bytes its launch asks for.  A layout is a small value whose members are
 // offsets in doubles, each written as the region before it plus that region's length.  The kernel takes its pointers from the
 // layout and the launch its size, so a kernel's idea of its LDS and its launch's cannot drift apart.

@@ -1,6 +1,6 @@
 // Half-space and corridor limit factors (GVI_PSI_HINGE_HALFSPACE): psi, margin and the closed-form Gaussian
 // moments of one row.  Plain C++ that also compiles for the host (tests/stubs/halfspace_on_cpu.cpp runs it under AddressSanitizer /
-// UBSan); the kernels that call it are in kernels_factor.hpp.
+// UBSan); the kernels that call it are in kernels_closed.hpp.
 //
 // Parameter block of one factor, J rows on a slice of dimension d:  p = [sigma (J) | eps (J) | b (J) | A (J x d, row-major)]
 //   psi(x)    = sum_j sigma_j max(0, a_j^T x - (b_j - eps_j))^2

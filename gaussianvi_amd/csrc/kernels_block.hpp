@@ -21,8 +21,13 @@
 // (The tail protocol on a factor's idle second wave, as factor_fused_kernel runs it: every form tried made the compiler merge
 // call sites over a pointer into the argument block and copy the block to scratch -- see block_products_of; not kept.)
 #pragma once
+#include "device_common.hpp"
 #include "factor_dev.hpp"
-#include "kernels_factor.hpp"
+#include "factor_lds.hpp"
+#include "kernels_epilogue.hpp"
+#include "kernels_prep.hpp"
+#include "kernels_reg.hpp"
+#include "kernels_sreg.hpp"
 
 namespace gvi {
 

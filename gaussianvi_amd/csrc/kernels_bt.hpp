@@ -68,7 +68,6 @@ __global__ __launch_bounds__(256) void sub_kernel(int64_t n, const double* __res
 }
 
 // ---- fused glue of the resident NGD iteration (one launch each instead of one per set) ----
-constexpr int MAX_SETS = 8;
 struct SetDesc {
   int K, d;
   const int32_t* start;

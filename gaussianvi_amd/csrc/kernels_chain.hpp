@@ -832,7 +832,7 @@ __device__ __forceinline__ void marginal_node(double* sm, const int lane, const 
 // launch took exactly as long as the two launches it replaces (chain_bench, T = 1025, n = 6: 47.6 vs 47.4 us).  Instead the
 // producer stores what the consumers read WRITE-THROUGH at agent scope (st_out), every thread waits for its own stores
 // (s_waitcnt vmcnt(0)) in front of the barrier, and thread 0 stores the word; the consumers read those values -- and only
-// those -- with agent-scope loads (chain_ld) behind the word.  Same protocol as the epilogue's tail (kernels_factor.hpp,
+// those -- with agent-scope loads (chain_ld) behind the word.  Same protocol as the epilogue's tail (kernels_epilogue.hpp,
 // epi_tail).  The explicit wait is needed: __syncthreads() is a workgroup-scope release, which on gfx950 (outside
 // threadgroup-split mode) is s_waitcnt lgkmcnt(0) + s_barrier WITHOUT vmcnt(0) -- the word could overtake other waves'
 // data stores.  tests/test_handover_isa.py checks the order in the built code object.

@@ -2,7 +2,7 @@
 // back-transform, the full moments pass of the resident NGD iteration in a single launch.
 //
 // Replaces, for the sum-of-squares factor sets of a chain, the three launches prep_all_kernel -> moments_orbit_pair_kernel ->
-// epilogue_all_kernel (kernels_factor.hpp / kernels_orbit.hpp; reference: GVIFactorizedBase::update_*_from_joint,
+// epilogue_all_kernel (kernels_prep.hpp / kernels_orbit.hpp / kernels_epilogue.hpp; reference: GVIFactorizedBase::update_*_from_joint,
 // gvibase/GVIFactorizedBase.h:104-122; updateGH + calculate_partial_V, ngd/NGDFactorizedBaseGH.h:50-88).  The device
 // functions are the SAME ones those kernels call (prep_body_d, orbit_wave, epilogue_body_p, epi_tail_arrive): results are
 // bit-identical to the three-launch route with four chunks per factor.
@@ -23,7 +23,11 @@
 // Nothing of the per-pass products goes to memory: S^-T, H and u0 stay in LDS between the phases (the host marks the sets'
 // products as not resident; a later pass at the same state runs its own prep).
 #pragma once
+#include "device_common.hpp"
+#include "factor_lds.hpp"
+#include "kernels_epilogue.hpp"
 #include "kernels_orbit.hpp"
+#include "kernels_prep.hpp"
 
 namespace gvi {
 

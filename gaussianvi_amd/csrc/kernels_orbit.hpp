@@ -1,13 +1,13 @@
 // moments_orbit_kernel: the sum-of-squares psi kinds on the SIGN-ORBIT form of the sparse Gauss-Hermite table.
 //
-// The lane-per-point kernels (kernels_factor.hpp) treat a sigma point as a dense d-vector: at (12,5) they spend 72 FMAs on
+// The lane-per-point kernels (kernels_sreg.hpp) treat a sigma point as a dense d-vector: at (12,5) they spend 72 FMAs on
 // H z and 90 on c z z^T per evaluation although a point has at most FOUR non-zero coordinates, and every point is one of
 // 2^s sign images of the same magnitudes.  Here a lane owns a whole orbit (csrc/orbits.hpp: support c_0 < ... < c_{s-1},
 // magnitudes m_j, one weight w) of ONE factor (wave = factor x chunk of orbit tiles; the factor's H and its 91 moment
 // accumulators live in LDS):
 //   * only the s columns H[:, c_j] of the support are touched: they are read from LDS once per orbit;
 //   * the 2^s sign patterns are walked in Gray-code order, one coordinate flips per step:  v += +-2 m_j H[:, c_j]  (M FMAs);
-//   * only HALF the orbit is walked: for a +-pair the cross terms cancel (kernels_factor.hpp, sreg_pipe_body):
+//   * only HALF the orbit is walked: for a +-pair the cross terms cancel (kernels_sreg.hpp, sreg_pipe_body):
 //         psi(z) + psi(-z) = 2 (q + k0),  psi(z) - psi(-z) = 4 l,   q = sum_r s_r v_r^2,  l = sum_r (s_r u0_r) v_r,  v = H z;
 //   * within the orbit the EVEN moments are sign-weighted sums of q (Walsh sums):
 //         m0 += 2w sum(q + k0);   M2[c_i][c_j] += 2w m_i m_j sum sigma_i sigma_j (q + k0);
@@ -30,7 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels_factor.hpp"
+#include "device_common.hpp"
 #include "walk_prio.hpp"
 
 namespace gvi {

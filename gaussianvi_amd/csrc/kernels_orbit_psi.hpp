@@ -16,6 +16,8 @@
 // Output: the same packed chunk partials [m0 | m1[d] | upper triangle of M2] as every moments kernel, so prep (symmetric
 // root) and epilogue (back-transform) are the existing ones.
 #pragma once
+#include "device_common.hpp"
+#include "factor_dev.hpp"
 #include "kernels_orbit.hpp"
 #include "psi_point.hpp"
 

@@ -19,8 +19,8 @@
 #include <stdint.h>
 
 #include "device_common.hpp"
-#include "kernels_factor.hpp"
 #include "kernels_orbit.hpp"
+#include "mom_args.hpp"
 #include "psi_point.hpp"
 #include "readout_moments.hpp"
 

@@ -4,7 +4,7 @@
 //
 //   cost[s][k] = psi_k(x_s[start_k n .. start_k n + d)) / temperature_k        clr[s][k] = min_b sdf(p_b) - r_b
 //
-// sample_cost_kernel, ONE launch for every set of the list (block -> set through the block offsets, like PrepList):
+// sample_cost_kernel, ONE launch for every set of the list (block -> set through the block offsets, like PrepList of kernels_prep.hpp):
 //   sum-of-squares sets (QUAD_PRIOR / FIXED_PRIOR, closed-form sets included): psi = sum_r sgn_r (b_r + A_r x)^2.  A workgroup
 //     of four waves owns a tile of 4 G consecutive factors and walks a chunk of samples.  Lanes are (factor, residual row r) groups
 //     of P = 2^ceil(log2 m) lanes inside ONE wave, G = 64 / P factors per wave: a lane loads row r of A_k, b_r and sgn_r ONCE into
@@ -25,7 +25,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "kernels_factor.hpp"
+#include "device_common.hpp"   // MAX_SETS
+#include "factor_dev.hpp"
 #include "psi_point.hpp"
 
 namespace gvi {
@@ -38,14 +39,14 @@ constexpr int SCOST_TARGET_BLOCKS = 2048; // blocks a sum-of-squares set aims fo
 struct SampleCostList {
   int nsets, T, n, S;
   const double* X;                 // [S][T][n]
-  int boff[MAX_FSETS + 1];         // first block of set i
-  FactorDev f[MAX_FSETS];
-  const int32_t* start[MAX_FSETS];
-  int ftiles[MAX_FSETS];           // sum-of-squares sets: factor tiles; blocks = ftiles * ceil(S / schunk)
-  int schunk[MAX_FSETS];           //   samples per block
-  double* cost[MAX_FSETS];         // [S][ld_cost] at column 0 of the set, or null
-  double* clr[MAX_FSETS];          // [S][ld_clr], hinge kinds only, or null
-  int64_t ld_cost[MAX_FSETS], ld_clr[MAX_FSETS];
+  int boff[MAX_SETS + 1];         // first block of set i
+  FactorDev f[MAX_SETS];
+  const int32_t* start[MAX_SETS];
+  int ftiles[MAX_SETS];           // sum-of-squares sets: factor tiles; blocks = ftiles * ceil(S / schunk)
+  int schunk[MAX_SETS];           //   samples per block
+  double* cost[MAX_SETS];         // [S][ld_cost] at column 0 of the set, or null
+  double* clr[MAX_SETS];          // [S][ld_clr], hinge kinds only, or null
+  int64_t ld_cost[MAX_SETS], ld_clr[MAX_SETS];
 };
 static_assert(sizeof(SampleCostList) <= 4096, "kernel arguments");
 

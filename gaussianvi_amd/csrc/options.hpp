@@ -22,7 +22,7 @@ struct Options {
   int fuse_trial = 2;
   int target_waves = 2048;            // waves the lane-per-point kernels aim for over one set
   bool mirror = true;                 // 0: never pair z with -z (A/B; results agree to rounding)
-  int split_flush = 64;               // (SPLIT_FLUSH of kernels_factor.hpp) 0: plain recursive sums in the split kernel (A/B of the (24,7) rounding)
+  int split_flush = 64;               // (SPLIT_FLUSH of kernels_split.hpp) 0: plain recursive sums in the split kernel (A/B of the (24,7) rounding)
   bool sreg_pipe = true;              // 0: full pass on the compiler-scheduled body (A/B; bit-identical results)
   bool no_scost = false;              // 1: cost pass on the one-factor-per-wave kernel (A/B)
   // sum-of-squares sets on the sign-orbit kernel (kernels_orbit.hpp) when the table decomposes; 0: the lane-per-point
@@ -39,7 +39,7 @@ struct Options {
   // sum-of-squares sets: per-pass products from the Cholesky factor of the marginal instead of its symmetric square root
   // (same moments -- the quadrature is exact there -- without the Jacobi sweeps)
   bool chol_sqrt = true;
-  // the register Cholesky of the three-launch route's prep (prep_all_kernel) in its row-broadcast form (kernels_factor.hpp,
+  // the register Cholesky of the three-launch route's prep (prep_all_kernel) in its row-broadcast form (kernels_prep.hpp,
   // prep_chol_body<DT, ROWB>) instead of v_readlane; bit-identical (A/B inside one library), and slower in that launch
   // (profiles/r06_unit_top.txt section 4), hence off.  The fused pass takes the row-broadcast form unconditionally.
   bool chol_rowb = false;

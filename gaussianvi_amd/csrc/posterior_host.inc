@@ -24,7 +24,7 @@ static gvi_status scost_check_set(gvi_ctx* ctx, const FactorSet& s, bool clearan
 
 // every set of the context can be evaluated on the device (gvi_sample_costs / gvi_ngd_sample_costs)
 static gvi_status scost_check_all(gvi_ctx* ctx, int clearance_set) {
-  if ((int)ctx->sets.size() > MAX_FSETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
+  if ((int)ctx->sets.size() > MAX_SETS) return fail(ctx, GVI_ERR_UNSUPPORTED, "more than 8 factor sets");
   for (int i = 0; i < (int)ctx->sets.size(); ++i) GVICK(scost_check_set(ctx, *ctx->sets[i], i == clearance_set));
   return GVI_OK;
 }

@@ -1,4 +1,4 @@
-// What the obstacle kinds on linear read-outs (PSI_READOUT, psi_kinds.hpp) share -- the register policies of kernels_factor.hpp,
+// What the obstacle kinds on linear read-outs (PSI_READOUT, psi_kinds.hpp) share -- the register policies of kernels_reg.hpp,
 // the read-out-space rule of readout_moments.hpp, balls_psi.hpp: where check point j's W_j | c_j | tau_j sit in a factor's block,
 // the sums G = W S, g = W mu + c in ONE association, and the hinge.  Plain C++17 for host and device.  Every product that is
 // added goes through fma explicitly, so the host build and the device build round alike whatever the contraction setting.

@@ -14,7 +14,7 @@
 
 namespace gvi {
 
-// psi operand structs of the register kernels (kernels_factor.hpp defines them): the tags below only name them
+// psi operand structs of the register kernels (kernels_reg.hpp defines them): the tags below only name them
 template <int D, int M> struct PsiQuad;
 struct PsiRange1D;
 template <int D, int KIND> struct PsiHingeSdf;
@@ -69,7 +69,7 @@ bool with_reg_instance(int kind, int d, int m, F&& f) {
     case KIND_HINGE_SDF_3D_SEG:   // d = 12: 256 VGPRs + 18 AGPR copies under launch_bounds(256) -> generic kernel
       if (d == 6) return hit(f, RegInst<6, PsiHingeSeg<6, 3>>{});
       break;
-    // analytic balls: the policy is PsiHingeBalls<D, P> (kernels_factor.hpp), handed out under the tag of every hinge on a
+    // analytic balls: the policy is PsiHingeBalls<D, P> (kernels_reg.hpp), handed out under the tag of every hinge on a
     // signed distance, PsiHingeSdf<D, KIND>.  Every listed instance compiles without scratch or spills
     case KIND_HINGE_BALLS_2D:
       if (d == 2) return hit(f, RegInst<2, PsiHingeSdf<2, KIND_HINGE_BALLS_2D>>{});
@@ -445,7 +445,7 @@ inline Fuse decide_fuse(int nsets, const RouteFacts* s, const RouteDecision* p, 
 }
 
 // Cholesky factor instead of the symmetric root: sum-of-squares psi on a generated table of degree >= 3 (exact quadrature --
-// kernels_factor.hpp, prep_chol_body), the instantiated dimensions, and not when the caller is going to look at the sigma
+// kernels_prep.hpp, prep_chol_body), the instantiated dimensions, and not when the caller is going to look at the sigma
 // points themselves (force_sym: gvi_expand / gvi_moments_from_psi) or runs the JKO map
 inline bool chol_products(int kind, int d, int table_p, bool chol_sqrt, bool force_sym) {
   return chol_sqrt && !force_sym && psi_kind_is<PSI_SUMSQ>(kind) && table_p >= 3 && d <= 32;

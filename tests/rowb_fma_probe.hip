@@ -1,4 +1,4 @@
-// Test-only probe of the row-broadcast multiply-add of the Cholesky products (csrc/dpp_rowb.hpp, rowb_fma; kernels_factor.hpp,
+// Test-only probe of the row-broadcast multiply-add of the Cholesky products (csrc/dpp_rowb.hpp, rowb_fma; kernels_prep.hpp,
 // prep_chol_body), compiled and loaded by tests/test_rowb_fma_semantics_gpu.py:
 //     v_fmac_f64_dpp acc, src, -mul row_newbcast:n        acc += (src of lane n of the own 16-lane row) * (-mul)
 // with the destination a register of its own (not the broadcast operand, unlike the form tests/rowbcast_probe.hip pins) and

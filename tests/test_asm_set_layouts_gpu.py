@@ -78,7 +78,7 @@ from test_handover_fresh_gpu import far_at_every_node
 gpu = pytest.mark.gpu
 
 GVI_ERR_UNSUPPORTED = 3
-ASM_SPARSE_MAX, MAX_SETS = 4, 8                                   # kernels_chain.hpp, kernels_bt.hpp
+ASM_SPARSE_MAX, MAX_SETS = 4, 8                                   # kernels_chain.hpp, device_common.hpp
 ALL_ON = dict(asm_dense=1, assemble_on_load=1, chain_merge=1)
 
 

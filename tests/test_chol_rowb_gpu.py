@@ -1,4 +1,4 @@
-"""Option "chol_rowb": the register Cholesky of the per-pass products (kernels_factor.hpp, prep_chol_body) with DPP row-broadcast
+"""Option "chol_rowb": the register Cholesky of the per-pass products (kernels_prep.hpp, prep_chol_body) with DPP row-broadcast
 multipliers against its v_readlane form, through the prep launch of the three-launch route (option "fused" 0), which holds
 both forms as instances of its own.  Same products with the same signs: S = L, S^-T, Sigma^-1, H = A L and u0 must agree bit
 for bit; where a pivot is not positive the NaNs must sit in exactly the same entries and every other entry must still agree

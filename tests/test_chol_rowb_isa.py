@@ -1,4 +1,4 @@
-"""The row-broadcast form of the register Cholesky (kernels_factor.hpp, prep_chol_body<DT, ROWB>) is in the built gfx950 code
+"""The row-broadcast form of the register Cholesky (kernels_prep.hpp, prep_chol_body<DT, ROWB>) is in the built gfx950 code
 object where it belongs (CPU only: disassembles the in-tree library the way test_handover_isa.py does).
 
 A factorisation of dimension d has d (d - 1) / 2 trailing updates and its inverse as many: each is one v_fmac_f64_dpp with a

@@ -173,9 +173,7 @@ def test_the_layout_is_written_once():
         if name != "factor_lds.hpp":
             text = open(os.path.join(CSRC, name)).read()
             assert "(dp + 1) / 2" not in text and "4 * dd + 2 * dp" not in text, name
-    for name in ("kernels_factor.hpp", "kernels_fused.hpp", "kernels_block.hpp", "gvi_hip.hip"):
-        text = open(os.path.join(CSRC, name)).read()
-        assert "behind prep_body's own LDS" not in text, name
-        for word in ("size_t epilogue_lds_doubles", "size_t box_closed_lds_doubles", "size_t halfspace_closed_lds_doubles", "int SPLIT_LDS_DOUBLES",
-                     "size_t fused_item_doubles", "size_t block3_lds_doubles"):
-            assert word not in text, (name, word)
+            assert "behind prep_body's own LDS" not in text, name
+            for word in ("size_t epilogue_lds_doubles", "size_t box_closed_lds_doubles", "size_t halfspace_closed_lds_doubles", "int SPLIT_LDS_DOUBLES",
+                         "size_t fused_item_doubles", "size_t block3_lds_doubles"):
+                assert word not in text, (name, word)

@@ -1,4 +1,4 @@
-"""The per-factor spectral stage (kernels_factor.hpp: prep_body<EPLP, DT>, the one-wave cyclic Jacobi; jko_half_kernel /
+"""The per-factor spectral stage (kernels_prep.hpp: prep_body<EPLP, DT>, the one-wave cyclic Jacobi; jko_half_kernel /
 jko_finish_kernel around it) at every block size class and on the inputs where an eigen-solver goes wrong (-m gpu).
 
 Sizes D_ALL = 1..17, 20, 24, 28, 31, 32: every unrolled instance (2, 4, 6, 12), odd d -- the phantom rotation partner dp = d + 1
@@ -55,7 +55,7 @@ row) and two separate runs printed the same figures, so the margin is not a matt
 On the library of the commit before this module, the four rule-before-sets rows of test_rule_is_a_property_of_the_context
 fail (n = 2, 6; "rule-sets", "rule-chain_set-sets") and everything else passes.
 
-Sensitivity: four arithmetic-only edits to a scratch copy of kernels_factor.hpp, each run once on this module (124 tests):
+Sensitivity: four arithmetic-only edits to a scratch copy of the prep source (kernels_prep.hpp today), each run once on this module (124 tests):
   l + 2h for l + 4h in the JKO spectral function   all 117 JKO rows exceed (39 test_jko_map), test_prox_step_wide [9, 16], the six
                                                    test_rule_is_a_property_of_the_context (their prox half); nothing else
   jko_half_kernel forming I + h S                  the same 47 tests, all 117 JKO rows
