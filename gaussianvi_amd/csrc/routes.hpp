@@ -1,8 +1,8 @@
 // Route selection of the factor stage: which kernel a set's moments (full) or cost pass runs on, how the pass is cut into
 // chunks, and which launches of the resident iteration go out as one.  Everything here is arithmetic on a handful of facts
 // about a set, its table and the options: decide_route / decide_fuse / decide_full allocate nothing and call no HIP function,
-// so tests/test_routes_host.py runs them on the CPU (tests/stubs/routes_check.cpp, plain and sanitized builds).  gvi_hip.hip
-// binds a decision to buffers and kernel arguments (plan_moments) and launches it.  Plain C++17, no HIP.
+// so tests/test_routes_host.py runs them on the CPU (tests/stubs/routes_check.cpp, plain and sanitized builds).
+// launch_factor.inc binds a decision to buffers and kernel arguments (plan_moments) and launches it.  Plain C++17, no HIP.
 #pragma once
 #include <stdint.h>
 
@@ -38,6 +38,7 @@ struct ClosedSumsq {};
 struct ClosedBox {};
 struct ClosedHalfspace {};
 template <int P, int CLS> struct ReadoutInst {};   // CLS: READOUT_LEAD / _SEG / _BALLS, how the kind lays its read-outs out (psi_kinds.hpp)
+template <int EPLP> struct PrepInst {};            // EPLP: elements of the d x d block a lane holds (kernels_prep.hpp)
 constexpr auto any_instance = [](auto) {};
 template <class F, class Inst> bool hit(F& f, Inst inst) { f(inst); return true; }
 
@@ -204,6 +205,16 @@ bool with_readout_instance(int kind, F&& f) {
     case KIND_HINGE_BALLS_2D: return hit(f, ReadoutInst<2, READOUT_BALLS>{});
     case KIND_HINGE_BALLS_3D: return hit(f, ReadoutInst<3, READOUT_BALLS>{});
   }
+  return false;
+}
+
+// prep_kernel<EPLP>, prep_all_kernel<EPLP, ROWB> (kernels_prep.hpp): one wave per factor, so the d x d block of the widest
+// factor of the launch sets the elements per lane; any d <= 32
+template <class F>
+bool with_prep_instance(int d, F&& f) {
+  if (d <= 8) return hit(f, PrepInst<1>{});
+  if (d <= 16) return hit(f, PrepInst<4>{});
+  if (d <= 32) return hit(f, PrepInst<16>{});
   return false;
 }
 

@@ -15,6 +15,7 @@ SCOST = {QUAD: (12,), FIXED: (6,)}                                    # with_sco
 SPLIT_D = (16, 20, 24)                                                # with_split_instance: m = d and m = d / 2 -> 6
 ORBIT_M = (2, 6, 12, 14)                                              # with_orbit_instance (m = 2, 14: supports <= 4)
 OPSI_ROWS = {RANGE: 1, H2D: 2, BODY: 3, H3D: 3, ARM: 7}               # with_orbit_psi_instance: 5, orbit_psi_rows
+PREP = ((8, 1), (16, 4), (32, 16))                                    # with_prep_instance: (largest d, elements per lane)
 CODE = dict(orbit=6, opsi=7, sreg=2, scost=2, reg=2, split=3, generic=1)   # gvi_profile_geometry
 
 

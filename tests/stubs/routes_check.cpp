@@ -1,6 +1,7 @@
 // Stand-alone driver of gaussianvi_amd/csrc/routes.hpp for tests/test_routes_host.py (plain and -fsanitize=address,undefined
 // builds).  Reads one command per line from the file argv[1] and answers each with one line:
 //   reg KIND D M | sreg KIND D M | scost KIND D M | split D M | orbit M SMAX | opsi KIND | fused M SMAX D0 D1 | closed KIND
+//   | prep D
 //                                  -> NAME 0, or NAME 1 and the template arguments of the instance the list hands out
 //   variant V                      -> variant 0, or variant 1 and what the predicates say of the force: reg must_reg sgpr orbit opsi
 //   route KEY=VALUE...             -> route STATUS ROUTE NCHUNK CHUNK MCHUNK GX GY PIPE | REFUSAL
@@ -41,6 +42,7 @@ template <int M, int SMAX, int WAVES, int D0, int D1> std::string describe(Fused
 inline std::string describe(ClosedSumsq) { return "sumsq"; }
 inline std::string describe(ClosedBox) { return "box"; }
 inline std::string describe(ClosedHalfspace) { return "halfspace"; }
+template <int EPLP> std::string describe(PrepInst<EPLP>) { return std::to_string(EPLP); }
 
 static const char* ROUTE_NAMES[] = {"Empty", "Closed", "Orbit", "OrbitPsi", "Split", "Sreg", "Scost", "Reg", "Generic"};
 
@@ -99,6 +101,7 @@ int main(int argc, char** argv) {
     else if (cmd == "opsi") { ls >> a; answer(with_orbit_psi_instance(a, say)); }
     else if (cmd == "fused") { ls >> a >> b >> c >> d; answer(with_fused_instance(a, b, c, d, say)); }
     else if (cmd == "closed") { ls >> a; answer(with_closed_instance(a, say)); }
+    else if (cmd == "prep") { ls >> a; answer(with_prep_instance(a, say)); }
     else if (cmd == "variant") {
       ls >> a;
       RouteForce f;

@@ -117,7 +117,7 @@ def test_documented_option_names_are_the_implemented_ones():
     body = src[src.index("constexpr OptionRow OPTION_ROWS[] = {"):]
     body = body[:body.index("};")]
     implemented = set(re.findall(r'^  opt_[a-z0-9_]+\("([a-z0-9_]+)"', body, re.M))
-    hip = open(os.path.join(root, "gaussianvi_amd", "csrc", "gvi_hip.hip")).read()
+    hip = open(os.path.join(root, "gaussianvi_amd", "csrc", "api_inspect.inc")).read()     # the file that defines gvi_set_option
     assert "option_set(ctx->opt, name, value" in hip[hip.index("gvi_status gvi_set_option("):], "gvi_set_option looks the name up in the table"
     assert documented == implemented, (sorted(documented - implemented), sorted(implemented - documented))
 

@@ -260,7 +260,7 @@ def test_interface_is_declared_bound_and_documented():
     assert "8 read-out-space rule" in header
     assert {"gvi_factors_set_readout_rule", "gvi_factors_readout_info"} <= set(_lib.SIGNATURES)
     assert hasattr(api.Context, "factors_set_readout_rule") and hasattr(api.Context, "factors_readout_info")
-    hip = open(os.path.join(CSRC, "gvi_hip.hip")).read()
+    hip = open(os.path.join(CSRC, "api_setup.inc")).read()        # the file that defines gvi_factors_set_readout_rule
     for text in ("only the kinds on linear read-outs", "order is 0 (off) or 2 <= order <= 16 with order^P <= 1024"):
         assert text in hip
     assert "read-out rule kernel supports d <= 32" in open(os.path.join(CSRC, "routes.hpp")).read()

@@ -8,7 +8,8 @@ expected value is written out here or comes from route_model.py; none is read ba
 A table is described by the facts the decision reads of it: the stand-in below carries (N, largest support, tiles) where the
 model reads them off the nodes.  Of the four refusals tests/test_factor_routes_gpu.py::test_refusals pins, "factor dimension
 > 32" is the prep launch's own (it runs before any plan) and is no decision of the header: here its place is taken by the
-generic kernel's and the half-space kernel's d <= 32."""
+generic kernel's and the half-space kernel's d <= 32, and by the miss of with_prep_instance at d = 33 that the launch answers
+with that text."""
 import itertools
 import os
 import subprocess
@@ -16,7 +17,7 @@ import subprocess
 import pytest
 
 import route_model as rm
-from route_model import ARM, BODY, FIXED, H2D, H3D, OPSI_ROWS, QUAD, RANGE, REG, SCOST, SEG2, SEG3, SPLIT_D, SREG, _ceil, _chunks, _route
+from route_model import ARM, BODY, FIXED, H2D, H3D, OPSI_ROWS, PREP, QUAD, RANGE, REG, SCOST, SEG2, SEG3, SPLIT_D, SREG, _ceil, _chunks, _route
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STUB = os.path.join(ROOT, "tests", "stubs", "routes_check.cpp")
@@ -92,6 +93,9 @@ def _list_cases():
         out.append((f"closed {kind}", f"closed 1 {CLOSED[kind]}" if kind in CLOSED else "closed 0"))
     for v in range(-1, 9):
         out.append((f"variant {v}", f"variant 1 {FORCE[v]}" if v in FORCE else "variant 0"))
+    for d in range(1, 41):                                                   # the prep kernels: the first tier that holds d
+        tier = next((eplp for dmax, eplp in PREP if d <= dmax), None)
+        out.append((f"prep {d}", f"prep 0" if tier is None else f"prep 1 {tier}"))
     return out
 
 
@@ -320,6 +324,8 @@ def test_the_cases_cover_what_they_claim():
     assert {v for k, v in lists.items() if k.startswith("orbit ") and v != "orbit 0"} == {"orbit 1 " + v for v in ORBIT.values()}
     assert {v for k, v in lists.items() if k.startswith("fused ") and v != "fused 0"} == {"fused 1 " + v for v in FUSED.values()}
     assert hits("fused") == 4 + 2 + 4                                        # (6, 1..4), (6, 5..6), (2, 1..4)
+    # the prep tiers at their edges, written out: d = 1, 8 | 9, 16 | 17, 32 hit 1 | 4 | 16 elements per lane, d = 33 misses
+    assert [lists[f"prep {d}"] for d in (1, 8, 9, 16, 17, 32, 33)] == ["prep 1 1", "prep 1 1", "prep 1 4", "prep 1 4", "prep 1 16", "prep 1 16", "prep 0"]
     routes = [want.split()[2] for _, want in _route_cases() if want.startswith("route 0")]
     assert set(routes) == set(NAME.values())                                 # every route but Empty and Closed, which have cases of their own
     assert len(_route_cases()) == len(ROWS) * len(VARIANTS) * 2 * 2
